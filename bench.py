@@ -17,6 +17,11 @@ ships; value_raw_format) and the CPU baseline -- decode policy 1 (every layer on
 generate() entry point, beside the oracle's restatement of that path on a one-layer sample.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model opt-30b] [--batch 64 | --global-batch 256] [--prompt 256]
+                    [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what its timed generate() computed as DIR/<name>.npy -- tokens.npy (the ids the
+caller receives, [B, prompt + new], float64) and logits.npy (the last decode step's logits, [B, vocab], float32) -- so that two builds
+can be compared output for output (weights and prompt are seeded: the same arguments give the same inputs).
 
 N > 1: batch-sharded data parallel, one rank per GPU over RCCL; started as-is it launches its own
 `python -m torch.distributed.run --nproc-per-node N` children (before touching any GPU) and relays rank 0's line.
@@ -102,6 +107,8 @@ def build_parser():
                     help="build-defined: with decoding policy 2, this many streamed layers run their decode step on the host cores "
                          "(policy 1 per layer, weights never cross the link); 0 = the reference's uniform policy; -1 = let "
                          "lia_amd.planner.plan_cpu_layers choose from the box's host rates")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the timed generate()'s outputs (tokens.npy, the last step's logits.npy; at most 64 MB in all) to DIR")
     ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)   # CPU test of the --gpus N self-launch
     ap.add_argument("--selftest-dp-line", action="store_true", help=argparse.SUPPRESS)    # CPU (gloo) test of the N > 1 parts of the line
     return ap
@@ -410,6 +417,28 @@ def first_divergence(ids_a, ids_b, T, logits_b=None):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6      # --dump-outputs: every file together
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: each {name: array} -> path/<name>.npy, integer arrays as float64 (exact), the others as float32.  Should the
+    files exceed `budget` bytes, the largest array keeps a fixed, seeded sample of its rows and their indices go to <name>_rows.npy."""
+    import numpy as np
+    out = {k: np.ascontiguousarray(v, dtype=np.float64 if np.issubdtype(v.dtype, np.integer) else np.float32) for k, v in arrays.items()}
+    big = max(out, key=lambda k: out[k].nbytes)
+    rest = sum(v.nbytes for k, v in out.items() if k != big)
+    if rest + out[big].nbytes > budget:
+        rows = out[big].shape[0]
+        keep = max(1, (budget - rest) // (out[big].nbytes // rows + 8))          # + 8: the row's index in <name>_rows.npy
+        idx = np.sort(np.random.default_rng(seed).choice(rows, size=keep, replace=False))
+        out[big] = out[big][idx]
+        out[big + "_rows"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in out.items()}
+
+
 def pmc_traffic(kernel_substr):
     """HBM bytes per launch of the dominant kernel from the committed PMC pass of this same command
     (the newest profiles/r*_opt30b_bench_pmc_hbm.json, tools/profile_round.sh: separate --pmc FETCH_SIZE / WRITE_SIZE runs, gfx950 x2 fetch correction).
@@ -643,6 +672,8 @@ def dp_line_selftest(a):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     a = build_parser().parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "RANK" not in os.environ:
         return self_launch(a.gpus, argv)
     if a.selftest_launcher:
@@ -770,6 +801,14 @@ def main(argv=None):
             st["thr0"] = hostinfo.cgroup_cpu_throttle()
             st["t0"] = time.time()
 
+    last_step = []
+    if a.dump_outputs:
+        # --dump-outputs: keep the newest (logits, next ids) the scheduler returns -- fresh tensors every step, no copy in the timed path
+        def forward_keeping_last(*args, _forward=sched.forward, **kwargs):
+            r = _forward(*args, **kwargs)
+            last_step[:] = r
+            return r
+        sched.forward = forward_keeping_last
     out_ids, lat = generate(model, ids, step_hook=hook, **gen_kwargs)
     sync()
     elapsed = time.time() - st["t0"]
@@ -779,6 +818,11 @@ def main(argv=None):
     wire_dec = sched.decode_stats() if not is_llama else {"launches": 0, "ms": 0.0, "bytes_in": 0.0, "bytes_out": 0.0}
     prof_prefill, (pre_h2d_bytes, pre_h2d_ms) = st["prof_prefill"], st["pre_h2d"]
     assert len(lat) == new and out_ids.shape == (B, T + new)
+    if a.dump_outputs:
+        del sched.forward
+        if rank == 0:
+            dump_outputs(a.dump_outputs, {"tokens": out_ids.numpy(), "logits": last_step[0].float().cpu().numpy()})
+        last_step.clear()
     prefill_ms = 1e3 * lat[0]                             # run_generation.py:345: first-token latency
     dec_mean_s = sum(lat[1:]) / len(lat[1:])              # :346-349 "Average 2... latency"
     timed = sorted(lat[1 + a.warmup:])

@@ -410,6 +410,35 @@ def test_bench_line_contract_on_a_small_model():
     assert d["ids_check"]["cooperative_vs_headline"]["steps_compared"] >= 4 and d["ids_check"]["cooperative_kv_in_hbm_vs_headline"]["steps_compared"] >= 4
 
 
+def test_bench_dump_outputs_are_the_timed_runs_last_step_and_repeat(tmp_path):
+    """bench.py --dump-outputs on opt-125m dims, twice: tokens.npy is the timed generate()'s ids, logits.npy its last decode step's logits
+    (the last generated id is their argmax, EOS suppressed as min_new_tokens asks), and the same arguments give the same files"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, T, steps, warmup = 8, 32, 3, 1
+    got = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", "opt-125m", "--batch", str(B), "--prompt", str(T),
+                            "--steps", str(steps), "--warmup", str(warmup), "--gpu-percentage", "25", "--no-raw-leg", "--no-defer-kv-leg",
+                            "--no-cooperative-leg", "--no-cpu-baseline", "--no-auto-plan", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads(r.stdout.strip().splitlines()[-1])
+        assert d["steps"] == steps and d["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / run)) == ["logits.npy", "tokens.npy"]
+        got.append({k: np.load(tmp_path / run / f"{k}.npy") for k in ("tokens", "logits")})
+    tokens, logits = got[0]["tokens"], got[0]["logits"]
+    assert tokens.dtype == np.float64 and tokens.shape == (B, T + 1 + warmup + steps)
+    assert logits.dtype == np.float32 and logits.shape == (B, 50272) and np.isfinite(logits).all()
+    masked = logits.copy()
+    masked[:, 2] = -np.inf
+    assert (masked.argmax(axis=1) == tokens[:, -1]).all()
+    for k in ("tokens", "logits"):
+        assert np.array_equal(got[0][k], got[1][k]), k
+
+
 def test_a_layer_that_does_not_pack_ships_raw_by_itself():
     """pack10 on the wire, one streamed layer whose values do not fit the format (magnitudes spread over 24 binades: most fall
     outside the symbol window): that layer alone is pinned raw (LayerStore._encode_packed), the others travel packed, and the ids /

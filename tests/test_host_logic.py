@@ -446,6 +446,37 @@ def test_bench_first_divergence_reports_step_and_gap():
     assert same == {"ids_equal": True, "steps_compared": 2, "first_divergent_step": None}
 
 
+def test_bench_dump_outputs_dtypes_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs: integer outputs as float64, the rest as float32, every file within the budget; a larger output keeps a
+    fixed, seeded sample of its rows (the same rows every run) and names them in <name>_rows.npy"""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("lia_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    tokens = np.arange(4 * 9, dtype=np.int64).reshape(4, 9) + 50000
+    logits = np.random.default_rng(1).standard_normal((4, 1000)).astype(np.float32)
+    assert bench.dump_outputs(str(tmp_path / "all"), {"tokens": tokens, "logits": logits}) == {"tokens": [4, 9], "logits": [4, 1000]}
+    t, lg = np.load(tmp_path / "all" / "tokens.npy"), np.load(tmp_path / "all" / "logits.npy")
+    assert t.dtype == np.float64 and (t == tokens).all() and lg.dtype == np.float32 and (lg == logits).all()
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 2**20
+    big = np.random.default_rng(2).standard_normal((64, 1000)).astype(np.float32)            # 256 kB against a 60 kB budget
+    budget = 60_000
+    shapes = [bench.dump_outputs(str(tmp_path / d), {"tokens": tokens, "logits": big}, budget=budget) for d in ("s1", "s2")]
+    assert shapes[0] == shapes[1] and 1 <= shapes[0]["logits"][0] < 64 and shapes[0]["logits_rows"] == shapes[0]["logits"][:1]
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= budget + 3 * 128       # + the .npy headers
+    rows = np.load(tmp_path / "s1" / "logits_rows.npy")
+    assert rows.dtype == np.float64 and (np.diff(rows) > 0).all() and (rows == np.load(tmp_path / "s2" / "logits_rows.npy")).all()
+    assert (np.load(tmp_path / "s1" / "logits.npy") == big[rows.astype(np.int64)]).all()
+
+
+def test_bench_refuses_fewer_than_one_timed_step():
+    """--steps is the number of timed decode steps and ms_per_step divides by it: 0 is refused before anything starts"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_predicted_dp_table_names_what_binds_each_line():
     """planner.predict_dp (DESIGN.md section 6's table, bench.py's config.predicted): the broadcast stream is bound by the root's link at
     every N (throughput grows with the rows, the step does not move), the all-gather stream divides the link time by N until one
