@@ -269,14 +269,15 @@ __device__ __forceinline__ void row_rmsnorm_block(const uint4 (&v)[NV], const ui
   row_rmsnorm_vt<NV, 1, false>(reinterpret_cast<const uint4(&)[1][NV]>(v), reinterpret_cast<const uint4(&)[1][NV]>(gv), nv, H, eps, yr, red);
 }
 
-// LlamaMLP act_fn(gate) * up on two packed bf16 pairs: bf16( bf16(silu(g)) * u ); silu in fp32 through the hardware exp2 /
-// reciprocal (v_exp_f32, v_rcp_f32: 1 ulp each) instead of libm expf + an IEEE division -- the result is rounded to bf16 right
-// after, so a last-bit fp32 difference reaches the output about once in 2^15 elements (HF's own silu is no libm-exact
-// reference either: Sleef on the CPU, a fast-math kernel on GPUs)
+// silu(g) = g / (1 + exp(-g)) in fp32, for the bf16 rounding that follows it: ocml's expf and an IEEE division.  The hardware
+// exp2 / reciprocal (v_exp_f32 with a rounded g log2 e, v_rcp_f32) missed that rounding for bf16 gates whose silu lies within
+// ~1 fp32 ulp of a bf16 tie (g = 5.9375: every one of them, a whole bf16 ulp of silu); below g = -88.7 exp(-g) overflows, and
+// silu is g exp(g) to far below one bf16 ulp there (the hardware form returned 0 from -87.5 on, where silu(g) is ~1e-37).
+__device__ __forceinline__ float lia_silu(float g) { return g < -88.0f ? g * expf(g) : g / (1.0f + expf(-g)); }
+
+// LlamaMLP act_fn(gate) * up on two packed bf16 pairs: bf16( bf16(silu(g)) * u )
 __device__ __forceinline__ uint32_t lia_silu_mul_pair(uint32_t gw, uint32_t uw) {
-  const float g0 = bf2f(gw & 0xffff), g1 = bf2f(gw >> 16);
-  const float s0 = rbf(g0 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * g0)));
-  const float s1 = rbf(g1 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * g1)));
+  const float s0 = rbf(lia_silu(bf2f(gw & 0xffff))), s1 = rbf(lia_silu(bf2f(gw >> 16)));
   return pack_bf16x2(s0 * bf2f(uw & 0xffff), s1 * bf2f(uw >> 16));
 }
 
