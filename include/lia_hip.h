@@ -152,7 +152,11 @@ int lia_kv_deliver_batch_ms(lia_ctx* ctx, double* ms);
 int lia_layernorm(const lia_bf16* x, long ldx, const lia_bf16* g, const lia_bf16* b, lia_bf16* y, long ldy, long rows,
                   int H, float eps, void* stream);
 /* torch.matmul(x, w.t()) + bias [relu] [residual + .], decoder.py:79-105,229,310; attentions.py:393-394,418.
- * y[M,N] row-major with leading dimension ldy.  bias / residual may be NULL.  split_k: 0 = heuristic. */
+ * y[M,N] row-major with leading dimension ldy.  bias / residual may be NULL.  split_k: 0 = heuristic.
+ * Preconditions, else LIA_ERR_INVALID and nothing is launched: N % 16 == 0 and K % 64 == 0; ldx % 8 == 0 with x and w 16-byte
+ * aligned (the kernels stage 16-byte row pieces); bias 8-byte aligned.  The skinny regime (M <= 256 and K % 128 == 0) stores
+ * 4 columns at a time: ldy % 4 == 0 and ldr % 4 == 0, y and residual 8-byte aligned.  Every other shape runs the tiled kernels,
+ * which store and read the residual 8 columns at a time: ldy % 8 == 0 and ldr % 8 == 0, y and residual 16-byte aligned. */
 int lia_linear(lia_ctx* ctx, const lia_bf16* x, long ldx, const lia_bf16* w, const lia_bf16* bias,
                const lia_bf16* residual, long ldr, lia_bf16* y, long ldy, int M, int N, int K, int relu, int split_k,
                void* stream);

@@ -456,7 +456,11 @@ static int gemm_checked(lia_ctx* ctx, const bf16_t* x, long ldx, const bf16_t* w
     double bytes = 2.0 * ((double)N * K + (double)M * K + (double)M * N);
     ctx->prof_recs->push_back({regime, bytes, 2.0 * M * (double)N * K});
   }
-  if (rc) { lia_set_error("linear: unsupported shape M=%d N=%d K=%d", M, N, K); return LIA_ERR_INVALID; }
+  if (rc) {
+    lia_set_error("linear: unsupported shape or layout M=%d N=%d K=%d ldx=%ld ldy=%ld ldr=%ld (lia_hip.h, lia_linear: 16-byte x / w rows, "
+                  "whole 8-byte stores, 16-byte ones unless M <= 256 and K %% 128 == 0)", M, N, K, ldx, om.ld[0], ep.residual ? ep.ldr : 0L);
+    return LIA_ERR_INVALID;
+  }
   HIP_TRY(hipGetLastError());
   return LIA_OK;
 }

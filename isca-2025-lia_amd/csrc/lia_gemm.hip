@@ -924,12 +924,15 @@ static void launch_skinny2(const bf16_t* x, long ldx, const bf16_t* W, long ldw,
                      split > 1 ? partial : nullptr, ep, om);
 }
 
+static inline bool lia_misaligned(const void* p, unsigned bytes) { return ((uintptr_t)p & (bytes - 1)) != 0; }
+
 // the combine kernel that also runs `post`, if this shape has one; false: nothing launched
 static bool launch_fused_combine(const float* ws, int split, int M, int N, const LiaEpilogue& ep, const LiaOutMap& om, const LiaPost& post,
                                  LiaGemmOpts* opts, hipStream_t st) {
   if (opts && !opts->fuse_combine) return false;
   if (post.kind == LIA_POST_LAYERNORM || post.kind == LIA_POST_RMSNORM) {
-    if (om.seg_n != N || om.cache_mode[0] || (N & 7) || (N >> 3) > LIA_ROW_THREADS * 2 || (om.ld[0] & 7) || (post.ldo & 7) || !post.g || !post.out) return false;
+    if (om.seg_n != N || om.cache_mode[0] || (N & 7) || (N >> 3) > LIA_ROW_THREADS * 2 || (om.ld[0] & 7) || (post.ldo & 7) || !post.g || !post.out ||
+        lia_misaligned(om.base[0], 16) || lia_misaligned(post.out, 16)) return false;
     if (post.kind == LIA_POST_LAYERNORM && !post.b) return false;
 #define LIA_NORM_COMBINE(K)                                                                                                            \
     do {                                                                                                                               \
@@ -942,7 +945,7 @@ static bool launch_fused_combine(const float* ws, int split, int M, int N, const
     return true;
   }
   if (post.kind == LIA_POST_SILU_MUL) {
-    if ((N & 7) || (post.ldo & 3) || !post.out || (post.gu_block && (post.gu_block != LIA_GU_BLOCK || (N % (2 * LIA_GU_BLOCK))))) return false;
+    if ((N & 7) || (post.ldo & 3) || !post.out || lia_misaligned(post.out, 8) || (post.gu_block && (post.gu_block != LIA_GU_BLOCK || (N % (2 * LIA_GU_BLOCK))))) return false;
     const long nq = (long)M * (N >> 3);
     hipLaunchKernelGGL(lia_splitk_reduce_silu_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, ws, split, M, N, ep, post);
     if (opts) ++opts->fused_combines[post.kind];
@@ -958,7 +961,25 @@ static bool launch_fused_combine(const float* ws, int split, int M, int N, const
   return false;
 }
 
-// Returns 0 on success, -1 on unsupported shape.  workspace is only touched when split-K is chosen.
+// What the chosen regime can load and store (the preconditions lia_hip.h states for lia_linear).  Both regimes stage x / W rows
+// by 16-byte LDS-DMA.  The skinny kernel and the split-K combines store 4 columns (8 bytes) of one segment at a time and read bias /
+// residual 4 at a time; the tiled epilogue (epilogue_via_lds_part) stores 8 columns (16 bytes) per lane into the ONE segment of the
+// lane's first column and reads the residual 8 columns at a time -- so there a segment must be a whole number of 8-column stores.
+static bool gemm_layout_ok(const bf16_t* x, long ldx, const bf16_t* W, long ldw, int N, const LiaEpilogue& ep, const LiaOutMap& om,
+                           bool tiled) {
+  const int q = tiled ? 8 : 4;                       // columns per store
+  if (om.seg_n <= 0 || om.seg_n % q || (N + om.seg_n - 1) / om.seg_n > LIA_OUT_SEGS) return false;
+  if ((ldx & 7) || (ldw & 7) || lia_misaligned(x, 16) || lia_misaligned(W, 16)) return false;
+  if (ep.bias && lia_misaligned(ep.bias, 8)) return false;
+  if (ep.residual && ((ep.ldr % q) || lia_misaligned(ep.residual, 2 * q))) return false;
+  for (int s = 0; s * om.seg_n < N; ++s)
+    if (!om.base[s] || (om.ld[s] % q) || lia_misaligned(om.base[s], 2 * q) ||
+        (om.cache_mode[s] && (om.T <= 0 || om.Bc <= 0 || om.b0 < 0 || om.pos0 < 0))) return false;
+  return true;
+}
+
+// Returns 0 on success, -1 on an unsupported shape or layout (gemm_layout_ok), before anything is launched.  workspace is only
+// touched when split-K is chosen.
 // opts (nullable = defaults): the per-context switches and counters (LiaGemmOpts, lia_common.h; lia_ctx_set_option) -- the
 // library keeps no process-wide setting.
 extern "C" int lia_gemm_launch(const bf16_t* x, long ldx, const bf16_t* W, long ldw, int M, int N, int K,
@@ -972,9 +993,12 @@ extern "C" int lia_gemm_launch(const bf16_t* x, long ldx, const bf16_t* W, long 
   // roofline timing; the split-K combine kernel is outside the bracket).  *regime: 1 skinny, 2 tiled.
   if (regime) *regime = 0;
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  if ((N % 16) != 0 || (om->seg_n % 4) != 0) return -1;
+  if ((N % 16) != 0) return -1;
+  const bool skinny = M <= 256 && (K % (2 * S2_BK)) == 0;
+  if (!skinny && (K % TL_BK) != 0) return -1;
+  if (!gemm_layout_ok(x, ldx, W, ldw, N, *ep, *om, !skinny)) return -1;
   const bool fuse = !opts || opts->fuse_combine;
-  if (M <= 256 && (K % (2 * S2_BK)) == 0) {
+  if (skinny) {
     constexpr int WAVES = 8;
     const int nchunks = K / S2_BK;
     // Two workgroup shapes.  RT = 1: 128 weight rows, LDS-DMA moves (128 + 16 MT)/128 bytes per weight byte, two
@@ -1032,7 +1056,7 @@ extern "C" int lia_gemm_launch(const bf16_t* x, long ldx, const bf16_t* W, long 
                            M > 64 && M <= 128 && force_split <= 0 && (N + 127) / 128 >= 192 && !ep->residual;
     if (glu_shape) {
       rt = 1; mcut = false; split = 1;
-      if (post_done && fuse && post->out && (post->ldo & 3) == 0) {
+      if (post_done && fuse && post->out && (post->ldo & 3) == 0 && !lia_misaligned(post->out, 8)) {
         ep_s.glu = 1;
         memset(&om_s, 0, sizeof(om_s));
         om_s.base[0] = post->out; om_s.ld[0] = post->ldo; om_s.seg_n = N / 2; om_s.T = 1;
@@ -1068,14 +1092,13 @@ extern "C" int lia_gemm_launch(const bf16_t* x, long ldx, const bf16_t* W, long 
     }
     return 0;
   }
-  if ((K % TL_BK) != 0) return -1;
   if (regime) *regime = 2;
   // the tiled kernels' epilogue writes silu(gate) * up itself when the weight rows are interleaved (LiaEpilogue::glu): the
   // [M, 2F] intermediate of a prefill (7.5 GB per Llama-3-8B layer at B 128 x T 1024) is never written nor read back
   LiaEpilogue ep_t = *ep;
   LiaOutMap om_t = *om;
   if (post && post_done && fuse && post->kind == LIA_POST_SILU_MUL && post->gu_block == LIA_GU_BLOCK &&
-      (N % (2 * LIA_GU_BLOCK)) == 0 && post->out && (post->ldo & 7) == 0 && !ep->residual) {
+      (N % (2 * LIA_GU_BLOCK)) == 0 && post->out && (post->ldo & 7) == 0 && !lia_misaligned(post->out, 16) && !ep->residual) {
     ep_t.glu = 1;
     memset(&om_t, 0, sizeof(om_t));
     om_t.base[0] = post->out; om_t.ld[0] = post->ldo; om_t.seg_n = N / 2; om_t.T = 1;

@@ -13,13 +13,16 @@ import numpy as np
 ROWS_PER_CHUNK = 256        # norms work on this many rows at a time: a 4097 x 16392 input stays a few hundred MB in float64
 
 
-def rnd(x):
-    """float64 -> the nearest bf16 value (ties to even), still as float64; subnormals, overflow to inf and NaN as bf16 has them"""
+def rnd(x, ties_away=False):
+    """float64 -> the nearest bf16 value (ties to even), still as float64; subnormals, overflow to inf and NaN as bf16 has them.
+    ties_away (a mutant): ties rounded away from zero."""
     x = np.asarray(x, dtype=np.float64)
     _, e = np.frexp(x)                                  # |x| = m 2^e, 0.5 <= m < 1: 8 significant bits -> quantum 2^(e - 8)
     qe = np.maximum(e - 8, -133)                        # below 2^-126 the quantum stays 2^-133 (bf16 subnormals)
     with np.errstate(over="ignore", invalid="ignore"):
-        y = np.ldexp(np.rint(np.ldexp(x, -qe)), qe)
+        s = np.ldexp(x, -qe)
+        s = np.copysign(np.floor(np.abs(s) + 0.5), s) if ties_away else np.rint(s)
+        y = np.ldexp(s, qe)
         y = np.where(np.abs(y) >= 2.0 ** 128, np.copysign(np.inf, x), y)
     return np.where(np.isfinite(x), y, x)
 
@@ -97,6 +100,46 @@ def rope(x, cosb, sinb, pos, heads, round_products=True):
     return bits(rnd(r(xf * c) + r(rot * s))).reshape(rows, heads * d)        # roundings: x cos, rot sin, their sum
 
 
+def matmul(x, w, drop_last_k=False):
+    """x [M, K] . w [N, K]^T in float64 (bf16 bit patterns in).  drop_last_k (a mutant): the last K chunk of 64 left out."""
+    K = w.shape[1]
+    k = K - 64 if drop_last_k else K
+    return f64(np.ascontiguousarray(x)[:, :k]) @ f64(np.ascontiguousarray(w)[:, :k]).T
+
+
+def matmul_slack(x, w):
+    """delta = K 2^-24 (|x| . |w|^T): how far any sequential fp32 accumulation of x . w^T can lie from the exact sum"""
+    K = w.shape[1]
+    return K * 2.0 ** -24 * (np.abs(f64(x)) @ np.abs(f64(w)).T)
+
+
+def linear(x, w, bias=None, residual=None, relu=False, *, acc=None, round_acc=True, round_before_residual=True, ties_away=False,
+           drop_last_k=False, bias_seg=None):
+    """torch.matmul(x, w.t()) + bias [relu] [residual + .] with the reference's (and the GPU epilogue's) rounding points, each
+    straight from float64:
+        t = bf16(acc);  t = bf16(t + bias);  t = max(t, 0);  y = bf16(residual + t)
+    acc: the float64 x . w^T (computed when None); passing acc -/+ delta evaluates the same chain there.  Every step is monotone
+    non-decreasing in acc, so [linear(acc - delta), linear(acc + delta)] holds every result an accumulation within delta gives.
+    Mutants: round_acc=False (no rounding after the matmul: the bias goes onto the unrounded sum), round_before_residual=False (the
+    value before the residual add not rounded), ties_away (ties rounded away from zero at every rounding point), drop_last_k
+    (the last K chunk of 64 left out of the sum), bias_seg=S (the bias of column n taken from column n + S: the neighbouring
+    segment of an out-map with S columns per segment)."""
+    a = matmul(x, w, drop_last_k) if acc is None else np.asarray(acc, dtype=np.float64)
+    r = lambda v: rnd(v, ties_away)
+    last = residual is not None and not round_before_residual         # the rounding in front of the residual add is skipped
+    t = r(a) if round_acc and not (last and bias is None) else a
+    if bias is not None:
+        b = f64(bias)
+        if bias_seg:
+            b = np.roll(b, -bias_seg)
+        t = t + b if last else r(t + b)
+    if relu:
+        t = np.maximum(t, 0.0)
+    if residual is not None:
+        t = r(f64(residual) + t)
+    return bits(r(t))                                                               # (a no-op unless a mutant left t unrounded)
+
+
 def split_gate_up(gu, F, gu_block):
     """gu [M, 2F] -> (gate [M, F], up [M, F]): gu_block 0: columns [gate | up]; 32: blocks of 32 gate | 32 up columns"""
     M = gu.shape[0]
@@ -104,6 +147,13 @@ def split_gate_up(gu, F, gu_block):
         v = gu.reshape(M, F // gu_block, 2, gu_block)
         return v[:, :, 0, :].reshape(M, F), v[:, :, 1, :].reshape(M, F)
     return gu[:, :F], gu[:, F:2 * F]
+
+
+def silu_mul_glu(gu, gu_block=32):
+    """silu_mul of a gate | up projection's output gu [M, 2F] in the interleaved layout (blocks of gu_block gate | gu_block up
+    columns, LIA_GU_BLOCK) or, gu_block 0, as [gate | up] halves"""
+    g, u = split_gate_up(gu, gu.shape[1] // 2, gu_block)
+    return silu_mul(g, u)
 
 
 def silu_mul(g, u):

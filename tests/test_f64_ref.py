@@ -93,3 +93,38 @@ def test_argmax_takes_the_first_maximum_and_skips_the_suppressed_token():
     x[2, :] = 0xff80                                                      # all -inf
     assert R.argmax(x)[1:3].tolist() == [3, 0] and R.argmax(x, last_on_ties=True)[1] == 40
     assert R.argmax(x, suppress=3)[1] == 17 and R.argmax(x, suppress=int(R.argmax(x)[0]))[0] != R.argmax(x)[0]
+
+
+@pytest.mark.parametrize("M,N,K,has_bias,has_res,relu", [(37, 256, 768, True, False, False), (64, 96, 2048, True, True, False),
+                                                         (5, 512, 4096, True, False, True), (130, 64, 320, False, True, False),
+                                                         (16, 128, 1024, False, False, False), (9, 80, 4160, True, True, True)])
+def test_linear_matches_oracle(oracle, M, N, K, has_bias, has_res, relu):
+    """f64_ref.linear against the oracle's GPU-semantics linear (split_bias: bf16(acc) -> bf16(+ bias) -> relu -> bf16(res + .)),
+    and the oracle's fp32 result inside the bracket [linear(acc - delta), linear(acc + delta)] the GPU tests use"""
+    x, w = rand_bits(40, (M, K)), rand_bits(41, (N, K), K ** -0.5)
+    b = rand_bits(42, (N,), 0.5) if has_bias else None
+    r = rand_bits(43, (M, N)) if has_res else None
+    orc = oracle.linear(x, w, b, r, relu, split_bias=True)
+    agree(R.linear(x, w, b, r, relu), orc, f"linear {M}x{N}x{K} bias {has_bias} res {has_res} relu {relu}")
+    acc, d = R.matmul(x, w), R.matmul_slack(x, w)
+    lo, hi, o = R.f64(R.linear(x, w, b, r, relu, acc=acc - d)), R.f64(R.linear(x, w, b, r, relu, acc=acc + d)), R.f64(orc)
+    assert ((lo <= o) & (o <= hi)).all()
+
+
+def test_linear_rounding_points():
+    """the chain's rounding points and its mutants on hand-made sums: ties to even at bf16(acc), at bf16(t + bias) and at
+    bf16(residual + t); each mutant switch changes at least one of these outputs"""
+    one = lambda v: R.bits(np.array([v], np.float64))
+    x = R.bits(np.ones((1, 128)))
+    w = R.bits(np.concatenate([np.full(64, 0.0), np.full(64, 4.0)])[None, :])     # x . w = 256, all of it in the last K chunk
+    acc = np.array([[257.0]])                                    # a tie between 256 and 258: even -> 256
+    assert R.f64(R.linear(x, w, acc=acc))[0, 0] == 256.0
+    assert R.f64(R.linear(x, w, acc=acc, ties_away=True))[0, 0] == 258.0
+    assert R.f64(R.linear(x, w, one(1.0), acc=acc))[0, 0] == 256.0            # bf16(256 + 1) = 256: the rounded sum came first
+    assert R.f64(R.linear(x, w, one(1.0), acc=acc, round_acc=False))[0, 0] == 258.0   # bf16(257 + 1) = 258
+    assert R.f64(R.linear(x, w, None, one(1.0), acc=acc))[0, 0] == 256.0
+    assert R.f64(R.linear(x, w, None, one(1.0), acc=acc, round_before_residual=False))[0, 0] == 258.0
+    assert R.f64(R.linear(x, w, None, None, True, acc=-acc))[0, 0] == 0.0
+    assert R.f64(R.linear(x, w))[0, 0] == 256.0 and R.f64(R.linear(x, w, drop_last_k=True))[0, 0] == 0.0
+    b2 = R.bits(np.array([1.0, 2.0]))
+    assert R.f64(R.linear(x, np.concatenate([w, w]), b2, acc=np.array([[0.0, 0.0]]), bias_seg=1)).tolist() == [[2.0, 1.0]]
