@@ -290,14 +290,30 @@ int lia_stream_mark_ready(lia_streamer* s, int slot);
  * the layer does not fit the format and must travel raw. */
 size_t lia_pack10_bound(size_t n_values);
 int lia_pack10_encode(const lia_bf16* src_device, size_t n_values, char* dst_device, size_t dst_capacity, size_t* out_bytes);
-/* Host-side consistency check of an encoded buffer's 256-byte header (magic, version, value count == the slot's, every offset
- * inside `staged_bytes`, counts within their capacities) -- run when a packed layer is mapped from a checkpoint file or pinned,
- * because the decode kernel takes its loop bounds and offsets from the header.  0 = consistent, negative = the failed check. */
+/* Host-side consistency check of an encoded buffer (`header_host`: all staged_bytes of it): the header (magic, version, value
+ * count == the slot's, every offset inside `staged_bytes`, counts within their capacities), then the region and offset tables
+ * and the escape records -- run when a packed layer is mapped from a checkpoint file or pinned, because the decode kernel takes
+ * its loop bounds and offsets from the header and its stream positions from the tables.  0 = consistent, negative = the failed
+ * check (LIA_P10_*). */
 int lia_pack10_validate(const void* header_host, size_t staged_bytes, size_t n_values);
+/* lia_pack10_validate's codes.  The checks beyond the header read the region tables, the two offset tables, the last block's
+ * planes and level-2 codes and the escape records (O(n / 1024 + n_esc)), never beyond staged_bytes; they bound every address
+ * the decode and patch kernels form, provided the decode reads from a staging buffer of lia_pack10_bound(n_values) bytes. */
+#define LIA_P10_SHORT (-1)    /* NULL, or fewer than 256 staged bytes                                                      */
+#define LIA_P10_FORMAT (-2)   /* magic / version                                                                           */
+#define LIA_P10_COUNT (-3)    /* value count / region count differs from the slot's                                        */
+#define LIA_P10_OFFSET (-4)   /* a section outside staged_bytes, overlapping the next or not 256-byte aligned; staged_bytes
+                                 or a stream's read window beyond lia_pack10_bound(n_values)                               */
+#define LIA_P10_CAPACITY (-5) /* a count beyond its capacity, or the overflow flag                                         */
+#define LIA_P10_REGION (-6)   /* a region table with e3 outside 1..242 or a symbol twice                                   */
+#define LIA_P10_TABLE (-7)    /* tab2 / tab3 not starting at 0, decreasing, stepping by more than 1024 (tab3 by more than
+                                 tab2), far from n_l2 / n_l3, or the last block's counts disagree with its planes / codes  */
+#define LIA_P10_ESCAPE (-8)   /* more escape records than level-3 codes, or a record index >= n_values                     */
 /* Rebuild the raw bf16 values of an encoded buffer (device -> device), asynchronous on `stream` (NULL = the default
  * stream): the kernels the streamer runs, exposed for re-tiering a layer that the host holds in a packed format
  * (model placement, lia/modeling_opt.py:229-268) and for the round-trip tests.  format: 10 (the argument is kept so that a later
- * format needs no new entry point). */
+ * format needs no new entry point).  A buffer that lia_pack10_validate passed is decoded without a read outside src_device
+ * when src_device holds lia_pack10_bound(n_values) bytes. */
 int lia_pack_decode(const char* src_device, lia_bf16* dst_device, size_t n_values, int format, void* stream);
 /* format: 10 */
 int lia_stream_prefetch_packed(lia_streamer* s, int slot, const void* host_ptr, size_t packed_bytes, size_t n_values, int format,

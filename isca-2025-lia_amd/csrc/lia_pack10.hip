@@ -10,6 +10,7 @@
 // History: pack12 (r01: one 4-bit code per value against a 14-binade window, 12 bits) and pack11 (r01: a 3-bit code in bit-planes
 // + a 4-bit overflow stream, 11.13 bits) were the first two generations; pack10 replaced them as the default in r02 and they were
 // removed in r05 (git history; LABNOTES.md has their measurements: 88.7 / 95.7 / 98.6 decode tokens/s for 12 / 11 / 10).
+#include "../../include/lia_hip.h"
 #include "lia_common.h"
 #include <string.h>
 
@@ -420,7 +421,7 @@ __global__ __launch_bounds__(256) void lia_pack10_patch_kernel(const char* __res
   const unsigned n = hd->n_esc;
   for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     uint2 r = esc[i];
-    dst[r.x] = (bf16_t)r.y;
+    if (r.x < hd->n) dst[r.x] = (bf16_t)r.y;      // second guard behind lia_pack10_validate: never write outside the layer
   }
 }
 
@@ -473,21 +474,88 @@ extern "C" int lia_pack10_encode(const bf16_t* src, size_t n_values, char* dst, 
 }
 
 // Host-side check of an encoded buffer BEFORE it is trusted: the decode kernel sizes its loops and takes every offset
-// from the header, so a stale or corrupt layer file whose header disagrees with the slot would write past it.  `buf`: the first
-// 256 bytes (host memory: a mapped checkpoint file, a pinned copy); staged_bytes: the bytes the caller holds / will copy;
-// n_values: the bf16 values the destination slot has room for.  0 = consistent, negative = the reason (lia_last_error has the text).
+// from the header, so a stale or corrupt layer file whose header disagrees with the slot would write past it.  `buf`: the whole
+// staged buffer (host memory: a mapped checkpoint file, a pinned copy); staged_bytes: the bytes the caller holds / will copy;
+// n_values: the bf16 values the destination slot has room for.  0 = consistent, negative = the failed check (LIA_P10_* in
+// lia_hip.h).  Nothing beyond staged_bytes is read, and the header checks come first.
+//
+// What the checks bound, block by block (blk < nblk = n / 1024), for the kernels that read the buffer:
+//   * rtab[blk >> 6], a, b0, b1, tab2[blk], tab3[blk]: inside their sections (every section ends before the next one starts);
+//   * each region: e3 in [1, 242], so the decode kernel's byte-wise e3 + i tables (i <= 13) carry into no other byte; six
+//     distinct symbols;
+//   * tab2 / tab3 start at 0, never decrease, step by at most 1024 (tab3 by at most tab2's step), end within 1024 codes of n_l2 /
+//     n_l3; the last block's level-2 count and level-3 count are checked against its planes and level-2 codes exactly (earlier
+//     blocks are not: that is a scan of n / 4 bytes);
+//   * escape records: n_esc <= n_l3, every index < n (lia_pack10_patch_kernel skips any other as a second guard).
+// lp10_get_bits reads the 32-bit words `word` and `word + 1` (and `word + 2` when 4 * n3 + bitoff % 32 > 64) at bit offset
+// 2 (tab2[blk] + ex2) or 4 (tab3[blk] + ex3), where the wave's exclusive prefix ex2 / ex3 plus the lane's own n2 / n3 is at most
+// 1024 whatever the planes hold.  With tab2[blk] <= n_l2 and tab3[blk] <= n_l3 every read lies below
+//   off_l2 + (n_l2 + 1024) / 4 + 8      and      off_l3 + (n_l3 + 1024) / 2 + 8,
+// and both (and staged_bytes) are checked to be <= lia_pack10_bound(n): the size of every staging buffer a decode reads
+// (lia_stream_* stage into lia_pack10_bound of the slot's values; model.py stages a file-backed layer the same way).  A consistent
+// encoding reads only its streams' 16 bytes of padding; the margin above covers planes that disagree with the tables (garbage
+// out, but no read outside the staging buffer).  Every offset is a multiple of 256, as the encoder writes them, so the kernels'
+// vector loads stay aligned.
+static bool lp10_table_ok(const uint32_t* tab, const uint32_t* lim, size_t nblk, uint64_t total) {
+  if (tab[0] != 0) return false;
+  for (size_t b = 1; b < nblk; ++b) {
+    const uint32_t step = tab[b] - tab[b - 1];
+    if (tab[b] < tab[b - 1] || step > 1024 || (lim && step > lim[b] - lim[b - 1])) return false;
+  }
+  return tab[nblk - 1] <= total && total - tab[nblk - 1] <= 1024;
+}
+
 extern "C" int lia_pack10_validate(const void* buf, size_t staged_bytes, size_t n_values) {
-  if (!buf || staged_bytes < sizeof(LiaPack10Header)) return -1;
+  if (!buf || staged_bytes < sizeof(LiaPack10Header)) return LIA_P10_SHORT;
   LiaPack10Header hd;
   memcpy(&hd, buf, sizeof(hd));
-  if (hd.magic != LP10_MAGIC || hd.version != 2) return -2;
-  if (hd.n != n_values || (n_values % 1024) || hd.region_shift != LP10_REGION_SHIFT || hd.n_regions != (uint32_t)lp10_regions(n_values)) return -3;
+  if (hd.magic != LP10_MAGIC || hd.version != 2) return LIA_P10_FORMAT;
+  if (hd.n != n_values || (n_values % 1024) || hd.region_shift != LP10_REGION_SHIFT || hd.n_regions != (uint32_t)lp10_regions(n_values)) return LIA_P10_COUNT;
   const uint64_t offs[] = {hd.off_rtab, hd.off_a, hd.off_b0, hd.off_b1, hd.off_tab2, hd.off_tab3, hd.off_l2, hd.off_l3, hd.off_esc};
   uint64_t prev = sizeof(LiaPack10Header);
-  for (uint64_t o : offs) { if (o < prev || o > staged_bytes) return -4; prev = o; }
-  if (hd.off_a + n_values > hd.off_b0 || hd.off_b1 + n_values / 8 > hd.off_tab2) return -4;
-  if (hd.overflow || hd.n_esc > hd.esc_cap || hd.n_l2 > hd.l2_cap || hd.n_l3 > hd.l3_cap || hd.n_l2 > n_values || hd.n_l3 > n_values) return -5;
-  if (hd.off_l2 + (hd.n_l2 + 3) / 4 > hd.off_l3 || hd.off_l3 + (hd.n_l3 + 1) / 2 > hd.off_esc || hd.off_esc + (uint64_t)hd.n_esc * 8 > staged_bytes) return -4;
+  for (uint64_t o : offs) { if (o < prev || o > staged_bytes) return LIA_P10_OFFSET; prev = o; }
+  if (hd.off_a + n_values > hd.off_b0 || hd.off_b1 + n_values / 8 > hd.off_tab2) return LIA_P10_OFFSET;
+  if (hd.overflow || hd.n_esc > hd.esc_cap || hd.n_l2 > hd.l2_cap || hd.n_l3 > hd.l3_cap || hd.n_l2 > n_values || hd.n_l3 > n_values) return LIA_P10_CAPACITY;
+  if (hd.off_l2 + (hd.n_l2 + 3) / 4 > hd.off_l3 || hd.off_l3 + (hd.n_l3 + 1) / 2 > hd.off_esc || hd.off_esc + (uint64_t)hd.n_esc * 8 > staged_bytes) return LIA_P10_OFFSET;
+  // ---- beyond the header: the sections the kernels dereference (O(n / 1024 + n_esc), all below staged_bytes by the checks above)
+  const size_t nblk = n_values / 1024;
+  if (nblk == 0) return LIA_P10_COUNT;                            // no encoding has zero values (and the tables need a last block)
+  for (uint64_t o : offs)
+    if (o % 256) return LIA_P10_OFFSET;
+  if (hd.off_rtab + (uint64_t)hd.n_regions * sizeof(Lp10Region) > hd.off_a || hd.off_b0 + n_values / 8 > hd.off_b1 ||
+      hd.off_tab2 + nblk * 4 > hd.off_tab3 || hd.off_tab3 + nblk * 4 > hd.off_l2)
+    return LIA_P10_OFFSET;
+  const uint64_t cap = lia_pack10_bound(n_values);
+  if (staged_bytes > cap || hd.off_l2 + (hd.n_l2 + 1024) / 4 + 8 > cap || hd.off_l3 + (hd.n_l3 + 1024) / 2 + 8 > cap) return LIA_P10_OFFSET;
+  const char* p = (const char*)buf;
+  for (uint32_t r = 0; r < hd.n_regions; ++r) {
+    Lp10Region rt;
+    memcpy(&rt, p + hd.off_rtab + (size_t)r * sizeof(rt), sizeof(rt));
+    if (rt.e3 < 1 || rt.e3 > 255 - 14 + 1) return LIA_P10_REGION;
+    const uint32_t s[6] = {rt.sym1 & 0xff, (rt.sym1 >> 8) & 0xff, (rt.sym1 >> 16) & 0xff,
+                           rt.sym2 & 0xff, (rt.sym2 >> 8) & 0xff, (rt.sym2 >> 16) & 0xff};
+    for (int i = 0; i < 6; ++i)
+      for (int j = 0; j < i; ++j)
+        if (s[i] == s[j]) return LIA_P10_REGION;
+  }
+  const uint32_t* tab2 = (const uint32_t*)(p + hd.off_tab2);
+  const uint32_t* tab3 = (const uint32_t*)(p + hd.off_tab3);
+  if (!lp10_table_ok(tab2, nullptr, nblk, hd.n_l2) || !lp10_table_ok(tab3, tab2, nblk, hd.n_l3)) return LIA_P10_TABLE;
+  // the last block: its level-2 count from the planes, its level-3 count from its level-2 codes (the last ones of the stream)
+  const uint16_t* b0 = (const uint16_t*)(p + hd.off_b0);
+  const uint16_t* b1 = (const uint16_t*)(p + hd.off_b1);
+  uint64_t last2 = 0, last3 = 0;
+  for (size_t g = (nblk - 1) * 64; g < nblk * 64; ++g) last2 += __builtin_popcount((uint32_t)(b0[g] & b1[g]));
+  if (last2 != hd.n_l2 - tab2[nblk - 1] || hd.n_l3 - tab3[nblk - 1] > last2) return LIA_P10_TABLE;
+  const uint8_t* l2 = (const uint8_t*)(p + hd.off_l2);
+  for (uint64_t i = tab2[nblk - 1]; i < hd.n_l2; ++i) last3 += ((l2[i >> 2] >> (2 * (i & 3))) & 3) == 3;
+  if (last3 != hd.n_l3 - tab3[nblk - 1]) return LIA_P10_TABLE;
+  if (hd.n_esc > hd.n_l3) return LIA_P10_ESCAPE;
+  for (uint32_t i = 0; i < hd.n_esc; ++i) {
+    uint32_t idx;
+    memcpy(&idx, p + hd.off_esc + (size_t)i * 8, sizeof(idx));
+    if (idx >= n_values) return LIA_P10_ESCAPE;
+  }
   return 0;
 }
 

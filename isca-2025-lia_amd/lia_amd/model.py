@@ -204,7 +204,8 @@ class LayerStore:
             return dev
         if self.shard:
             raise ValueError("this rank holds one slice of the layer's wire bytes (allgather streaming); it cannot be re-tiered here")
-        enc = torch.empty(self.stream_bytes, dtype=torch.uint8, device="cuda")
+        # staged in lia_pack10_bound bytes: the size lia_pack10_validate bounds the decode kernel's reads by
+        enc = torch.empty(self._lib.lia_pack10_bound(self.nbytes // 2), dtype=torch.uint8, device="cuda")
         N.check(self._lib.lia_memcpy_h2d(enc.data_ptr(), self._ptr, self.stream_bytes), "lia_memcpy_h2d")
         N.check(self._lib.lia_pack_decode(ctypes.c_void_p(enc.data_ptr()), ctypes.c_void_p(dev.data_ptr()), self.nbytes // 2,
                                           int(self.packed), None), "lia_pack_decode")
@@ -428,7 +429,9 @@ class LayerStore:
         rc = self._lib.lia_pack10_validate(ctypes.c_void_p(host_ptr), nbytes, self.nbytes // 2)
         if rc != 0:
             why = {-1: "shorter than a header", -2: "bad magic / version", -3: "value count differs from this model's layer",
-                   -4: "an offset points outside the buffer", -5: "a count exceeds its capacity"}.get(rc, f"code {rc}")
+                   -4: "an offset points outside the buffer", -5: "a count exceeds its capacity",
+                   -6: "a region table is invalid", -7: "an offset table is inconsistent",
+                   -8: "an escape record is invalid"}.get(rc, f"code {rc}")       # LIA_P10_* (include/lia_hip.h)
             raise ValueError(f"{what}: not a consistent pack10 layer of {self.nbytes // 2} values ({why}); the file is stale or corrupt")
 
     def set_from_file_to_device(self, path, offset, nbytes, fmt):
@@ -445,7 +448,7 @@ class LayerStore:
             self._validate_packed(host.ctypes.data, nbytes, path)
         dev = torch.empty(self.nbytes, dtype=torch.uint8, device="cuda")
         if fmt:
-            enc = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+            enc = torch.empty(self._lib.lia_pack10_bound(self.nbytes // 2), dtype=torch.uint8, device="cuda")   # (as _raw_on_device)
             N.check(self._lib.lia_memcpy_h2d(enc.data_ptr(), host.ctypes.data, nbytes), "lia_memcpy_h2d")
             N.check(self._lib.lia_pack_decode(ctypes.c_void_p(enc.data_ptr()), ctypes.c_void_p(dev.data_ptr()), self.nbytes // 2, int(fmt),
                                               None), "lia_pack_decode")
