@@ -12,12 +12,16 @@ value = batch x steps / that bracket (tokens/s), protocol.decode_tokens_per_s = 
 An untimed warm-up generate (same cache size, two decode steps) runs first, as --num-warmup iterations do there.
 Weights: seeded random init of the exact architecture (no checkpoints offline).
 
-In the same run, on rank 0 at N = 1: a shorter leg with the streamed layers in RAW bf16 (what the reference
-ships; value_raw_format) and the CPU baseline -- decode policy 1 (every layer on the host cores) through the same
-generate() entry point, beside the oracle's restatement of that path on a one-layer sample.
+A plain run does only that: build, warm up, time, write --dump-outputs, print the line.  Everything else the benchmark
+measures runs behind --full, after the timed steps of the same run: on rank 0 at N = 1 a shorter leg with the streamed
+layers in RAW bf16 (what the reference ships; value_raw_format), the prefill with the reference's K/V order
+(prefill_ms_defer_kv_0), the cooperative-split legs (value_cooperative*), the CPU baseline -- decode policy 1 (every layer
+on the host cores) through the same generate() entry point, beside the oracle's restatement of that path on a one-layer
+sample --, the oracle parity sample, the id checks between legs, the auto_plan object and the committed PMC traffic of the
+dominant kernels; at N > 1 the extra data-parallel legs.  The --no-* switches below leave out single legs of a --full run.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model opt-30b] [--batch 64 | --global-batch 256] [--prompt 256]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 --dump-outputs DIR: after the timed steps, rank 0 writes what its timed generate() computed as DIR/<name>.npy -- tokens.npy (the ids the
 caller receives, [B, prompt + new], float64) and logits.npy (the last decode step's logits, [B, vocab], float32) -- so that two builds
@@ -65,6 +69,9 @@ def build_parser():
     ap.add_argument("--decoding-policy", type=int, default=None, help="default: 2 on one GPU; on N > 1 GPUs 3 (KV in HBM: G ranks share the host's "
                     "CPU quota, host attention would run on 1/G of it each), else 2")
     ap.add_argument("--num-minibatch", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the extra legs (raw wire, K/V order, cooperative split, "
+                    "CPU baseline, oracle parity, auto_plan; N > 1: the extra data-parallel legs) and read the committed PMC traffic; "
+                    "a plain run measures the headline only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-raw-leg", action="store_true", help="skip the second, shorter leg with raw bf16 on the wire")
     ap.add_argument("--raw-steps", type=int, default=6)
@@ -78,7 +85,7 @@ def build_parser():
                     "reported with its own CFS-throttle counters (r05 verdict, weak item 9: one 8-step average had an unknown spread)")
     ap.add_argument("--no-dp-extra-legs", action="store_true", help="N > 1: skip the KV-in-HBM and all-gather legs")
     ap.add_argument("--dp-allgather-legs", action="store_true",
-                    help="N > 1: also run the all-gather legs (every rank re-draws the model and pins 1/N of each streamed layer; value_allgather*). "
+                    help="N > 1, with --full: also run the all-gather legs (every rank re-draws the model and pins 1/N of each streamed layer; value_allgather*). "
                          "Off by default: this streaming mode has run over gloo and over RCCL at world size 1 only, and an optional leg must "
                          "not be able to take the measured headline line down with it on first contact with an 8-GPU node")
     ap.add_argument("--dp-extra-steps", type=int, default=6)
@@ -442,7 +449,7 @@ def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
 def pmc_traffic(kernel_substr):
     """HBM bytes per launch of the dominant kernel from the committed PMC pass of this same command
     (the newest profiles/r*_opt30b_bench_pmc_hbm.json, tools/profile_round.sh: separate --pmc FETCH_SIZE / WRITE_SIZE runs, gfx950 x2 fetch correction).
-    PMC collection cannot run inside the timed benchmark, so the live line carries the committed measurement and names it."""
+    PMC collection cannot run inside the timed benchmark, so a --full line carries the committed measurement and names it."""
     import glob
     files = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_bench_opt30b_pmc_hbm.json")) +
                    glob.glob(os.path.join(ROOT, "profiles", "r*_opt30b_bench_pmc_hbm.json")), key=os.path.basename)
@@ -841,7 +848,7 @@ def main(argv=None):
         # rocprofv3's kernel durations (profiles/) carry no such term, so it is taken out before dividing
         sk_ms = max(1e-9, sk_raw_ms - sk_n * prof.get("empty_bracket_ms", 0.0))
         achieved = prof["skinny_bytes"] / (sk_ms * 1e-3) / 1e9 if sk_ms > 0 else 0.0
-        traffic, traffic_src = (pmc_traffic("lia_gemm_skinny2_kernel<4") if (a.model == "opt-30b" and B == 64) else (None, None))
+        traffic, traffic_src = (pmc_traffic("lia_gemm_skinny2_kernel<4") if (a.full and a.model == "opt-30b" and B == 64) else (None, None))
         headline = (a.model == "opt-30b" and rows_total == 64 and T == 256 and a.gpu_percentage == 10 and not a.cpu_layers)
         config5 = (a.model == "opt-30b" and a.global_batch == 256 and T == 256 and a.gpu_percentage == 10 and world > 1)
         streamed = (not is_llama) and n_gpu < shape.layers
@@ -925,7 +932,7 @@ def main(argv=None):
                 wn = wire_dec["launches"]
                 w_ms = max(1e-9, wire_dec["ms"] - wn * prof.get("empty_bracket_ms", 0.0))
                 w_bytes = wire_dec["bytes_in"] + wire_dec["bytes_out"]
-                w_traffic, w_src = pmc_traffic(f"lia_{a.stream_format}_decode_kernel") if (a.model == "opt-30b" and B == 64) else (None, None)
+                w_traffic, w_src = pmc_traffic(f"lia_{a.stream_format}_decode_kernel") if (a.full and a.model == "opt-30b" and B == 64) else (None, None)
                 wk = {"bound": "hbm", "kernel": f"lia_{a.stream_format}_decode_kernel (wire format -> bf16 layer in the streamer slot, own stream)",
                       "achieved": w_bytes / (w_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": w_bytes / (w_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                       "traffic": w_traffic, "traffic_source": w_src, "launches": wn, "avg_launch_us": 1e3 * w_ms / wn,
@@ -949,7 +956,7 @@ def main(argv=None):
 
     # ---- second leg: the same streamed layers as RAW bf16 (what the reference ships), same model object, re-tiered ----------
     ids_check = {}
-    if rank == 0 and world == 1 and not is_llama and fmt and not a.no_raw_leg and n_gpu < shape.layers:
+    if a.full and rank == 0 and world == 1 and not is_llama and fmt and not a.no_raw_leg and n_gpu < shape.layers:
         sched.wire = 0
         t0 = time.time()
         ids_raw, lat_raw, logits_raw = generate(model, ids, max_steps=2 + a.raw_steps, return_logits=True, **gen_kwargs)
@@ -962,7 +969,7 @@ def main(argv=None):
         sched.wire = fmt
 
     # ---- the prefill with the reference's K/V semantics: store_cache beside the prefill (modeling_opt.py:334-345), not deferred -----
-    if rank == 0 and world == 1 and not is_llama and not a.no_defer_kv_leg and n_gpu < shape.layers and a.prefill_policy == 0 \
+    if a.full and rank == 0 and world == 1 and not is_llama and not a.no_defer_kv_leg and n_gpu < shape.layers and a.prefill_policy == 0 \
             and getattr(sched, "defer_kv", False):
         try:
             sched.defer_kv = False
@@ -982,7 +989,7 @@ def main(argv=None):
             sched.defer_kv = True
 
     # ---- build-defined cooperative split, beside (never instead of) the headline: the planner's host-computed layer count ------
-    if rank == 0 and world == 1 and not is_llama and not a.no_cooperative_leg and not a.cpu_layers and a.decoding_policy == 2 \
+    if a.full and rank == 0 and world == 1 and not is_llama and not a.no_cooperative_leg and not a.cpu_layers and a.decoding_policy == 2 \
             and n_gpu < shape.layers:
         try:
             from lia_amd import planner
@@ -1028,7 +1035,7 @@ def main(argv=None):
                 out["cooperative_kv_in_hbm_leg"] = {"error": f"{type(e).__name__}: {e}"}
 
     # ---- CPU baseline: the reference's policy 1 ("compute everything on CPU", IPEX/AMX there) on this box's host cores ----------
-    if rank == 0 and world == 1 and not is_llama and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not is_llama and not a.no_cpu_baseline:
         cpu_kwargs = dict(gen_kwargs, prefill_policy=0, decoding_policy=1, gpu_percentage=0)
         cpu_kwargs.pop("cpu_layers", None)
         product = None
@@ -1079,7 +1086,7 @@ def main(argv=None):
     # ---- what `run.py --auto-plan` picks on THIS box for this configuration (r04 verdict, weak item 8: on a box whose CPU baseline beats
     # the reference's hand-picked 0 / 2, the line itself should show the planner choosing the better policy, next to the leg that
     # measured it): the same calibrate() + plan() + plan_cpu_layers() the harness runs, capped at the configured gpu%
-    if rank == 0 and world == 1 and not is_llama and not a.no_auto_plan and n_gpu < shape.layers and not a.cpu_layers:
+    if a.full and rank == 0 and world == 1 and not is_llama and not a.no_auto_plan and n_gpu < shape.layers and not a.cpu_layers:
         try:
             from types import SimpleNamespace
             from lia_amd import run_generation
@@ -1113,8 +1120,8 @@ def main(argv=None):
     if rank == 0 and ids_check:
         out["ids_check"] = ids_check
 
-    # ---- N > 1: two short extra legs so that ONE line shows why the curve bends (same model, same ranks) -------------------
-    if dist is not None and (world > 1 or force_dp) and not is_llama and not a.no_dp_extra_legs and n_gpu < shape.layers:
+    # ---- N > 1, --full: two short extra legs so that ONE line shows why the curve bends (same model, same ranks) ------------
+    if a.full and dist is not None and (world > 1 or force_dp) and not is_llama and not a.no_dp_extra_legs and n_gpu < shape.layers:
         # The headline of this run is already measured.  It is printed NOW, and again -- extended -- as the last line when the legs
         # are done: should a leg hang in a collective (one rank failing where the others do not), a watchdog ends every rank with
         # exit code 3 (a process killed inside a collective has NOT succeeded) after rank 0 has re-printed the headline line with

@@ -43,6 +43,14 @@ def test_bench_flag_surface():
     assert a.global_batch // a.gpus == 32                    # BASELINE config 5
 
 
+def test_bench_extra_legs_are_opt_in():
+    """a plain `bench.py --gpus 1 --steps K --warmup W` measures the headline only; the extra legs need --full"""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.build_parser().parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"]).full is False
+    assert bench.build_parser().parse_args(["--full"]).full is True
+
+
 def _load_bench():
     import importlib.util
     spec = importlib.util.spec_from_file_location("lia_bench_mod", os.path.join(ROOT, "bench.py"))

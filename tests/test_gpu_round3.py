@@ -359,7 +359,7 @@ def test_h2d_microbenchmark_twin_three_tiers():
 
 
 def test_bench_line_contract_on_a_small_model():
-    """bench.py end to end on opt-125m dims (seconds): ONE JSON line as the last line of stdout, with the contract's keys, the
+    """bench.py --full end to end on opt-125m dims (seconds): ONE JSON line as the last line of stdout, with the contract's keys, the
     binding roofline named (`pcie` for a streamed configuration, the dominant kernel's HBM figures as a sub-object), the CPU
     baseline, the oracle parity sample and the id checks of the legs."""
     import json
@@ -367,7 +367,7 @@ def test_bench_line_contract_on_a_small_model():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", "opt-125m", "--batch", "8", "--prompt", "32", "--steps", "4",
-                        "--warmup", "1", "--gpu-percentage", "25", "--raw-steps", "2", "--cpu-steps", "2", "--coop-steps", "4"],
+                        "--warmup", "1", "--gpu-percentage", "25", "--raw-steps", "2", "--cpu-steps", "2", "--coop-steps", "4", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     last = r.stdout.strip().splitlines()[-1]
@@ -408,6 +408,36 @@ def test_bench_line_contract_on_a_small_model():
     assert d["value_cooperative"] > 0 and "error" not in d["cooperative_leg"]
     assert d["value_cooperative_kv_in_hbm"] > 0 and "error" not in d["cooperative_kv_in_hbm_leg"], d.get("cooperative_kv_in_hbm_leg")
     assert d["ids_check"]["cooperative_vs_headline"]["steps_compared"] >= 4 and d["ids_check"]["cooperative_kv_in_hbm_vs_headline"]["steps_compared"] >= 4
+
+
+BENCH_FULL_ONLY_KEYS = ("value_raw_format", "raw_format_leg", "prefill_ms_defer_kv_0", "prefill_defer_kv_0_leg", "value_cooperative",
+                        "cooperative_leg", "value_cooperative_kv_in_hbm", "cooperative_kv_in_hbm_leg", "cpu_baseline", "parity", "auto_plan",
+                        "ids_check", "cooperative_seeded_from_store", "dp_extra_legs")
+
+
+def test_bench_plain_line_is_the_headline_only():
+    """bench.py without --full on opt-125m dims: the same headline keys and live roofline as the --full line, and none of the extra
+    legs, samples or checks that --full adds (a plain run measures its headline only)"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", "opt-125m", "--batch", "8", "--prompt", "32", "--steps", "4",
+                        "--warmup", "1", "--gpu-percentage", "25"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert k in d, k
+    assert d["unit"] == "tokens/s" and d["steps"] == 4 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["value"] > 0 and abs(d["value"] - 8 * 4 / (d["ms_per_step"] * 4e-3)) < 1e-6 * d["value"] + 1e-9
+    assert d["prefill_ms"] > 0 and d["config"]["new_tokens"] == 6
+    rf = d["roofline"]
+    assert rf["bound"] == "pcie" and rf["traffic"] > 0 and rf["dominant_kernel"]["launches"] > 0
+    present = [k for k in BENCH_FULL_ONLY_KEYS if k in d]
+    assert not present, present
+    assert not ({"value_raw_format", "value_cooperative", "parity_max_err_in_quanta", "auto_plan_policies"} & set(rf["scalars"])), rf["scalars"]
 
 
 def test_bench_dump_outputs_are_the_timed_runs_last_step_and_repeat(tmp_path):

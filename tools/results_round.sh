@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 out=gpurun_out/results_$tag
 mkdir -p "$out"
 export LIA_STATE_DIR="$PWD/$out/state"      # the cooperative controller's converged counts (scheduler.CoopStore) stay on this box, for this round
-run() { name=$1; shift; echo "== $name: bench.py $*"; timeout 1500 python3 bench.py "$@" > "$out/$name.log" 2>&1; tail -1 "$out/$name.log" > "$out/$name.json"; cut -c1-220 "$out/$name.json"; echo; }
+run() { name=$1; shift; echo "== $name: bench.py --full $*"; timeout 1500 python3 bench.py --full "$@" > "$out/$name.log" 2>&1; tail -1 "$out/$name.log" > "$out/$name.json"; cut -c1-220 "$out/$name.json"; echo; }
 run opt30b_gpu10_p0p2_pack10
 # the same command again in a NEW process: the cooperative legs start on the count the first one converged on (seeded_from_store)
 run opt30b_gpu10_p0p2_pack10_second_process --no-raw-leg --no-cpu-baseline
