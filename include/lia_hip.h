@@ -174,6 +174,22 @@ int lia_attention(const lia_bf16* q, long ldq, const lia_bf16* kcache, const lia
 /* embed_tokens + embed_positions, modeling_opt.py:1108,357-378,1142 */
 int lia_embed(const int64_t* ids, const lia_bf16* tok, const lia_bf16* pos, lia_bf16* y, int B, int T, int past_len, int H,
               void* stream);
+/* ---- left-padded batches (generate(..., attention_mask=M), M = s_b zeros then ones per row) -------------------------------
+ * The reference's CPU branch: positions from the mask (lia/modeling_opt.py:368-378), the 4-D additive causal + padding mask
+ * (lia/modeling_opt.py:1133 -> mha_fusion.py:532-566).  A query at cache position i >= s_b attends keys s_b .. i; a query at a
+ * pad position (i < s_b) gives a zero row.  Its GPU branch drops the mask (attentions.py:444-449, modeling_opt.py:1434,1469).
+ * lia_ctx_set_key_starts: the table of s_b per cache batch row (host pointer, n_rows entries >= 0; NULL or 0 clears it).  The
+ * context keeps a host copy and a device copy; lia_layer_forward, lia_layer_forward_last and lia_decode_layers then serve rows
+ * b0 .. b0 + B - 1 through the padded attention (GPU policies and the policy-2 host attention); each s_b must be <= pos0 + T - 1.
+ * Without a table they take the unpadded route, unchanged.
+ * lia_embed_padded: position p - s_b + 2 for the token at cache position p = past_len + t >= s_b, position 1 at a pad position.
+ * lia_attention_padded: lia_attention with the starts of the served rows.  starts: DEVICE pointers, B entries (row b <-> b0 + b). */
+int lia_ctx_set_key_starts(lia_ctx* ctx, const int32_t* starts_host, int n_rows);
+int lia_embed_padded(const int64_t* ids, const lia_bf16* tok, const lia_bf16* pos, lia_bf16* y, int B, int T, int past_len, int H,
+                     const int32_t* starts_device, void* stream);
+int lia_attention_padded(const lia_bf16* q, long ldq, const lia_bf16* kcache, const lia_bf16* vcache, lia_bf16* out, long ldo,
+                         int B, int T, int S, int heads, int head_dim, int cache_batch, int b0, const int32_t* starts_device,
+                         void* stream);
 /* final LN on the last position + tied lm_head + greedy argmax: modeling_opt.py:1563, models.py:424-431,
  * greedy_search.py:367,395.  logits [B,vocab], next_ids [B] (device).  suppress_token >= 0: that token's score
  * counts as -inf (EOS while min_new_tokens is unmet, run_generation.py:173,179-182); -1: none. */
@@ -240,6 +256,11 @@ long lia_ctx_get_counter(lia_ctx* ctx, int key);
 int lia_host_attention(const lia_bf16* q, const lia_bf16* k, const lia_bf16* v, lia_bf16* kcache, lia_bf16* vcache,
                        lia_bf16* out, int B, int T, int pos0, int heads, int head_dim, int cache_batch, int b0,
                        int n_threads);
+/* the same over a left-padded batch (the reference's additive padding mask, mha_fusion.py:532-566): served row b attends keys
+ * starts[b] .. pos0 + t, a query at a pad position gives a zero row.  starts: HOST, B entries, 0 <= starts[b] <= pos0 + T - 1. */
+int lia_host_attention_padded(const lia_bf16* q, const lia_bf16* k, const lia_bf16* v, lia_bf16* kcache, lia_bf16* vcache,
+                              lia_bf16* out, int B, int T, int pos0, int heads, int head_dim, int cache_batch, int b0,
+                              int n_threads, const int32_t* starts);
 
 /* policy 1, "compute everything on CPU" (modeling_opt.py:1168): the same layer entirely on the host cores.  The
  * reference routes it through IPEX (tpp_linear_bias/_relu/_add, TPPGEMMKrnl.h:89-176,671-765,858-951 + the masked
@@ -254,6 +275,14 @@ int lia_host_layer_forward(const lia_layer_desc* d, const void* const weights[16
 int lia_host_layers_forward(const lia_layer_desc* d, int n_layers, const void* const* weights, lia_bf16* x, lia_bf16* y,
                             void* const* kcaches, void* const* vcaches, int smax, int cache_batch, int B, int T, int pos0,
                             int b0, int n_threads);
+/* policy 1 over a left-padded batch (lia/modeling_opt.py:1133 + mha_fusion.py:532-566 on the CPU branch): the attention of
+ * lia_host_attention_padded inside; starts: HOST, B entries for the served rows (no context here, so an explicit argument) */
+int lia_host_layer_forward_padded(const lia_layer_desc* d, const void* const weights[16], const lia_bf16* x, lia_bf16* y,
+                                  lia_bf16* kcache, lia_bf16* vcache, int smax, int cache_batch, int B, int T, int pos0, int b0,
+                                  int n_threads, const int32_t* starts);
+int lia_host_layers_forward_padded(const lia_layer_desc* d, int n_layers, const void* const* weights, lia_bf16* x, lia_bf16* y,
+                                   void* const* kcaches, void* const* vcaches, int smax, int cache_batch, int B, int T, int pos0,
+                                   int b0, int n_threads, const int32_t* starts);
 int lia_host_layernorm(const lia_bf16* x, const lia_bf16* g, const lia_bf16* b, lia_bf16* y, long rows, int H, float eps,
                        int n_threads);
 int lia_host_linear(const lia_bf16* x, const lia_bf16* w, const lia_bf16* bias, const lia_bf16* residual, lia_bf16* y, long M,

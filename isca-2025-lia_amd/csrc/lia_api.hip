@@ -28,6 +28,14 @@ extern "C" void lia_blit_launch(void* dst, const void* src, size_t bytes, hipStr
 extern "C" int lia_attn_prefill_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
                                        int B, int T, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
                                        hipStream_t st);
+extern "C" int lia_attn_prefill_padded_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
+                                              int B, int T, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
+                                              const int* starts, hipStream_t st);
+extern "C" int lia_attn_decode_padded_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
+                                             int B, int S, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
+                                             const int* starts, hipStream_t st);
+extern "C" void lia_embed_padded_launch(const int64_t* ids, const bf16_t* tok, const bf16_t* pos, bf16_t* y, int B, int T,
+                                        int past_len, int H, const int* starts, hipStream_t st);
 extern "C" int lia_attn_decode_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
                                       int B, int S, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
                                       hipStream_t st);
@@ -103,6 +111,12 @@ struct lia_ctx {
   bool serialized;
   char* hidden_tmp;           // a third hidden-state buffer for lia_decode_layers (a layer never writes the buffer it reads)
   size_t hidden_tmp_bytes;
+  // left-padded batch (lia_ctx_set_key_starts): per cache batch row, the first cache position its queries attend; a host copy
+  // (validation, the policy-2 host attention) and a device copy in a buffer of key_starts_cap entries that only grows
+  std::vector<int>* key_starts;
+  int* key_starts_dev;
+  int key_starts_cap;
+  int key_starts_n;           // 0: no table -- every layer call takes the unpadded route
 };
 
 extern "C" int lia_ctx_chain_next_norm(lia_ctx* c, const lia_bf16* g, const lia_bf16* b) {
@@ -161,6 +175,8 @@ extern "C" void lia_ctx_destroy(lia_ctx* c) {
   }
   if (c->ws) (void)hipFree(c->ws);
   if (c->hidden_tmp) (void)hipFree(c->hidden_tmp);
+  if (c->key_starts_dev) (void)hipFree(c->key_starts_dev);
+  delete c->key_starts;
   if (c->host_stage) (void)hipHostFree(c->host_stage);
   if (c->deliver_t0) { (void)hipEventDestroy(c->deliver_t0); (void)hipEventDestroy(c->deliver_t1); }
   if (c->deliver_events) {
@@ -201,6 +217,28 @@ extern "C" int lia_ctx_synchronize_compute(lia_ctx* c) {
 
 // Per-context options and counters (r05: the A/B switches used to be process-wide setters -- lia_gemm_set_* -- although the
 // library promises that two contexts of one process are independent, include/lia_hip.h).
+extern "C" int lia_ctx_set_key_starts(lia_ctx* c, const int32_t* starts, int n_rows) {
+  if (!c || n_rows < 0) return LIA_ERR_INVALID;
+  if (!starts || n_rows == 0) { c->key_starts_n = 0; return LIA_OK; }
+  for (int b = 0; b < n_rows; ++b)
+    if (starts[b] < 0) { lia_set_error("lia_ctx_set_key_starts: starts[%d] = %d < 0", b, starts[b]); return LIA_ERR_INVALID; }
+  // launches queued earlier may still read the device table: let them finish before it is replaced or overwritten
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->compute));
+  if (c->key_starts_cap < n_rows) {
+    if (c->key_starts_dev) (void)hipFree(c->key_starts_dev);
+    c->key_starts_dev = nullptr; c->key_starts_cap = 0; c->key_starts_n = 0;
+    HIP_TRY(hipMalloc((void**)&c->key_starts_dev, (size_t)n_rows * sizeof(int)));
+    c->key_starts_cap = n_rows;
+  }
+  if (!c->key_starts) c->key_starts = new std::vector<int>();
+  c->key_starts->assign(starts, starts + n_rows);
+  HIP_TRY(hipMemcpyAsync(c->key_starts_dev, c->key_starts->data(), (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice, c->compute));
+  HIP_TRY(hipStreamSynchronize(c->compute));
+  c->key_starts_n = n_rows;
+  return LIA_OK;
+}
+
 extern "C" int lia_ctx_set_option(lia_ctx* c, int key, long value) {
   if (!c) return LIA_ERR_INVALID;
   switch (key) {
@@ -539,6 +577,35 @@ extern "C" int lia_embed(const int64_t* ids, const lia_bf16* tok, const lia_bf16
   return LIA_OK;
 }
 
+extern "C" int lia_embed_padded(const int64_t* ids, const lia_bf16* tok, const lia_bf16* pos, lia_bf16* y, int B, int T,
+                                int past_len, int H, const int32_t* starts, void* stream) {
+  if (!ids || !tok || !pos || !y || !starts) { lia_set_error("lia_embed_padded: NULL tensor"); return LIA_ERR_MISSING; }
+  if (B <= 0 || T <= 0 || past_len < 0 || H % 8) { lia_set_error("lia_embed_padded: B=%d T=%d past=%d H=%d", B, T, past_len, H); return LIA_ERR_INVALID; }
+  lia_embed_padded_launch(ids, tok, pos, y, B, T, past_len, H, starts, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+extern "C" int lia_attention_padded(const lia_bf16* q, long ldq, const lia_bf16* kcache, const lia_bf16* vcache, lia_bf16* out,
+                                    long ldo, int B, int T, int S, int heads, int head_dim, int cache_batch, int b0,
+                                    const int32_t* starts, void* stream) {
+  if (!q || !kcache || !vcache || !out || !starts) { lia_set_error("lia_attention_padded: NULL tensor"); return LIA_ERR_MISSING; }
+  if (B <= 0 || T <= 0 || S < T || b0 < 0 || b0 + B > cache_batch || (T > 1 && S != T)) {
+    lia_set_error("lia_attention_padded: B=%d T=%d S=%d cache_batch=%d b0=%d (multi-token blocks only as a prefill, S == T)", B, T, S,
+                  cache_batch, b0);
+    return LIA_ERR_INVALID;
+  }
+  const int rc = T == 1 ? lia_attn_decode_padded_launch(q, ldq, kcache, vcache, out, ldo, B, S, heads, heads, head_dim, cache_batch, b0, 0, starts, (hipStream_t)stream)
+                        : lia_attn_prefill_padded_launch(q, ldq, kcache, vcache, out, ldo, B, T, heads, heads, head_dim, cache_batch, b0, 0, starts, (hipStream_t)stream);
+  if (rc) {
+    lia_set_error("lia_attention_padded: head_dim %d unsupported (32/64/128), S=%d too long, or a cache of %d batch rows x %d values per key row beyond the d = 128 prefill kernel's 32-bit staging offsets",
+                  head_dim, S, cache_batch, heads * head_dim);
+    return LIA_ERR_INVALID;
+  }
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
 extern "C" int lia_lm_head(lia_ctx* ctx, const lia_bf16* hidden, int B, int T, int H, const lia_bf16* lnw,
                            const lia_bf16* lnb, const lia_bf16* emb, int vocab, float eps, int suppress_token,
                            lia_bf16* logits, int64_t* next_ids, void* stream) {
@@ -600,6 +667,23 @@ static int layer_forward_impl(lia_ctx* ctx, const lia_layer_desc* d, int policy,
   if ((policy == 3) != (kv->on_device != 0)) {
     lia_set_error("lia_layer_forward: policy %d needs a %s cache", policy, policy == 3 ? "device" : "host");
     return LIA_ERR_INVALID;
+  }
+  // left padding (lia_ctx_set_key_starts): the table's rows b0 .. b0 + B - 1 -- the generation's rows, whatever the layout of the
+  // K / V destination below (the policy-0 slab has rows 0 .. B - 1 of its own)
+  const int* kst_dev = nullptr;
+  const int* kst_host = nullptr;
+  if (ctx->key_starts_n) {
+    if (b0 + B > ctx->key_starts_n) {
+      lia_set_error("lia_layer_forward: rows %d..%d beyond the %d rows of the key-start table", b0, b0 + B - 1, ctx->key_starts_n);
+      return LIA_ERR_INVALID;
+    }
+    kst_host = ctx->key_starts->data() + b0;
+    kst_dev = ctx->key_starts_dev + b0;
+    for (int b = 0; b < B; ++b)
+      if (kst_host[b] > pos0 + T - 1) {
+        lia_set_error("lia_layer_forward: row %d starts at %d, beyond its last position %d", b0 + b, kst_host[b], pos0 + T - 1);
+        return LIA_ERR_INVALID;
+      }
   }
   const int H = d->hidden, F = d->ffn, hd = H / d->heads;
   const long M = (long)B * T;
@@ -692,7 +776,8 @@ static int layer_forward_impl(lia_ctx* ctx, const lia_layer_desc* d, int policy,
     lia_blit_launch(hv, vb, one, st);
     HIP_TRY(hipStreamSynchronize(st));
     const auto ha_t0 = std::chrono::steady_clock::now();
-    rc = lia_host_attention(hq, hk, hv, kv->k, kv->v, ha, B, T, pos0, d->heads, hd, kv->batch, b0, ctx->host_threads);
+    rc = kst_host ? lia_host_attention_padded(hq, hk, hv, kv->k, kv->v, ha, B, T, pos0, d->heads, hd, kv->batch, b0, ctx->host_threads, kst_host)
+                  : lia_host_attention(hq, hk, hv, kv->k, kv->v, ha, B, T, pos0, d->heads, hd, kv->batch, b0, ctx->host_threads);
     if (rc) return rc;
     if (ctx->prof_on) {
       ctx->prof_host_attn_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ha_t0).count();
@@ -702,8 +787,13 @@ static int layer_forward_impl(lia_ctx* ctx, const lia_layer_desc* d, int policy,
   } else {
     // GPU attention (attentions.py:443-536)
     // (tail: the last query of a causal block attends every key -- one decode-style query per row over the S rows just written)
-    int arc = (T == 1 || tail) ? lia_attn_decode_launch(qb + tail_off, tail_ld, kdst, vdst, ao, H, B, (int)S, d->heads, d->heads, hd, dst_batch, dst_b0, 0, st)
-                               : lia_attn_prefill_launch(qb, H, kdst, vdst, ao, H, B, T, d->heads, d->heads, hd, dst_batch, dst_b0, 0, st);
+    int arc;
+    if (kst_dev)
+      arc = (T == 1 || tail) ? lia_attn_decode_padded_launch(qb + tail_off, tail_ld, kdst, vdst, ao, H, B, (int)S, d->heads, d->heads, hd, dst_batch, dst_b0, 0, kst_dev, st)
+                             : lia_attn_prefill_padded_launch(qb, H, kdst, vdst, ao, H, B, T, d->heads, d->heads, hd, dst_batch, dst_b0, 0, kst_dev, st);
+    else
+      arc = (T == 1 || tail) ? lia_attn_decode_launch(qb + tail_off, tail_ld, kdst, vdst, ao, H, B, (int)S, d->heads, d->heads, hd, dst_batch, dst_b0, 0, st)
+                             : lia_attn_prefill_launch(qb, H, kdst, vdst, ao, H, B, T, d->heads, d->heads, hd, dst_batch, dst_b0, 0, st);
     if (arc) { lia_set_error("attention: unsupported head_dim %d / S %zu", hd, S); return LIA_ERR_INVALID; }
     if (policy == 0) {
       // deliver rows [pos0, pos0+T) of batch rows [b0, b0+B) to the host cache

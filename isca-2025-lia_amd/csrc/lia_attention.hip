@@ -26,12 +26,17 @@
 //   O^T = V^T . P^T  (A = V^T from a transposed LDS image, B = the P^T accumulator registers re-used
 //   directly as the next MFMA's operand, cdna_hip_programming.md section 3).
 // ---------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void lia_attn_prefill_kernel(const bf16_t* __restrict__ q, long ldq,
-                                                                const bf16_t* __restrict__ kc,
-                                                                const bf16_t* __restrict__ vc, bf16_t* __restrict__ out,
-                                                                long ldo, int T, int heads, int kv_heads, int Bc, int b0,
-                                                                float scaling, int post_scale) {
+// Left padding (PADDED = 1, every kernel below): served row b's tokens start at cache position kstart = starts[b]; its query i >= kstart
+// sees keys kstart .. i.  That is the unpadded causal attention of a sequence of T - kstart tokens whose first sits at kstart, so the padded
+// instantiations run the unpadded arithmetic on that shifted frame -- queries, keys and output rows offset by kstart, T - kstart tokens,
+// key tiles aligned to kstart (every tile wholly before kstart is never visited, no key needs a lower mask) -- and write query rows
+// 0 .. kstart - 1 as zeros without any K / V work.  A real row's result is bit for bit that of the same row unpadded.
+// starts: per served row b (the caller passes its table + b0); PADDED = 0 never reads it
+template <int D, int PADDED>
+__global__ __launch_bounds__(256) void lia_attn_prefill_kernel(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ kc,
+                                                                const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int Tp,
+                                                                int heads, int kv_heads, int Bc, int b0, float scaling, int post_scale,
+                                                                const int* __restrict__ starts) {
   constexpr int CH = D / 8;              // 16-byte chunks per K row
   constexpr int RPB = 16 / CH;           // K rows per 256-byte LDS bank row
   constexpr int KSTEPS = D / 16;         // MFMA k-steps over d for S^T
@@ -43,16 +48,28 @@ __global__ __launch_bounds__(256) void lia_attn_prefill_kernel(const bf16_t* __r
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   const int hh = blockIdx.y, b = blockIdx.z;
+  // Tp: the batch rows' pitch in q / out (tokens per row); T: the row's tokens from its start kstart on (the shifted frame, see above)
+  const int kstart = PADDED ? __builtin_amdgcn_readfirstlane(starts[b]) : 0;   // (uniform: keeps the row start scalar)
+  const int T = Tp - kstart;
+  const int nqblk = PADDED ? (T + 127) / 128 : (int)gridDim.x;   // query blocks of the row
+  if (PADDED) {
+    // pad query rows of this workgroup's 128 (unshifted) rows: zeros
+    for (int idx = tid; idx < 128 * (D / 4); idx += 256) {
+      const int row = (int)blockIdx.x * 128 + idx / (D / 4);
+      if (row < kstart) *(uint2*)(out + ((long)b * Tp + row) * ldo + (long)hh * D + 4 * (idx % (D / 4))) = uint2{0u, 0u};
+    }
+    if ((int)blockIdx.x >= nqblk) return;
+  }
   // every other (batch row, head) takes its query blocks and its waves' row blocks in reverse order (r05, see the d = 128 kernel:
   // otherwise XCD gridDim.x - 1 and SIMD 3 collect all the long rows of the causal triangle); the results do not depend on it
   const int rev = (hh + b) & 1;
-  const int q_wg = (rev ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x) * 128;
+  const int q_wg = (rev ? nqblk - 1 - (int)blockIdx.x : (int)blockIdx.x) * 128;
   const int q_wave = q_wg + (rev ? 3 - wave : wave) * 32;
   // grouped-query attention (Llama family): query head hh reads K/V head hh / (heads / kv_heads); OPT: kv_heads == heads
   const int kh = hh / (heads / kv_heads);
   const long kv_row = (long)Bc * kv_heads * D;  // elements between consecutive sequence positions
-  const bf16_t* kbase = kc + ((long)(b0 + b) * kv_heads + kh) * D;
-  const bf16_t* vbase = vc + ((long)(b0 + b) * kv_heads + kh) * D;
+  const bf16_t* kbase = kc + ((long)(b0 + b) * kv_heads + kh) * D + (long)kstart * kv_row;
+  const bf16_t* vbase = vc + ((long)(b0 + b) * kv_heads + kh) * D + (long)kstart * kv_row;
   // OPT rounds q * d^-0.5 before the product (attentions.py:456); HF Llama rounds the product, then scales it
   // (eager_attention_forward: matmul(q, k^T) * scaling)
   const float qscale = post_scale ? 1.0f : scaling;
@@ -61,7 +78,7 @@ __global__ __launch_bounds__(256) void lia_attn_prefill_kernel(const bf16_t* __r
   bf16x8 qf[KSTEPS];
   {
     const int qrow = min(q_wave + r, T - 1);
-    const bf16_t* qp = q + ((long)b * T + qrow) * ldq + (long)hh * D;
+    const bf16_t* qp = q + ((long)b * Tp + kstart + qrow) * ldq + (long)hh * D;
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) {
 #ifdef P3X_NO_QLOAD
@@ -188,7 +205,7 @@ __global__ __launch_bounds__(256) void lia_attn_prefill_kernel(const bf16_t* __r
   (void)inv_l;
 
   if (my_q < T) {
-    bf16_t* op = out + ((long)b * T + my_q) * ldo + (long)hh * D;
+    bf16_t* op = out + ((long)b * Tp + kstart + my_q) * ldo + (long)hh * D;
 #pragma unroll
     for (int d = 0; d < DB; ++d)
 #pragma unroll
@@ -298,11 +315,11 @@ __device__ __forceinline__ uint2 p3_prob4(f32x4 r, float m, float l, float rl) {
   return uint2{p3_cvt_pk(q.x, q.y), p3_cvt_pk(q.z, q.w)};
 }
 
-template <int POST_SCALE>
-__global__ __launch_bounds__(256, 2) void lia_attn_prefill128_kernel(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ kc,
-                                                                  const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int T,
-                                                                  int heads, int kv_heads, long kv_row, long kv_batch, int b0, float scaling,
-                                                                  int nqb, int n_groups) {
+template <int POST_SCALE, int PADDED>
+__device__ __forceinline__ void lia_attn_prefill128_body(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ kc,
+                                                         const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int Tp,
+                                                         int heads, int kv_heads, long kv_row, long kv_batch, int b0, float scaling,
+                                                         int nqb, int n_groups, const int* __restrict__ starts) {
   constexpr int D = 128;
   __shared__ __attribute__((aligned(16))) char lds[2][2][64 * 256];   // [buffer][0 = K, 1 = V][key row of 256 bytes]
 
@@ -341,12 +358,32 @@ __global__ __launch_bounds__(256, 2) void lia_attn_prefill128_kernel(const bf16_
   // workgroup of a sequence costs the same (causal: 1 + ... keys), half as many workgroups are launched and drained -- the
   // launches alone were 75 us of the 313 us of OPT-30B's T = 256 launch (the kernel without loads, arithmetic and stores,
   // LABNOTES r06) -- and the second block's K / V tiles were just read by the first.
-  const int nqb_all = (T + 127) >> 7;
-  const int npass = (nqb != nqb_all && nqb_all - 1 - bx != bx) ? 2 : 1;
+  // PADDED: the row's T - kstart tokens from its start kstart on form the sequence (the shifted frame of lia_attn_prefill_body); its
+  // nqa query blocks are dealt to the first nqr workgroups of the row by the same pairing, Tp is the rows' pitch in q / out.
+  // (With padding the pairs of one launch no longer cost the same: rows with later starts finish early.)
+  const int kstart = PADDED ? __builtin_amdgcn_readfirstlane(starts[b]) : 0;   // (uniform: keeps the row start scalar)
+  const int T = Tp - kstart;
+  const int nqb_all = (Tp + 127) >> 7;
+  const bool pairs = nqb != nqb_all;
+  const int nqa = PADDED ? (T + 127) >> 7 : nqb_all;
+  const int nqr = PADDED ? (pairs ? (nqa + 1) >> 1 : nqa) : nqb;
+  if (PADDED) {
+    // pad query rows of the (unshifted) blocks this workgroup is dealt -- bx and, with pairs, its mirror: zeros, no K / V work
+    for (int k = 0; k < (pairs ? 2 : 1); ++k) {
+      const int ob = k ? nqb_all - 1 - bx : bx;
+      if (k && ob == bx) break;
+      for (int idx = tid; idx < 128 * 16; idx += 256) {
+        const int row = ob * 128 + (idx >> 4);
+        if (row < kstart) *(uint4*)(out + ((long)b * Tp + row) * ldo + (long)hh * D + 8 * (idx & 15)) = uint4{0u, 0u, 0u, 0u};
+      }
+    }
+    if (bx >= nqr) return;
+  }
+  const int npass = (pairs && nqa - 1 - bx != bx) ? 2 : 1;
   const int wsub = rev ? 3 - wave : wave;
   const int kh = hh / (heads / kv_heads);
-  const bf16_t* kbase = kc + (long)(b0 + b) * kv_batch + (long)kh * D;
-  const bf16_t* vbase = vc + (long)(b0 + b) * kv_batch + (long)kh * D;
+  const bf16_t* kbase = kc + (long)(b0 + b) * kv_batch + (long)kh * D + (long)kstart * kv_row;
+  const bf16_t* vbase = vc + (long)(b0 + b) * kv_batch + (long)kh * D + (long)kstart * kv_row;
   const float qscale = POST_SCALE ? 1.0f : scaling;
 
   // ---- staging by LDS-DMA: instruction j of wave w moves key rows 16 j + 4 w + (lane >> 4) of the tile, one 16-byte chunk per lane,
@@ -403,7 +440,7 @@ __global__ __launch_bounds__(256, 2) void lia_attn_prefill128_kernel(const bf16_
   const int lane = lane_p_;
   const int r = lane & 31, h = lane >> 5;
   // (the blocks in reverse order for every other (batch row, head), as the waves: see `rev`)
-  const int bxp = (nqb != nqb_all) ? (((pass ^ rev) & 1) ? nqb_all - 1 - bx : bx) : (rev ? nqb - 1 - bx : bx);
+  const int bxp = pairs ? (((pass ^ rev) & 1) ? nqa - 1 - bx : bx) : (rev ? nqr - 1 - bx : bx);
   const int q_wg = bxp * 128;
   const int q_wave = q_wg + wsub * 32;
   // (the first block's output staging lives in stage buffer 0, where the second block's first K tile goes)
@@ -416,7 +453,7 @@ __global__ __launch_bounds__(256, 2) void lia_attn_prefill128_kernel(const bf16_
   bf16x8 qf[8];
   {
     const int qrow = min(q_wave + r, T - 1);
-    const bf16_t* qp = q + ((long)b * T + qrow) * ldq + (long)hh * D;
+    const bf16_t* qp = q + ((long)b * Tp + kstart + qrow) * ldq + (long)hh * D;
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       uint4 v = *(const uint4*)(qp + 16 * s + 8 * h);
@@ -713,10 +750,26 @@ __global__ __launch_bounds__(256, 2) void lia_attn_prefill128_kernel(const bf16_
     for (int i = 0; i < 8; ++i) {
       const int rr = 4 * i + orow;
       const uint4 v = *(const uint4*)(ob + rr * 256 + ((oc ^ (rr & 15)) << 4));
-      if (q_wave + rr < T && st_on) *(uint4*)(out + ((long)b * T + q_wave + rr) * ldo + (long)hh * D + 8 * oc) = v;
+      if (q_wave + rr < T && st_on) *(uint4*)(out + ((long)b * Tp + kstart + q_wave + rr) * ldo + (long)hh * D + 8 * oc) = v;
     }
   }
   }   // pass
+}
+
+template <int POST_SCALE>
+__global__ __launch_bounds__(256, 2) void lia_attn_prefill128_kernel(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ kc,
+                                                                  const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int T,
+                                                                  int heads, int kv_heads, long kv_row, long kv_batch, int b0, float scaling,
+                                                                  int nqb, int n_groups) {
+  lia_attn_prefill128_body<POST_SCALE, 0>(q, ldq, kc, vc, out, ldo, T, heads, kv_heads, kv_row, kv_batch, b0, scaling, nqb, n_groups, nullptr);
+}
+// starts: per served row b (the caller passes its table + b0)
+template <int POST_SCALE>
+__global__ __launch_bounds__(256, 2) void lia_attn_prefill128_padded_kernel(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ kc,
+                                                                         const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int T,
+                                                                         int heads, int kv_heads, long kv_row, long kv_batch, int b0, float scaling,
+                                                                         int nqb, int n_groups, const int* __restrict__ starts) {
+  lia_attn_prefill128_body<POST_SCALE, 1>(q, ldq, kc, vc, out, ldo, T, heads, kv_heads, kv_row, kv_batch, b0, scaling, nqb, n_groups, starts);
 }
 
 
@@ -737,15 +790,19 @@ template <int CTRL> __device__ __forceinline__ float dpp_f32(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
 }
 
-template <int D, int G>
-__global__ __launch_bounds__(256) void lia_attn_decode_kernel(const bf16_t* __restrict__ q, long ldq,
-                                                               const bf16_t* __restrict__ kc,
-                                                               const bf16_t* __restrict__ vc, bf16_t* __restrict__ out,
-                                                               long ldo, int S, int heads, int kv_heads, int Bc, int b0,
-                                                               float scaling, int post_scale) {
+// PADDED: the row's keys are kstart .. Sp - 1 (kstart = starts[b] <= the query's position Sp - 1): the keys of a sequence of Sp - kstart
+// tokens starting at kstart, as in the prefill kernels -- the key loop starts at kstart, no key below it is read.
+// starts: per served row b (the caller passes its table + b0); PADDED = 0 never reads it
+template <int D, int G, int PADDED>
+__global__ __launch_bounds__(256) void lia_attn_decode_kernel(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ kc,
+                                                               const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int Sp,
+                                                               int heads, int kv_heads, int Bc, int b0, float scaling, int post_scale,
+                                                               const int* __restrict__ starts) {
   constexpr int LPK = D / 8;          // lanes per key
   constexpr int KPP = 256 / LPK;      // keys per pass of the workgroup
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int kstart = PADDED ? __builtin_amdgcn_readfirstlane(starts[blockIdx.y]) : 0;   // (uniform: keeps the row start scalar)
+  const int S = Sp - kstart;
   const int Spad = (S + 3) & ~3;
   float* sc = (float*)smem;                                   // [G][Spad] scores -> probabilities
   float* red = sc + (size_t)G * Spad;                         // [4 waves][G][D] partial outputs
@@ -753,8 +810,8 @@ __global__ __launch_bounds__(256) void lia_attn_decode_kernel(const bf16_t* __re
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int kh = blockIdx.x, b = blockIdx.y;
   const long kv_row = (long)Bc * kv_heads * D;
-  const bf16_t* kbase = kc + ((long)(b0 + b) * kv_heads + kh) * D;
-  const bf16_t* vbase = vc + ((long)(b0 + b) * kv_heads + kh) * D;
+  const bf16_t* kbase = kc + ((long)(b0 + b) * kv_heads + kh) * D + (long)kstart * kv_row;
+  const bf16_t* vbase = vc + ((long)(b0 + b) * kv_heads + kh) * D + (long)kstart * kv_row;
   const float qscale = post_scale ? 1.0f : scaling;
   const int sub = tid % LPK, kslot = tid / LPK;
 
@@ -916,9 +973,10 @@ __global__ __launch_bounds__(256) void lia_attn_decode_kernel(const bf16_t* __re
 }
 
 
-extern "C" int lia_attn_prefill_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
-                                       int B, int T, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
-                                       hipStream_t st) {
+// starts == nullptr: the unpadded kernels; otherwise their PADDED instantiations with the row starts starts[0 .. B - 1]
+// (device memory, 0 <= starts[b] <= T - 1)
+static int prefill_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T,
+                          int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, hipStream_t st) {
   if (B <= 0 || T <= 0) return 0;
   if (kv_heads <= 0 || heads % kv_heads) return -1;
   dim3 grid((T + 127) / 128, heads, B);
@@ -946,20 +1004,46 @@ extern "C" int lia_attn_prefill_launch(const bf16_t* q, long ldq, const bf16_t* 
       const unsigned nwg = xcd_order ? (unsigned)(((n_groups + 7) / 8) * 8 * nqb * (heads / kv_heads)) : (unsigned)(nqb * heads * B);
       if (!xcd_order) n_groups = 0;
       const dim3 grid128(nwg);
+      if (starts) {
+        if (post_scale) hipLaunchKernelGGL(lia_attn_prefill128_padded_kernel<1>, grid128, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, (long)Bc * hd, hd, b0, scaling, nqb, n_groups, starts);
+        else hipLaunchKernelGGL(lia_attn_prefill128_padded_kernel<0>, grid128, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, (long)Bc * hd, hd, b0, scaling, nqb, n_groups, starts);
+        break;
+      }
       if (post_scale) hipLaunchKernelGGL(lia_attn_prefill128_kernel<1>, grid128, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, (long)Bc * hd, hd, b0, scaling, nqb, n_groups);
       else hipLaunchKernelGGL(lia_attn_prefill128_kernel<0>, grid128, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, (long)Bc * hd, hd, b0, scaling, nqb, n_groups);
       break;
     }
-    case 64: hipLaunchKernelGGL(lia_attn_prefill_kernel<64>, grid, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, Bc, b0, scaling, post_scale); break;
-    case 32: hipLaunchKernelGGL(lia_attn_prefill_kernel<32>, grid, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, Bc, b0, scaling, post_scale); break;
+    case 64:
+      if (starts) hipLaunchKernelGGL((lia_attn_prefill_kernel<64, 1>), grid, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, Bc, b0, scaling, post_scale, starts);
+      else hipLaunchKernelGGL((lia_attn_prefill_kernel<64, 0>), grid, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, Bc, b0, scaling, post_scale, nullptr);
+      break;
+    case 32:
+      if (starts) hipLaunchKernelGGL((lia_attn_prefill_kernel<32, 1>), grid, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, Bc, b0, scaling, post_scale, starts);
+      else hipLaunchKernelGGL((lia_attn_prefill_kernel<32, 0>), grid, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, Bc, b0, scaling, post_scale, nullptr);
+      break;
     default: return -1;
   }
   return 0;
 }
 
+extern "C" int lia_attn_prefill_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
+                                       int B, int T, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
+                                       hipStream_t st) {
+  return prefill_launch(q, ldq, kc, vc, out, ldo, B, T, heads, kv_heads, d, Bc, b0, post_scale, nullptr, st);
+}
+
+// left-padded rows (the reference's CPU branch with an HF padding mask, lia/modeling_opt.py:1133 + mha_fusion.py:532-566):
+// served row b's query i >= starts[b] attends keys starts[b] .. i; rows i < starts[b] are zeros.  starts: device, B entries.
+extern "C" int lia_attn_prefill_padded_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
+                                              int B, int T, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
+                                              const int* starts, hipStream_t st) {
+  if (!starts) return -1;
+  return prefill_launch(q, ldq, kc, vc, out, ldo, B, T, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
+}
+
 template <int D>
 static int launch_decode(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int S, int heads,
-                         int kv_heads, int Bc, int b0, float scaling, int post_scale, hipStream_t st) {
+                         int kv_heads, int Bc, int b0, float scaling, int post_scale, const int* starts, hipStream_t st) {
   const int G = heads / kv_heads;
   dim3 grid(kv_heads, B);
   const int kpp = 256 / (D / 8);
@@ -968,10 +1052,14 @@ static int launch_decode(const bf16_t* q, long ldq, const bf16_t* kc, const bf16
   size_t lds = ((size_t)G * Spad + (size_t)4 * G * D + (size_t)G * 8) * sizeof(float);
   if (lds > 160 * 1024) return -1;
 #define LIA_DEC(GV)                                                                                                            \
-  {                                                                                                                            \
+  if (starts) {                                                                                                                \
     static bool attr = false;                                                                                                  \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)lia_attn_decode_kernel<D, GV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-    hipLaunchKernelGGL((lia_attn_decode_kernel<D, GV>), grid, dim3(256), lds, st, q, ldq, kc, vc, out, ldo, S, heads, kv_heads, Bc, b0, scaling, post_scale); \
+    if (!attr) { (void)hipFuncSetAttribute((const void*)lia_attn_decode_kernel<D, GV, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
+    hipLaunchKernelGGL((lia_attn_decode_kernel<D, GV, 1>), grid, dim3(256), lds, st, q, ldq, kc, vc, out, ldo, S, heads, kv_heads, Bc, b0, scaling, post_scale, starts); \
+  } else {                                                                                                                     \
+    static bool attr = false;                                                                                                  \
+    if (!attr) { (void)hipFuncSetAttribute((const void*)lia_attn_decode_kernel<D, GV, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
+    hipLaunchKernelGGL((lia_attn_decode_kernel<D, GV, 0>), grid, dim3(256), lds, st, q, ldq, kc, vc, out, ldo, S, heads, kv_heads, Bc, b0, scaling, post_scale, nullptr); \
   }
   switch (G) {
     case 1: LIA_DEC(1) break;
@@ -984,16 +1072,29 @@ static int launch_decode(const bf16_t* q, long ldq, const bf16_t* kc, const bf16
   return 0;
 }
 
-extern "C" int lia_attn_decode_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
-                                      int B, int S, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
-                                      hipStream_t st) {
+static int decode_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int S, int heads,
+                         int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, hipStream_t st) {
   if (B <= 0 || S <= 0) return 0;
   if (kv_heads <= 0 || heads % kv_heads) return -1;
   const float scaling = 1.0f / sqrtf((float)d);
   switch (d) {
-    case 128: return launch_decode<128>(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, Bc, b0, scaling, post_scale, st);
-    case 64: return launch_decode<64>(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, Bc, b0, scaling, post_scale, st);
-    case 32: return launch_decode<32>(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, Bc, b0, scaling, post_scale, st);
+    case 128: return launch_decode<128>(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, Bc, b0, scaling, post_scale, starts, st);
+    case 64: return launch_decode<64>(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, Bc, b0, scaling, post_scale, starts, st);
+    case 32: return launch_decode<32>(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, Bc, b0, scaling, post_scale, starts, st);
     default: return -1;
   }
+}
+
+extern "C" int lia_attn_decode_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
+                                      int B, int S, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
+                                      hipStream_t st) {
+  return decode_launch(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, d, Bc, b0, post_scale, nullptr, st);
+}
+
+// one query per served row at position S - 1 over keys starts[b] .. S - 1 (starts: device, B entries, each <= S - 1)
+extern "C" int lia_attn_decode_padded_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
+                                             int B, int S, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
+                                             const int* starts, hipStream_t st) {
+  if (!starts) return -1;
+  return decode_launch(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
 }

@@ -189,6 +189,36 @@ extern "C" void lia_embed_launch(const int64_t* ids, const bf16_t* tok, const bf
   hipLaunchKernelGGL(lia_embed_kernel, dim3(B * T), dim3(256), 0, st, ids, tok, pos, y, T, past_len, H);
 }
 
+// left-padded rows: row b's tokens start at cache position starts[b]; the token at position p = past_len + t takes the learned
+// position p - starts[b] + 2, a pad position (p < starts[b]) position 1 -- HF's (cumsum(mask) * mask) - 1 + 2
+// (lia/modeling_opt.py:368-378).  The same bf16 add as lia_embed_kernel.
+__global__ __launch_bounds__(256) void lia_embed_padded_kernel(const int64_t* __restrict__ ids, const bf16_t* __restrict__ tok,
+                                                                const bf16_t* __restrict__ pos, bf16_t* __restrict__ y, int T,
+                                                                int past_len, int H, const int* __restrict__ starts) {
+  const long row = blockIdx.x;
+  const int t = (int)(row % T);
+  const int p = past_len + t - starts[row / T];
+  const bf16_t* te = tok + ids[row] * (long)H;
+  const bf16_t* pe = pos + (long)(p >= 0 ? p + 2 : 1) * H;
+  bf16_t* yo = y + row * (long)H;
+  for (int i = threadIdx.x; i < (H >> 3); i += 256) {
+    uint4 a = *(const uint4*)(te + 8 * i), pv = *(const uint4*)(pe + 8 * i);
+    const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, pw[4] = {pv.x, pv.y, pv.z, pv.w};
+    uint32_t o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      o[j] = pack_bf16x2(bf2f(aw[j] & 0xffff) + bf2f(pw[j] & 0xffff), bf2f(aw[j] >> 16) + bf2f(pw[j] >> 16));
+    *(uint4*)(yo + 8 * i) = uint4{o[0], o[1], o[2], o[3]};
+  }
+}
+
+// starts: device, B entries
+extern "C" void lia_embed_padded_launch(const int64_t* ids, const bf16_t* tok, const bf16_t* pos, bf16_t* y, int B, int T,
+                                        int past_len, int H, const int* starts, hipStream_t st) {
+  if (B * T <= 0) return;
+  hipLaunchKernelGGL(lia_embed_padded_kernel, dim3(B * T), dim3(256), 0, st, ids, tok, pos, y, T, past_len, H, starts);
+}
+
 // Greedy argmax over bf16 logits [B, vocab], first maximal index on ties (greedy_search.py:367,395).
 // `suppress` (or -1): a token whose score counts as -inf -- what HF's MinNewTokensLengthLogitsProcessor does
 // to EOS while min_new_tokens is not reached (run_generation.py:173,179-182 sets min_new_tokens = max_new_tokens).

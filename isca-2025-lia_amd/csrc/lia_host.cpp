@@ -120,9 +120,24 @@ static inline lia_bf16 f32_to_bf16(float f) {
 // the output (:826-828).  beam_idx is the identity under greedy search (:1393-1402) and is not
 // materialised.  Work is split over (batch row, group of heads) so that for each cached position a
 // thread streams one contiguous run of the [S][B][h][d] cache.
-// the attention of one layer as a TEAM function (see the note above): every thread of the enclosing region calls it
+// row starts of a left-padded batch: each within the row's S = pos0 + T cache positions, before its last one
+static int check_starts(const char* who, const int* starts, int B, int S) {
+  if (!starts) return LIA_OK;
+  for (int b = 0; b < B; ++b)
+    if (starts[b] < 0 || starts[b] > S - 1) {
+      lia_set_error("%s: starts[%d] = %d outside [0, %d]", who, b, starts[b], S - 1);
+      return LIA_ERR_INVALID;
+    }
+  return LIA_OK;
+}
+
+// the attention of one layer as a TEAM function (see the note above): every thread of the enclosing region calls it.
+// starts (host, B entries, or NULL = all 0): left padding -- served row b attends keys starts[b] .. pos0 + t, the additive
+// finfo.min mask of the reference's CPU branch (mha_fusion.py:532-566, exp of it is 0); a query at a pad position
+// (pos0 + t < starts[b]) gets a zero row.
 static void host_attention_team(const lia_bf16* q, const lia_bf16* k, const lia_bf16* v, lia_bf16* kcache, lia_bf16* vcache,
-                                lia_bf16* out, int B, int T, int pos0, int heads, int head_dim, int cache_batch, int b0) {
+                                lia_bf16* out, int B, int T, int pos0, int heads, int head_dim, int cache_batch, int b0,
+                                const int* starts = nullptr) {
   const int d = head_dim;
   const long hd = (long)heads * d;
   const long row = (long)cache_batch * hd;
@@ -150,10 +165,16 @@ static void host_attention_team(const lia_bf16* q, const lia_bf16* k, const lia_
           memcpy(kcache + (long)(pos0 + t) * row + coff, k + src, (size_t)G * d * sizeof(lia_bf16));
           memcpy(vcache + (long)(pos0 + t) * row + coff, v + src, (size_t)G * d * sizeof(lia_bf16));
         }
+        const int j0 = starts ? starts[b] : 0;
         for (int t = 0; t < T; ++t) {
-          const int lim = pos0 + t;  // keys 0..lim (causal inside the new block)
+          const int lim = pos0 + t;  // keys j0..lim (causal inside the new block)
+          if (lim < j0) {
+            lia_bf16* op = out + ((long)b * T + t) * hd + (long)g * G * d;
+            memset(op, 0, (size_t)G * d * sizeof(lia_bf16));
+            continue;
+          }
           const lia_bf16* qp = q + ((long)b * T + t) * hd + (long)g * G * d;
-          for (int j = 0; j <= lim; ++j) {
+          for (int j = j0; j <= lim; ++j) {
             const lia_bf16* kp = kcache + (long)j * row + coff;
             // the run of this (row, head group) is G*d*2 bytes at a stride far beyond a page: the hardware prefetcher does
             // not follow it, so every line of the run PF rows ahead is requested here (one line alone: 13 GB/s per thread)
@@ -171,19 +192,19 @@ static void host_attention_team(const lia_bf16* q, const lia_bf16* k, const lia_
           for (int hh = 0; hh < G; ++hh) {
             float* s = sc + (size_t)hh * S;
             float mx = -INFINITY;
-            for (int j = 0; j <= lim; ++j) mx = s[j] > mx ? s[j] : mx;
+            for (int j = j0; j <= lim; ++j) mx = s[j] > mx ? s[j] : mx;
             float sum = 0.f;
-            for (int j = 0; j <= lim; ++j) {
+            for (int j = j0; j <= lim; ++j) {
               s[j] = expf(s[j] - mx);
               sum += s[j];
             }
             const float inv = 1.0f / sum;
-            for (int j = 0; j <= lim; ++j) s[j] *= inv;
+            for (int j = j0; j <= lim; ++j) s[j] *= inv;
           }
           __m512 o[8][8];  // [head in group][16-wide slice of d] (d <= 128)
           for (int hh = 0; hh < G; ++hh)
             for (int i = 0; i < nv; ++i) o[hh][i] = _mm512_setzero_ps();
-          for (int j = 0; j <= lim; ++j) {
+          for (int j = j0; j <= lim; ++j) {
             const lia_bf16* vp = vcache + (long)j * row + coff;
             if (j + PF <= lim) {
               const char* pf = (const char*)(vcache + (long)(j + PF) * row + coff);
@@ -206,9 +227,10 @@ static void host_attention_team(const lia_bf16* q, const lia_bf16* k, const lia_
   }
 }
 
-extern "C" int lia_host_attention(const lia_bf16* q, const lia_bf16* k, const lia_bf16* v, lia_bf16* kcache,
-                                  lia_bf16* vcache, lia_bf16* out, int B, int T, int pos0, int heads, int head_dim,
-                                  int cache_batch, int b0, int n_threads) {
+// starts: host, B entries (validated here: 0 <= starts[b] <= pos0 + T - 1, so every row keeps its last query), or NULL
+static int host_attention(const lia_bf16* q, const lia_bf16* k, const lia_bf16* v, lia_bf16* kcache, lia_bf16* vcache,
+                          lia_bf16* out, int B, int T, int pos0, int heads, int head_dim, int cache_batch, int b0, int n_threads,
+                          const int* starts) {
   if (!q || !k || !v || !kcache || !vcache || !out) {
     lia_set_error("lia_host_attention: NULL tensor");
     return LIA_ERR_MISSING;
@@ -223,16 +245,30 @@ extern "C" int lia_host_attention(const lia_bf16* q, const lia_bf16* k, const li
     lia_set_error("lia_host_attention: head_dim %d > 128 is not supported", head_dim);
     return LIA_ERR_INVALID;
   }
+  if (int rc = check_starts("lia_host_attention_padded", starts, B, pos0 + T)) return rc;
   if (n_threads <= 0) n_threads = omp_get_max_threads();
   HostCallScope scope;
   HostCall* const call = scope.call();
 #pragma omp parallel num_threads(n_threads)
   {
     HostCall* const prev = team_enter(call);
-    host_attention_team(q, k, v, kcache, vcache, out, B, T, pos0, heads, head_dim, cache_batch, b0);
+    host_attention_team(q, k, v, kcache, vcache, out, B, T, pos0, heads, head_dim, cache_batch, b0, starts);
     team_leave(prev);
   }
   return scope.result("lia_host_attention");
+}
+
+extern "C" int lia_host_attention(const lia_bf16* q, const lia_bf16* k, const lia_bf16* v, lia_bf16* kcache,
+                                  lia_bf16* vcache, lia_bf16* out, int B, int T, int pos0, int heads, int head_dim,
+                                  int cache_batch, int b0, int n_threads) {
+  return host_attention(q, k, v, kcache, vcache, out, B, T, pos0, heads, head_dim, cache_batch, b0, n_threads, nullptr);
+}
+
+extern "C" int lia_host_attention_padded(const lia_bf16* q, const lia_bf16* k, const lia_bf16* v, lia_bf16* kcache,
+                                         lia_bf16* vcache, lia_bf16* out, int B, int T, int pos0, int heads, int head_dim,
+                                         int cache_batch, int b0, int n_threads, const int* starts) {
+  if (!starts) { lia_set_error("lia_host_attention_padded: NULL starts"); return LIA_ERR_MISSING; }
+  return host_attention(q, k, v, kcache, vcache, out, B, T, pos0, heads, head_dim, cache_batch, b0, n_threads, starts);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -650,7 +686,7 @@ static LayerScratch& layer_scratch(size_t need) {
 // one decode-sized layer inside an enclosing parallel region (every thread calls it); sc: 6 * mh + M * F bf16 of scratch
 static void host_layer_team(const lia_layer_desc* d, const lia_bf16* const* W, const lia_bf16* x, lia_bf16* y, lia_bf16* kcache,
                             lia_bf16* vcache, int cache_batch, int B, int T, int pos0, int b0, lia_bf16* sc, size_t mh,
-                            LiaTeamBarrier& bar, int& sense) {
+                            LiaTeamBarrier& bar, int& sense, const int* starts) {
   const int H = d->hidden, F = d->ffn, heads = d->heads, M = B * T;
   lia_bf16 *ln = sc, *q = ln + mh, *k = q + mh, *v = k + mh, *ao = v + mh, *h1 = ao + mh, *f1 = h1 + mh;
   host_layernorm_team(x, W[0], W[1], ln, M, H, d->ln_eps);
@@ -659,7 +695,7 @@ static void host_layer_team(const lia_layer_desc* d, const lia_bf16* const* W, c
   host_linear_skinny_team(ln, W[6], W[7], nullptr, v, M, H, H, 0);
   host_linear_skinny_team(ln, W[2], W[3], nullptr, q, M, H, H, 0);
   team_barrier(bar, sense);
-  host_attention_team(q, k, v, kcache, vcache, ao, B, T, pos0, heads, H / heads, cache_batch, b0);
+  host_attention_team(q, k, v, kcache, vcache, ao, B, T, pos0, heads, H / heads, cache_batch, b0, starts);
   team_barrier(bar, sense);
   host_linear_skinny_team(ao, W[8], W[9], x, h1, M, H, H, 0);
   team_barrier(bar, sense);
@@ -673,9 +709,9 @@ static void host_layer_team(const lia_layer_desc* d, const lia_bf16* const* W, c
 // One decoder layer on the host: OPTDecoderLayer_forward with gpu_linear = gpu_attn = False (decoder.py:191-193,
 // 206, 248-250, 276, 286-287, 312-315; attentions.py:365-376, 401-440).  weights: 16 HOST pointers in create_buffer
 // order, row-major.  x, y: host [B,T,H]; cache: host [smax][cache_batch][h][d], rows pos0.. appended.
-extern "C" int lia_host_layer_forward(const lia_layer_desc* d, const void* const weights[16], const lia_bf16* x, lia_bf16* y,
-                                      lia_bf16* kcache, lia_bf16* vcache, int smax, int cache_batch, int B, int T, int pos0,
-                                      int b0, int n_threads) {
+static int host_layer_forward(const lia_layer_desc* d, const void* const weights[16], const lia_bf16* x, lia_bf16* y,
+                              lia_bf16* kcache, lia_bf16* vcache, int smax, int cache_batch, int B, int T, int pos0,
+                              int b0, int n_threads, const int* starts) {
   if (!d || !weights || !x || !y || !kcache || !vcache) { lia_set_error("lia_host_layer_forward: NULL argument"); return LIA_ERR_MISSING; }
   for (int i = 0; i < 16; ++i)
     if (!weights[i]) { lia_set_error("lia_host_layer_forward: weights[%d] is NULL", i); return LIA_ERR_MISSING; }
@@ -686,6 +722,7 @@ extern "C" int lia_host_layer_forward(const lia_layer_desc* d, const void* const
     return LIA_ERR_INVALID;
   }
   if (int rc = host_isa_ok("lia_host_layer_forward")) return rc;
+  if (int rc = check_starts("lia_host_layer_forward_padded", starts, B, pos0 + T)) return rc;
   if (n_threads > 0) omp_set_num_threads(n_threads);
   const lia_bf16* const* W = (const lia_bf16* const*)weights;
   const long M = (long)B * T;
@@ -706,7 +743,7 @@ extern "C" int lia_host_layer_forward(const lia_layer_desc* d, const void* const
     {
       HostCall* const prev = team_enter(call);
       int sense = 0;
-      host_layer_team(d, W, x, y, kcache, vcache, cache_batch, B, T, pos0, b0, sc, mh, bar, sense);
+      host_layer_team(d, W, x, y, kcache, vcache, cache_batch, B, T, pos0, b0, sc, mh, bar, sense, starts);
       team_leave(prev);
     }
     return scope.result("lia_host_layer_forward");
@@ -715,7 +752,7 @@ extern "C" int lia_host_layer_forward(const lia_layer_desc* d, const void* const
   host_linear(ln, W[4], W[5], nullptr, k, M, H, H, 0);
   host_linear(ln, W[6], W[7], nullptr, v, M, H, H, 0);
   host_linear(ln, W[2], W[3], nullptr, q, M, H, H, 0);
-  int rc = lia_host_attention(q, k, v, kcache, vcache, ao, B, T, pos0, heads, H / heads, cache_batch, b0, n_threads);
+  int rc = host_attention(q, k, v, kcache, vcache, ao, B, T, pos0, heads, H / heads, cache_batch, b0, n_threads, starts);
   if (rc) return rc;                                                       // (the block stays with the thread; the next call reuses it)
   host_linear(ao, W[8], W[9], x, h1, M, H, H, 0);
   host_layernorm(h1, W[10], W[11], ln, M, H, d->ln_eps);
@@ -725,13 +762,26 @@ extern "C" int lia_host_layer_forward(const lia_layer_desc* d, const void* const
   return scope.result("lia_host_layer_forward");
 }
 
+extern "C" int lia_host_layer_forward(const lia_layer_desc* d, const void* const weights[16], const lia_bf16* x, lia_bf16* y,
+                                      lia_bf16* kcache, lia_bf16* vcache, int smax, int cache_batch, int B, int T, int pos0,
+                                      int b0, int n_threads) {
+  return host_layer_forward(d, weights, x, y, kcache, vcache, smax, cache_batch, B, T, pos0, b0, n_threads, nullptr);
+}
+
+extern "C" int lia_host_layer_forward_padded(const lia_layer_desc* d, const void* const weights[16], const lia_bf16* x, lia_bf16* y,
+                                             lia_bf16* kcache, lia_bf16* vcache, int smax, int cache_batch, int B, int T, int pos0,
+                                             int b0, int n_threads, const int* starts) {
+  if (!starts) { lia_set_error("lia_host_layer_forward_padded: NULL starts"); return LIA_ERR_MISSING; }
+  return host_layer_forward(d, weights, x, y, kcache, vcache, smax, cache_batch, B, T, pos0, b0, n_threads, starts);
+}
+
 // n_layers consecutive decode-sized layers (policy 1's decode step: every layer on the host) in ONE parallel region: the hidden
 // state ping-pongs between x and y (the result is in x when n_layers is even, in y when it is odd -- the return value says
 // which: 0 = x, 1 = y, negative = error).  With a parked OpenMP team every region costs a futex wake per thread; an opt-125m
 // token at batch 1 is twelve 0.1 ms layers (configs[0]).
-extern "C" int lia_host_layers_forward(const lia_layer_desc* d, int n_layers, const void* const* weights, lia_bf16* x, lia_bf16* y,
-                                       void* const* kcaches, void* const* vcaches, int smax, int cache_batch, int B, int T,
-                                       int pos0, int b0, int n_threads) {
+static int host_layers_forward(const lia_layer_desc* d, int n_layers, const void* const* weights, lia_bf16* x, lia_bf16* y,
+                               void* const* kcaches, void* const* vcaches, int smax, int cache_batch, int B, int T,
+                               int pos0, int b0, int n_threads, const int* starts) {
   if (!d || !weights || !x || !y || !kcaches || !vcaches || n_layers <= 0) { lia_set_error("lia_host_layers_forward: NULL argument"); return LIA_ERR_MISSING; }
   for (long i = 0; i < 16L * n_layers; ++i)
     if (!weights[i]) { lia_set_error("lia_host_layers_forward: weights[%ld][%ld] is NULL", i / 16, i % 16); return LIA_ERR_MISSING; }
@@ -746,6 +796,7 @@ extern "C" int lia_host_layers_forward(const lia_layer_desc* d, int n_layers, co
     return LIA_ERR_INVALID;
   }
   if (int rc = host_isa_ok("lia_host_layers_forward")) return rc;
+  if (int rc = check_starts("lia_host_layers_forward_padded", starts, B, pos0 + T)) return rc;
   if (n_threads > 0) omp_set_num_threads(n_threads);
   const size_t mh = ((size_t)M * H + 31) & ~(size_t)31, mf = ((size_t)M * F + 31) & ~(size_t)31;
   lia_bf16* const sc = layer_scratch(6 * mh + mf).p;     // (fetched by the caller: thread_local)
@@ -760,7 +811,7 @@ extern "C" int lia_host_layers_forward(const lia_layer_desc* d, int n_layers, co
     lia_bf16 *in = x, *out = y;
     for (int l = 0; l < n_layers; ++l) {
       host_layer_team(d, (const lia_bf16* const*)(weights + 16L * l), in, out, (lia_bf16*)kcaches[l], (lia_bf16*)vcaches[l], cache_batch, B, T,
-                      pos0, b0, sc, mh, bar, sense);
+                      pos0, b0, sc, mh, bar, sense, starts);
       team_barrier(bar, sense);
       lia_bf16* t = in; in = out; out = t;
     }
@@ -768,6 +819,19 @@ extern "C" int lia_host_layers_forward(const lia_layer_desc* d, int n_layers, co
   }
   if (int rc = scope.result("lia_host_layers_forward")) return rc;
   return n_layers & 1;
+}
+
+extern "C" int lia_host_layers_forward(const lia_layer_desc* d, int n_layers, const void* const* weights, lia_bf16* x, lia_bf16* y,
+                                       void* const* kcaches, void* const* vcaches, int smax, int cache_batch, int B, int T,
+                                       int pos0, int b0, int n_threads) {
+  return host_layers_forward(d, n_layers, weights, x, y, kcaches, vcaches, smax, cache_batch, B, T, pos0, b0, n_threads, nullptr);
+}
+
+extern "C" int lia_host_layers_forward_padded(const lia_layer_desc* d, int n_layers, const void* const* weights, lia_bf16* x, lia_bf16* y,
+                                              void* const* kcaches, void* const* vcaches, int smax, int cache_batch, int B, int T,
+                                              int pos0, int b0, int n_threads, const int* starts) {
+  if (!starts) { lia_set_error("lia_host_layers_forward_padded: NULL starts"); return LIA_ERR_MISSING; }
+  return host_layers_forward(d, n_layers, weights, x, y, kcaches, vcaches, smax, cache_batch, B, T, pos0, b0, n_threads, starts);
 }
 
 // memcpy by a team (the streamer's staging of pageable sources, lia_api.hip::staged_copy): 1 MiB pieces dealt out statically;

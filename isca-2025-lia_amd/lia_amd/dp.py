@@ -53,9 +53,14 @@ class DataParallelGroup:
     def is_root(self):
         return self.rank == self.root
 
-    def shard(self, input_ids):
+    def shard(self, input_ids, attention_mask=None):
+        """this rank's rows of input_ids -- and, given an attention_mask ([B, T] like input_ids), (ids, the same rows of the mask)"""
         lo, hi = shard_rows(input_ids.shape[0], self.rank, self.world)
-        return input_ids[lo:hi]
+        if attention_mask is None:
+            return input_ids[lo:hi]
+        if attention_mask.shape[0] != input_ids.shape[0]:
+            raise ValueError(f"attention_mask has {attention_mask.shape[0]} rows, input_ids {input_ids.shape[0]}")
+        return input_ids[lo:hi], attention_mask[lo:hi]
 
     def gather_ids(self, ids_local, n_rows_total):
         """All ranks' generated ids, concatenated in row order (token ids are tiny; gathered once per generate)."""

@@ -15,12 +15,33 @@ latency_list[i] is the wall clock of greedy iteration i (prepare inputs -> forwa
 """
 import time
 
+import numpy as np
 import torch
 
 from .scheduler import KVState, OffloadScheduler
 
 LIA_KWARGS = ("prefill_policy", "decoding_policy", "no_overlap", "pin_weight", "gpu_percentage", "num_minibatch",
               "enable_cxl")
+
+
+def left_padding_starts(attention_mask, shape):
+    """Validate a left-padded HF attention_mask of input_ids' shape [B, T] and return the per-row starts s_b (int32 [B]: row b
+    is s_b zeros, then ones), or None when the mask is absent or all ones -- the unpadded route.  ValueError names the problem."""
+    if attention_mask is None:
+        return None
+    m = attention_mask.detach().cpu().numpy() if isinstance(attention_mask, torch.Tensor) else np.asarray(attention_mask)
+    if tuple(m.shape) != tuple(shape):
+        raise ValueError(f"attention_mask has shape {tuple(m.shape)}, input_ids {tuple(shape)}: they must match")
+    if m.dtype != np.bool_ and not np.isin(m, (0, 1)).all():
+        raise ValueError("attention_mask values must be 0 or 1")
+    m = m.astype(np.int32)
+    if (m.sum(axis=1) == 0).any():
+        raise ValueError(f"attention_mask rows {np.flatnonzero(m.sum(axis=1) == 0).tolist()} have no 1 (no token to attend)")
+    if (np.diff(m, axis=1) < 0).any():
+        raise ValueError("attention_mask must be left padded: a 1 before a 0 in rows "
+                         f"{np.flatnonzero((np.diff(m, axis=1) < 0).any(axis=1)).tolist()} (right padding or holes)")
+    starts = (m.shape[1] - m.sum(axis=1)).astype(np.int32)
+    return None if not starts.any() else starts
 
 
 def _scheduler_of(model):
@@ -43,6 +64,7 @@ def generate(model, input_ids, max_new_tokens=None, min_new_tokens=None, do_samp
     # unknown kwargs are NOT rejected: the reference disables that check so its flags reach forward()
     # (lia/generation_utils.py:1166-1170)
     lia = {k: model_kwargs.pop(k, None) for k in LIA_KWARGS}
+    attention_mask = model_kwargs.pop("attention_mask", None)
     lia = {"prefill_policy": 1 if lia["prefill_policy"] is None else lia["prefill_policy"],
            "decoding_policy": 1 if lia["decoding_policy"] is None else lia["decoding_policy"],
            "no_overlap": bool(lia["no_overlap"]), "pin_weight": bool(lia["pin_weight"]),
@@ -57,8 +79,23 @@ def generate(model, input_ids, max_new_tokens=None, min_new_tokens=None, do_samp
     # timed steps); max_steps ends the loop early while the caches stay sized for max_new_tokens (a short warm-up call)
     hooks = {"step_hook": model_kwargs.pop("step_hook", None), "max_steps": model_kwargs.pop("max_steps", None)}
     min_new = min_new_tokens or 0
-    return _greedy_search(model, input_ids, max_new_tokens, min_new, eos_token_id, pad_token_id, token_latency,
-                          return_logits, lia, **hooks)
+    ids = torch.as_tensor(input_ids, dtype=torch.int64).cpu()
+    starts = left_padding_starts(attention_mask, ids.shape) if ids.dim() == 2 else None
+    if starts is not None and getattr(model, "family", "opt") == "llama":
+        raise ValueError("attention_mask with padding (zeros) is not supported for Llama-family models: their RoPE positions "
+                         "are not per row yet; pass equal-length prompts")
+    sched = _scheduler_of(model)
+    if starts is None:
+        return _greedy_search(model, ids, max_new_tokens, min_new, eos_token_id, pad_token_id, token_latency,
+                              return_logits, lia, **hooks)
+    # left-padded batch: the scheduler serves every forward of this generation with the row starts; cleared when it ends so
+    # that a later unpadded generate() takes the unpadded route
+    sched.set_key_starts(starts)
+    try:
+        return _greedy_search(model, ids, max_new_tokens, min_new, eos_token_id, pad_token_id, token_latency,
+                              return_logits, lia, **hooks)
+    finally:
+        sched.set_key_starts(None)
 
 
 def _greedy_search(model, input_ids, max_new_tokens, min_new_tokens, eos_token_id, pad_token_id, token_latency,

@@ -34,6 +34,9 @@ def build_parser():
     p.add_argument("--token-latency", action="store_true")
     p.add_argument("--prompt", default=None, type=str,
                    help="input prompt for self-defined if needed (run_generation.py:87); needs the tokenizer files in the -m directory")
+    p.add_argument("--prompt-file", default=None, type=str,
+                   help="a text file with one prompt per line: the batch is the prompts in file order, cycled to --batch-size, left "
+                        "padded, with the matching attention_mask (needs the tokenizer files in the -m directory; not with --prompt)")
     p.add_argument("--profile", action="store_true",
                    help="one profiled generate() before the timed loop (run_generation.py:103,290-307 runs torch.profiler over five "
                         "there); here the library's own HIP-event brackets: GEMM time / rates per phase, host attention, link traffic")
@@ -132,6 +135,35 @@ def prompt_input_ids(args, vocab, tokenizer, out=print):
         raise SystemExit(f"[ERROR] the tokenizer produced ids outside the model's vocabulary of {vocab} entries")
     out("---- Prompt size:", int(row.shape[1]))
     return row.repeat(args.batch_size, 1)
+
+
+def prompt_file_inputs(args, vocab, tokenizer, pad_token_id, out=print):
+    """--prompt-file: one prompt per line (blank lines skipped), the batch = the prompts in file order cycled to --batch-size (as the
+    reference repeats its one prompt), each tokenized alone and left padded to the longest with the tokenizer's pad token (the
+    model's pad_token_id when the tokenizer has none).  Returns (input_ids int64 [B, T], attention_mask int64 [B, T])."""
+    if tokenizer is None:
+        raise SystemExit("[ERROR] --prompt-file needs a tokenizer: point -m at a checkpoint directory that ships its tokenizer files "
+                         f"({', '.join(TOKENIZER_FILES[:3])}); {args.model_id!r} has none")
+    with open(args.prompt_file, encoding="utf-8") as f:
+        prompts = [line.rstrip("\n") for line in f if line.strip()]
+    if not prompts:
+        raise SystemExit(f"[ERROR] --prompt-file {args.prompt_file!r} holds no prompt")
+    rows = []
+    for text in prompts:
+        r = tokenizer(text, return_tensors="pt").input_ids.to(torch.int64)[0]
+        if r.numel() == 0 or int(r.max()) >= vocab or int(r.min()) < 0:
+            raise SystemExit(f"[ERROR] the tokenizer produced ids outside the model's vocabulary of {vocab} entries for {text!r}")
+        rows.append(r)
+    pad = tokenizer.pad_token_id if tokenizer.pad_token_id is not None else pad_token_id
+    B, T = args.batch_size, max(int(r.numel()) for r in rows)
+    ids = torch.full((B, T), int(pad), dtype=torch.int64)
+    mask = torch.zeros((B, T), dtype=torch.int64)
+    for b in range(B):
+        r = rows[b % len(rows)]
+        ids[b, T - r.numel():] = r
+        mask[b, T - r.numel():] = 1
+    out("---- Prompt sizes:", [int(r.numel()) for r in rows])
+    return ids, mask
 
 
 def is_llama(args):
@@ -413,6 +445,8 @@ def main(argv=None):
 
 def _main(args, rec=None):
     print(args)
+    if args.prompt is not None and args.prompt_file is not None:
+        raise SystemExit("[ERROR] --prompt and --prompt-file exclude each other: one prompt for every row, or one per line of the file")
     if not args.benchmark:
         print("note: only the --benchmark protocol exists here; running it")
     # the reference's launch line is `OMP_NUM_THREADS=40 numactl -m 0 -C 0-39 python run.py ...` (README.md:78): host compute
@@ -465,7 +499,11 @@ def _main(args, rec=None):
         if args.cpu_layers < 0 and args.cpu_layers_start is not None:
             generate_kwargs["cpu_layers_start"] = args.cpu_layers_start
     tokenizer = load_tokenizer(args.model_id)
-    input_ids = prompt_input_ids(args, model.shape.vocab, tokenizer)
+    if args.prompt_file is not None:
+        input_ids, generate_kwargs["attention_mask"] = prompt_file_inputs(args, model.shape.vocab, tokenizer,
+                                                                          generate_kwargs.get("pad_token_id", 1))
+    else:
+        input_ids = prompt_input_ids(args, model.shape.vocab, tokenizer)
     if args.profile:
         profile_once(model, input_ids, generate_kwargs)
     total_time, total_list = 0.0, []
@@ -489,6 +527,9 @@ def _main(args, rec=None):
         total_new_tokens = [int(o.shape[0] - i_.shape[0]) for i_, o in zip(input_ids, gen_ids)]
         if tokenizer is not None and args.prompt is not None:                 # run_generation.py:321-323
             print(tokenizer.batch_decode(gen_ids, skip_special_tokens=True)[:1], total_new_tokens[:4], flush=True)
+        if tokenizer is not None and args.prompt_file is not None:           # every row: the rows hold different prompts
+            for b, text in enumerate(tokenizer.batch_decode(gen_ids[:, input_ids.shape[1]:], skip_special_tokens=True)):
+                print(f"row {b}: {text!r}", flush=True)
         print(gen_ids[0, input_ids.shape[1]:].tolist(), total_new_tokens[:4], flush=True)
         print("Iteration: %d, Time: %.6f sec" % (i, toc - tic), flush=True)
         if rec is not None:

@@ -26,6 +26,7 @@ import ctypes
 import itertools
 import os
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -740,9 +741,16 @@ class OffloadScheduler:
         self._place(s, kv_state, pin_weight, enable_cxl, max_new_tokens, cpu_layers, cpu_layers_start)
         m, sh, ctx = self.model, self.model.shape, self.ctx
         ids_dev = input_ids.to("cuda", non_blocking=False).contiguous()
-        N.check(ctx.lib.lia_embed(ctypes.c_void_p(ids_dev.data_ptr()), ctypes.c_void_p(m.embed_tokens.data_ptr()),
-                                  ctypes.c_void_p(m.embed_positions.data_ptr()), ctypes.c_void_p(s.x.data_ptr()), s.B, s.T, s.pos0,
-                                  sh.hidden, ctypes.c_void_p(ctx.stream)), "lia_embed")
+        st = self._key_starts_for(s.B)
+        if st is None:
+            N.check(ctx.lib.lia_embed(ctypes.c_void_p(ids_dev.data_ptr()), ctypes.c_void_p(m.embed_tokens.data_ptr()),
+                                      ctypes.c_void_p(m.embed_positions.data_ptr()), ctypes.c_void_p(s.x.data_ptr()), s.B, s.T, s.pos0,
+                                      sh.hidden, ctypes.c_void_p(ctx.stream)), "lia_embed")
+        else:
+            N.check(ctx.lib.lia_embed_padded(ctypes.c_void_p(ids_dev.data_ptr()), ctypes.c_void_p(m.embed_tokens.data_ptr()),
+                                             ctypes.c_void_p(m.embed_positions.data_ptr()), ctypes.c_void_p(s.x.data_ptr()), s.B, s.T,
+                                             s.pos0, sh.hidden, ctypes.c_void_p(st[1].data_ptr()), ctypes.c_void_p(ctx.stream)),
+                    "lia_embed_padded")
         if s.policy == 1 and s.n_gpu < s.L:
             self._await_kv(kv_state)
             hidden = self._host_layers(s.x, kv_state, s.n_gpu, s.B, s.T, s.pos0)  # resident prefix on the GPU, the rest on the CPU
@@ -754,6 +762,40 @@ class OffloadScheduler:
         logits, nxt = ctx.lm_head(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, sh.ln_eps, suppress_token)
         self._deliver(s, kv_state)
         return logits, nxt
+
+    # -- left-padded batches (generation.generate(..., attention_mask=)) -----------------------------------------------------
+    def set_key_starts(self, starts):
+        """starts: int32 [B] (row b's first real cache position) for every forward until the next call, or None: the unpadded
+        route.  The library context keeps its own table (lia_ctx_set_key_starts: every GPU layer call and the policy-2 host
+        attention read rows b0 .. b0 + B - 1 of it); the embedding and the host-computed layers take it from here."""
+        if starts is None:
+            self._key_starts = None
+            if self.ctx is not None:
+                N.check(self.ctx.lib.lia_ctx_set_key_starts(self.ctx.handle, None, 0), "lia_ctx_set_key_starts")
+            return
+        host = np.ascontiguousarray(np.asarray(starts, dtype=np.int32))
+        self._key_starts = (host, None, None)
+        if self.ctx is not None:
+            self._upload_key_starts()
+
+    def _upload_key_starts(self):
+        host = self._key_starts[0]
+        N.check(self.ctx.lib.lia_ctx_set_key_starts(self.ctx.handle, ctypes.c_void_p(host.ctypes.data), host.shape[0]),
+                "lia_ctx_set_key_starts")
+        self._key_starts = (host, torch.from_numpy(host).to("cuda"), self.ctx.handle)
+
+    def _key_starts_for(self, B):
+        """(host int32 [B], device int32 [B]) of the current generation, or None.  Called behind _place, which may have created
+        a new library context (a larger workspace): the table is uploaded to the context that serves this forward."""
+        ks = getattr(self, "_key_starts", None)
+        if ks is None:
+            return None
+        if ks[2] is None or ks[2] != self.ctx.handle:
+            self._upload_key_starts()
+            ks = self._key_starts
+        if ks[0].shape[0] != B:
+            raise ValueError(f"the key-start table has {ks[0].shape[0]} rows, the forward {B}")
+        return ks
 
     def _validate(self, input_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch):
         """shapes and flags of one forward -> the step record; raises on the combinations the path does not have"""
@@ -1108,9 +1150,16 @@ class OffloadScheduler:
         kv = kv_state.kv[idx]
         import time
         t0 = time.time()
-        N.check(lib.lia_host_layer_forward(ctypes.byref(m.desc), ctypes.byref(w), ctypes.c_void_p(hx), ctypes.c_void_p(hy),
-                                           ctypes.c_void_p(kv.k), ctypes.c_void_p(kv.v), kv.smax, kv.batch, B, T, pos0, 0, threads),
-                "lia_host_layer_forward")
+        ks = self._key_starts_for(B)
+        if ks is None:
+            N.check(lib.lia_host_layer_forward(ctypes.byref(m.desc), ctypes.byref(w), ctypes.c_void_p(hx), ctypes.c_void_p(hy),
+                                               ctypes.c_void_p(kv.k), ctypes.c_void_p(kv.v), kv.smax, kv.batch, B, T, pos0, 0, threads),
+                    "lia_host_layer_forward")
+        else:
+            N.check(lib.lia_host_layer_forward_padded(ctypes.byref(m.desc), ctypes.byref(w), ctypes.c_void_p(hx), ctypes.c_void_p(hy),
+                                                      ctypes.c_void_p(kv.k), ctypes.c_void_p(kv.v), kv.smax, kv.batch, B, T, pos0, 0,
+                                                      threads, ctypes.c_void_p(ks[0].ctypes.data)),
+                    "lia_host_layer_forward_padded")
         self.host_layer_time["ms"] += 1e3 * (time.time() - t0)
         self.host_layer_time["calls"] += 1
         N.check(lib.lia_blit(ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(hy), nbytes, ctypes.c_void_p(ctx.stream)), "lia_blit")
@@ -1134,6 +1183,7 @@ class OffloadScheduler:
         from . import hostinfo
         threads = self._host_team(self.dp.world if self.dp else 1).threads
         host = list(range(n_gpu, sh.layers))
+        ks = self._key_starts_for(B)
         import time
         t_host0 = time.time()
         raw_ptr = {}
@@ -1159,8 +1209,13 @@ class OffloadScheduler:
                 vt = (ctypes.c_void_p * n)(*[kv_state.kv[i].v for i in host])
                 tab = self._host_tables = (key, wt, kt, vt)
             kv0 = kv_state.kv[host[0]]
-            where = lib.lia_host_layers_forward(ctypes.byref(m.desc), len(host), tab[1], ctypes.c_void_p(hx), ctypes.c_void_p(hy), tab[2], tab[3],
-                                                kv0.smax, kv0.batch, B, T, pos0, 0, threads)
+            if ks is None:
+                where = lib.lia_host_layers_forward(ctypes.byref(m.desc), len(host), tab[1], ctypes.c_void_p(hx), ctypes.c_void_p(hy), tab[2],
+                                                    tab[3], kv0.smax, kv0.batch, B, T, pos0, 0, threads)
+            else:
+                where = lib.lia_host_layers_forward_padded(ctypes.byref(m.desc), len(host), tab[1], ctypes.c_void_p(hx), ctypes.c_void_p(hy),
+                                                           tab[2], tab[3], kv0.smax, kv0.batch, B, T, pos0, 0, threads,
+                                                           ctypes.c_void_p(ks[0].ctypes.data))
             N.check(min(where, 0), "lia_host_layers_forward")
             if where == 1:
                 hx, hy = hy, hx
@@ -1168,9 +1223,15 @@ class OffloadScheduler:
             for idx in host:
                 w = ops.weight_ptr_array(raw_ptr[idx], m.offsets)
                 kv = kv_state.kv[idx]
-                N.check(lib.lia_host_layer_forward(ctypes.byref(m.desc), ctypes.byref(w), ctypes.c_void_p(hx), ctypes.c_void_p(hy),
-                                                   ctypes.c_void_p(kv.k), ctypes.c_void_p(kv.v), kv.smax, kv.batch, B, T, pos0, 0, threads),
-                        "lia_host_layer_forward")
+                if ks is None:
+                    N.check(lib.lia_host_layer_forward(ctypes.byref(m.desc), ctypes.byref(w), ctypes.c_void_p(hx), ctypes.c_void_p(hy),
+                                                       ctypes.c_void_p(kv.k), ctypes.c_void_p(kv.v), kv.smax, kv.batch, B, T, pos0, 0,
+                                                       threads), "lia_host_layer_forward")
+                else:
+                    N.check(lib.lia_host_layer_forward_padded(ctypes.byref(m.desc), ctypes.byref(w), ctypes.c_void_p(hx),
+                                                              ctypes.c_void_p(hy), ctypes.c_void_p(kv.k), ctypes.c_void_p(kv.v), kv.smax,
+                                                              kv.batch, B, T, pos0, 0, threads, ctypes.c_void_p(ks[0].ctypes.data)),
+                            "lia_host_layer_forward_padded")
                 hx, hy = hy, hx
         self.host_layer_time["ms"] += 1e3 * (time.time() - t_host0)
         self.host_layer_time["calls"] += len(host)
