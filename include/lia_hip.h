@@ -197,6 +197,18 @@ int lia_lm_head(lia_ctx* ctx, const lia_bf16* hidden, int B, int T, int H, const
                 const lia_bf16* emb, int vocab, float eps, int suppress_token, lia_bf16* logits, int64_t* next_ids,
                 void* stream);
 
+/* sampled decoding: HF's MinNewTokensLength -> Temperature -> TopK -> TopP -> multinomial, one draw per row of logits [B, ld]
+ * (bf16, as lia_lm_head / lia_llama_lm_head write them; DESIGN.md "Sampled decoding").  Per row: s = fp32(l) / temperature
+ * (s[suppress_token] = -inf); top_k > 0 and < vocab keeps every token with s >= the k-th largest s; top_p < 1 keeps, of those,
+ * every token whose tokens of strictly larger s hold < top_p of the kept mass exp(s - max s); the result is the smallest kept id
+ * whose running mass in id order exceeds uniforms[row] * the kept mass (the last kept id if rounding leaves none).  A token with
+ * s = -inf is never kept.  uniforms: device, B floats in [0, 1); next_ids: device, B; stats: device, B x 4 floats or NULL --
+ * per row t_k (-inf with top-k off), the top-p boundary s (-inf with top-p off), the kept count and the kept mass.
+ * LIA_ERR_INVALID, by name: temperature <= 0 or not finite, top_k < 0, top_p not in (0, 1], B <= 0, vocab <= 0 or > 2^21,
+ * ld < vocab, suppress_token not -1 or in [0, vocab), a NULL logits / uniforms / next_ids. */
+int lia_sample(lia_ctx* ctx, const lia_bf16* logits, long ld, int B, int vocab, float temperature, int top_k, float top_p,
+               int suppress_token, const float* uniforms, int64_t* next_ids, float* stats, void* stream);
+
 /* ---- Llama-family layer (BASELINE.json config 4; build-defined: the reference's LlamaDecoderLayer_forward,
  * decoder.py:121-169, has no policy plumbing -- SURVEY.md quirk 3).  Arithmetic = HF transformers' eager bf16 Llama.
  * weights[9]: 0 input_norm.w  1 q.w [h*d,H]  2 k.w [kvh*d,H]  3 v.w  4 o.w [H,h*d]  5 post_norm.w  6 gate.w [F,H]

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <chrono>
 #include <vector>
 
@@ -24,6 +25,8 @@ extern "C" void lia_layernorm_launch(const bf16_t* x, long ldx, const bf16_t* g,
 extern "C" void lia_embed_launch(const int64_t* ids, const bf16_t* tok, const bf16_t* pos, bf16_t* y, int B, int T,
                                  int past_len, int H, hipStream_t st);
 extern "C" void lia_argmax_launch(const bf16_t* logits, int64_t* out, int B, int vocab, int suppress, hipStream_t st);
+extern "C" void lia_sample_launch(const bf16_t* logits, long ld, int B, int vocab, float tau, int top_k, float top_p, int suppress,
+                                  const float* uniforms, int64_t* out, float* stats, hipStream_t st);
 extern "C" void lia_blit_launch(void* dst, const void* src, size_t bytes, hipStream_t st);
 extern "C" int lia_attn_prefill_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
                                        int B, int T, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
@@ -627,6 +630,27 @@ extern "C" int lia_lm_head(lia_ctx* ctx, const lia_bf16* hidden, int B, int T, i
   int rc = gemm_checked(ctx, lno, H, emb, B, vocab, H, ep, om, (float*)(ctx->ws + scratch), std::min(have, gemm_need), 0, st);
   if (rc) return rc;
   lia_argmax_launch(logits, next_ids, B, vocab, suppress_token, st);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+// temperature -> top-k -> top-p -> one draw per row (lia_sample.hip).  Any B; the row is read a fixed number of times.
+#define LIA_SAMPLE_MAX_VOCAB (256 * 8192)   // lia_sample.hip keeps one running sum per 8192-token tile in LDS
+extern "C" int lia_sample(lia_ctx* ctx, const lia_bf16* logits, long ld, int B, int vocab, float temperature, int top_k, float top_p,
+                          int suppress_token, const float* uniforms, int64_t* next_ids, float* stats, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!logits || !uniforms || !next_ids) {
+    lia_set_error("lia_sample: NULL %s", !logits ? "logits" : !uniforms ? "uniforms" : "next_ids");
+    return LIA_ERR_INVALID;
+  }
+  if (B <= 0) { lia_set_error("lia_sample: B=%d must be >= 1", B); return LIA_ERR_INVALID; }
+  if (vocab <= 0 || vocab > LIA_SAMPLE_MAX_VOCAB) { lia_set_error("lia_sample: vocab=%d must be in [1, %d]", vocab, LIA_SAMPLE_MAX_VOCAB); return LIA_ERR_INVALID; }
+  if (ld < vocab) { lia_set_error("lia_sample: ld=%ld < vocab=%d", ld, vocab); return LIA_ERR_INVALID; }
+  if (!(temperature > 0.f) || !std::isfinite(temperature)) { lia_set_error("lia_sample: temperature=%g must be finite and > 0", (double)temperature); return LIA_ERR_INVALID; }
+  if (top_k < 0) { lia_set_error("lia_sample: top_k=%d must be >= 0 (0: off)", top_k); return LIA_ERR_INVALID; }
+  if (!(top_p > 0.f && top_p <= 1.f)) { lia_set_error("lia_sample: top_p=%g must be in (0, 1] (1: off)", (double)top_p); return LIA_ERR_INVALID; }
+  if (suppress_token < -1 || suppress_token >= vocab) { lia_set_error("lia_sample: suppress_token=%d must be -1 or in [0, vocab)", suppress_token); return LIA_ERR_INVALID; }
+  lia_sample_launch(logits, ld, B, vocab, temperature, top_k, top_p, suppress_token, uniforms, next_ids, stats, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return LIA_OK;
 }

@@ -1,0 +1,328 @@
+// Sampled decoding: temperature -> top-k -> top-p -> one draw per row, over the bf16 logits lm_head wrote ("Sampled
+// decoding").  One LIA_ROW_THREADS workgroup per row, in the shape of lia_argmax_kernel; nothing is sorted.
+//
+// tau > 0 makes s = fp32(l) / tau a non-decreasing function of l, and l is bf16, so a row's order is the order of a 16-bit key of
+// its logits (key_of: sign-magnitude -> offset binary) and every per-token quantity -- s, the weight exp(s - m) -- is a function of
+// the key.  The boundaries are found from histograms of keys, 4096 bins of the top 12 key bits then 16 bins of the low 4 inside the
+// boundary bin (12 + 4 rather than 8 + 8: the top byte of a bf16 is its sign and exponent, and a row's logits fill only a few
+// exponents -- the LDS atomics of 64 lanes would pile onto a handful of bins):
+//   pass A  max key (m = s of it) and, with top-k on, counts per top-12 bin -> the bin holding the k-th largest key
+//   pass B  (top-k) counts per low nibble inside that bin -> kappa_k, t_k = s(kappa_k)
+//   pass C  (top-p) mass per top-12 bin over K1, in 2^-40 fixed point (u64 LDS atomics: exact integer sums, the same in every run)
+//   pass D  (top-p) mass per low nibble inside the boundary bin -> kappa_p, v_p = s(kappa_p)
+//   pass E  tiles of 8 tokens per thread in token order: block prefix sums of the kept weights, one carry per tile; then the tile
+//           where the running sum passes u * W is walked again for the token.
+// Membership is a key comparison: K = {key >= kappa_lo(t)}, kappa_lo(t) the smallest key whose s is >= t (a 16-step bisection by
+// one thread).  That is s_i >= t exactly, also where two keys give the same s (-0 / +0, or an s that rounds to 0 or inf).  A token
+// whose s is -inf (the suppressed one) carries no mass and is never kept.  Logits are finite or +-inf, not NaN.
+#include "lia_common.h"
+
+#define SMP_TILE (LIA_ROW_THREADS * 8)   // tokens per pass-E tile: 8 consecutive tokens per thread
+#define SMP_MAX_TILES 256                // pass-E carries kept in LDS: vocab <= 256 * 8192 (lia_sample checks)
+#define SMP_KEY_NEG_INF 0x007F           // key_of(bf16 -inf); keys below it are negative NaNs
+#define SMP_KEY_POS_INF 0xFF80           // key_of(bf16 +inf)
+#define SMP_BINS 4096
+#define SMP_FIX 0x1p40f                  // fixed-point scale of the top-p masses (w <= 1, vocab <= 2^21: sums < 2^61)
+
+__device__ __forceinline__ int key_of(uint32_t h) { return (h & 0x8000u) ? (int)(~h & 0xFFFFu) : (int)(h | 0x8000u); }
+__device__ __forceinline__ float score_of_key(int k, float tau) {
+  const uint32_t h = (k & 0x8000) ? (uint32_t)(k & 0x7FFF) : (uint32_t)(~k & 0xFFFF);
+  return bf2f((bf16_t)h) / tau;                // the IEEE fp32 division of the contract
+}
+
+// keys of tokens i .. i + 7 (-1 past the end of the row); the suppressed token's key is that of -inf
+__device__ __forceinline__ void load_keys8(const bf16_t* __restrict__ row, int i, int vocab, bool vec, int suppress, int k[8]) {
+  if (vec && i < vocab) {            // vec: vocab % 8 == 0 and 16-byte aligned rows
+    const uint4 v = *(const uint4*)(row + i);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) k[e] = key_of((w[e >> 1] >> ((e & 1) * 16)) & 0xffffu);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) k[e] = i + e < vocab ? key_of(row[i + e]) : -1;
+  }
+  const unsigned d = (unsigned)(suppress - i);
+  if (d < 8u) k[d] = SMP_KEY_NEG_INF;
+}
+
+// smallest key in (-inf, +inf] whose score is >= t (keys above SMP_KEY_NEG_INF: a -inf score is never kept)
+__device__ int key_lower_bound(float t, float tau) {
+  int lo = SMP_KEY_NEG_INF + 1, hi = SMP_KEY_POS_INF + 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (score_of_key(mid, tau) >= t) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+// exclusive prefix sum over the workgroup in thread order; *total (if not NULL): the sum of all, the same bits in every thread.
+// red: LIA_ROW_WAVES T of LDS.
+template <typename T> __device__ __forceinline__ T block_excl_scan(T v, T* red, T* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  T x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  T ex = __shfl_up(x, 1, 64);
+  if (lane == 0) ex = 0;
+  if (lane == 63) red[w] = x;
+  __syncthreads();
+  T pre = 0, tot = 0;
+#pragma unroll
+  for (int i = 0; i < LIA_ROW_WAVES; ++i) {
+    const T r = red[i];
+    if (i < w) pre += r;
+    tot += r;
+  }
+  __syncthreads();
+  if (total) *total = tot;
+  return pre + ex;
+}
+
+// The bin b of h[0 .. SMP_BINS) (bins in descending key order from the top) with  above(b) < thr <= above(b) + h[b],
+// above(b) = the sum of the bins above b.  Thread t owns bins 4095 - 4t - j, j < 4.  Writes (bin, above) to *out_bin, *out_above.
+template <typename T> __device__ __forceinline__ void find_boundary_bin(const T* h, T thr, T* red, int* out_bin, T* out_above) {
+  const int t = threadIdx.x;
+  if (t == 0) { *out_bin = 0; *out_above = 0; }     // (no bin qualifies only for a row without mass: no token is kept then)
+  T v[4], s = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { v[j] = h[SMP_BINS - 1 - 4 * t - j]; s += v[j]; }
+  T above = block_excl_scan<T>(s, red, (T*)nullptr);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (above < thr && thr <= above + v[j]) { *out_bin = SMP_BINS - 1 - 4 * t - j; *out_above = above; }
+    above += v[j];
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(LIA_ROW_THREADS) void lia_sample_kernel(const bf16_t* __restrict__ logits, long ld, int vocab, int vec,
+                                                                     float tau, int top_k, float top_p, int suppress,
+                                                                     const float* __restrict__ uniforms, int64_t* __restrict__ out,
+                                                                     float* __restrict__ stats) {
+  __shared__ uint64_t hist[SMP_BINS];            // pass A: uint32 counts (the first half), pass C: uint64 masses
+  __shared__ uint64_t nib[16];                   // passes B / D: the 16 low-nibble bins of the boundary bin
+  __shared__ uint64_t red64[LIA_ROW_WAVES];
+  __shared__ uint32_t red32[LIA_ROW_WAVES];
+  __shared__ float redf[LIA_ROW_WAVES];
+  __shared__ float carry_of[SMP_MAX_TILES + 1];  // pass E: running sum before tile j
+  __shared__ int sh_bin, sh_key[2], sh_pick;
+  __shared__ uint32_t sh_above32;
+  __shared__ uint64_t sh_above64;
+  uint32_t* cnt = (uint32_t*)hist;
+
+  const int tid = threadIdx.x;
+  const bf16_t* row = logits + (long)blockIdx.x * ld;
+  const bool topk_on = top_k > 0 && top_k < vocab;
+  const bool topp_on = top_p < 1.0f;
+
+  // ---- pass A: the maximum key; with top-k on, counts per top-12 bin ----
+  if (topk_on)
+    for (int b = tid; b < SMP_BINS / 2; b += LIA_ROW_THREADS) hist[b] = 0;
+  __syncthreads();
+  int kmax = -1;
+  for (int i = tid * 8; i < vocab; i += SMP_TILE) {
+    int k[8];
+    load_keys8(row, i, vocab, vec, suppress, k);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      kmax = max(kmax, k[e]);
+      if (topk_on && k[e] >= 0) atomicAdd(&cnt[k[e] >> 4], 1u);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, __shfl_xor(kmax, o, 64));
+  if ((tid & 63) == 0) red32[tid >> 6] = (uint32_t)kmax;
+  __syncthreads();
+  kmax = (int)red32[0];
+#pragma unroll
+  for (int w = 1; w < LIA_ROW_WAVES; ++w) kmax = max(kmax, (int)red32[w]);
+  const float m = score_of_key(kmax, tau);
+  __syncthreads();                   // (red32 is reused below)
+
+  // ---- pass B: the k-th largest key ----
+  int kap1 = SMP_KEY_NEG_INF + 1;    // K1 = {key >= kap1}
+  float t_k = -INFINITY;
+  if (topk_on) {
+    find_boundary_bin<uint32_t>(cnt, (uint32_t)top_k, red32, &sh_bin, &sh_above32);
+    const int bk = sh_bin;
+    if (tid < 16) nib[tid] = 0;
+    __syncthreads();
+    for (int i = tid * 8; i < vocab; i += SMP_TILE) {
+      int k[8];
+      load_keys8(row, i, vocab, vec, suppress, k);
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (k[e] >= 0 && (k[e] >> 4) == bk) atomicAdd((uint32_t*)&nib[k[e] & 15], 1u);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      uint32_t above = sh_above32;
+      int l = 15;
+      for (; l > 0; --l) {
+        const uint32_t c = *(const uint32_t*)&nib[l];
+        if (above + c >= (uint32_t)top_k) break;
+        above += c;
+      }
+      const int kk = (bk << 4) | l;
+      sh_key[0] = key_lower_bound(score_of_key(kk, tau), tau);
+      sh_key[1] = kk;
+    }
+    __syncthreads();
+    kap1 = sh_key[0];
+    t_k = score_of_key(sh_key[1], tau);
+  }
+
+  // ---- passes C and D: the top-p boundary over K1 ----
+  int kap2 = kap1;                   // K2 = {key >= kap2}
+  float v_p = -INFINITY;
+  if (topp_on) {
+    for (int b = tid; b < SMP_BINS; b += LIA_ROW_THREADS) hist[b] = 0;
+    if (tid < 16) nib[tid] = 0;
+    __syncthreads();
+    for (int i = tid * 8; i < vocab; i += SMP_TILE) {
+      int k[8];
+      load_keys8(row, i, vocab, vec, suppress, k);
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (k[e] >= kap1) {
+          const uint64_t f = __float2ull_rn(expf(score_of_key(k[e], tau) - m) * SMP_FIX);
+          if (f) atomicAdd((unsigned long long*)&hist[k[e] >> 4], (unsigned long long)f);
+        }
+    }
+    __syncthreads();
+    // W = the sum of every bin (the scan's total); the threshold p * W rounded up, so that A < p W <=> A < X for integers A
+    uint64_t s4 = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s4 += hist[4 * tid + j];
+    uint64_t W;
+    (void)block_excl_scan<uint64_t>(s4, red64, &W);
+    uint64_t X = (uint64_t)ceil((double)top_p * (double)W);
+    if (X < 1) X = 1;
+    find_boundary_bin<uint64_t>(hist, X, red64, &sh_bin, &sh_above64);
+    const int bp = sh_bin;
+    for (int i = tid * 8; i < vocab; i += SMP_TILE) {
+      int k[8];
+      load_keys8(row, i, vocab, vec, suppress, k);
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (k[e] >= kap1 && (k[e] >> 4) == bp) {
+          const uint64_t f = __float2ull_rn(expf(score_of_key(k[e], tau) - m) * SMP_FIX);
+          if (f) atomicAdd((unsigned long long*)&nib[k[e] & 15], (unsigned long long)f);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      uint64_t above = sh_above64;
+      int l = 15;
+      for (; l > 0; --l) {
+        if (above + nib[l] >= X) break;
+        above += nib[l];
+      }
+      const int kp = (bp << 4) | l;
+      sh_key[0] = key_lower_bound(score_of_key(kp, tau), tau);
+      sh_key[1] = kp;
+    }
+    __syncthreads();
+    kap2 = max(kap1, sh_key[0]);
+    v_p = score_of_key(sh_key[1], tau);
+  }
+
+  // ---- pass E: running sums of the kept weights in token order, one carry per tile ----
+  const int ntiles = (vocab + SMP_TILE - 1) / SMP_TILE;
+  float carry = 0.f;
+  int nkept = 0, last = -1;
+  for (int j = 0; j < ntiles; ++j) {
+    const int i = j * SMP_TILE + tid * 8;
+    int k[8];
+    load_keys8(row, i, vocab, vec, suppress, k);
+    float r = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (k[e] >= kap2) { r += expf(score_of_key(k[e], tau) - m); ++nkept; last = i + e; }
+    const float ex = block_excl_scan<float>(r, redf, (float*)nullptr);
+    if (tid == LIA_ROW_THREADS - 1) {
+      carry_of[j] = carry;
+      redf[0] = ex + r;               // the tile's total as the walk below computes it at the tile's last token
+    }
+    __syncthreads();
+    carry = carry + redf[0];
+    __syncthreads();
+  }
+  if (tid == 0) carry_of[ntiles] = carry;
+  // |K2| and the last kept token
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    nkept += __shfl_xor(nkept, o, 64);
+    last = max(last, __shfl_xor(last, o, 64));
+  }
+  if ((tid & 63) == 0) { red32[tid >> 6] = (uint32_t)nkept; red64[tid >> 6] = (uint64_t)(int64_t)last; }
+  if (tid == 0) sh_pick = 0x7fffffff;
+  __syncthreads();
+  nkept = 0;
+#pragma unroll
+  for (int w = 0; w < LIA_ROW_WAVES; ++w) { nkept += (int)red32[w]; last = max(last, (int)(int64_t)red64[w]); }
+  const float W2 = carry;
+  const float thr = uniforms[blockIdx.x] * W2;
+  int jc = -1;                        // the first tile whose running sum passes thr
+  for (int j = 0; j < ntiles; ++j)
+    if (carry_of[j + 1] > thr) { jc = j; break; }
+  if (jc >= 0) {
+    // walk tile jc again: the same sums in the same order, then the first kept token whose running sum passes thr
+    const int i = jc * SMP_TILE + tid * 8;
+    int k[8];
+    load_keys8(row, i, vocab, vec, suppress, k);
+    float wv[8], r = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      wv[e] = k[e] >= kap2 ? expf(score_of_key(k[e], tau) - m) : 0.f;
+      r += wv[e];
+    }
+    const float ex = block_excl_scan<float>(r, redf, (float*)nullptr);
+    const float c0 = carry_of[jc];
+    float q = 0.f;
+    int pick = 0x7fffffff, lastc = -1;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      q += wv[e];
+      if (k[e] >= kap2) {
+        lastc = i + e;
+        if (pick == 0x7fffffff && c0 + (ex + q) > thr) pick = i + e;
+      }
+    }
+    if (pick != 0x7fffffff) atomicMin(&sh_pick, pick);
+    // (the tile's total passed thr, so a kept token of it does; should rounding say otherwise, its last kept token)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lastc = max(lastc, __shfl_xor(lastc, o, 64));
+    if ((tid & 63) == 0) red32[tid >> 6] = (uint32_t)lastc;
+    __syncthreads();
+    if (tid == 0 && sh_pick == 0x7fffffff) {
+      int lc = -1;
+      for (int w = 0; w < LIA_ROW_WAVES; ++w) lc = max(lc, (int)red32[w]);
+      sh_pick = lc;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    int pick = jc >= 0 ? sh_pick : last;
+    if (pick < 0 || pick >= vocab) pick = last >= 0 ? last : 0;
+    out[blockIdx.x] = pick;
+    if (stats) {
+      float* so = stats + 4 * (long)blockIdx.x;
+      so[0] = t_k;
+      so[1] = v_p;
+      so[2] = (float)nkept;
+      so[3] = W2;
+    }
+  }
+}
+
+extern "C" void lia_sample_launch(const bf16_t* logits, long ld, int B, int vocab, float tau, int top_k, float top_p, int suppress,
+                                  const float* uniforms, int64_t* out, float* stats, hipStream_t st) {
+  if (B <= 0) return;
+  const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
+  hipLaunchKernelGGL(lia_sample_kernel, dim3(B), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, tau, top_k, top_p, suppress,
+                     uniforms, out, stats);
+}

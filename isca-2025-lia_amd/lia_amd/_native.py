@@ -76,6 +76,8 @@ SIGNATURES = {
     "lia_embed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "lia_lm_head": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float,
                             c_int, c_void_p, c_void_p, c_void_p]),
+    "lia_sample": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_float, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                           c_void_p]),
     "lia_host_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                    c_int, c_int, c_int, c_int, c_int]),
     "lia_llama_pack_offsets": (c_int, [ctypes.POINTER(LlamaDesc), ctypes.POINTER(c_size_t * 9), ctypes.POINTER(c_size_t)]),

@@ -42,6 +42,7 @@ class DataParallelGroup:
         self.dist, self.rank, self.world, self.local_rank = dist, rank, world, local_rank
         self.chunk_bytes = chunk_bytes or int(os.environ.get("LIA_DP_CHUNK_BYTES", DEFAULT_CHUNK))
         self.root = 0
+        self.n_rows = None         # the global batch of the last shard(): generate(do_sample=True) draws U for all of its rows
         # how a streamed layer reaches the G ranks: "broadcast" (BASELINE.json: rank 0 reads it over its link, one RCCL
         # broadcast) or "allgather" (SURVEY.md section 8e alternative: every rank keeps and reads 1/G of the wire bytes over
         # ITS OWN host link, one all-gather over xGMI puts the layer together -- G times the host-link rate)
@@ -56,6 +57,7 @@ class DataParallelGroup:
     def shard(self, input_ids, attention_mask=None):
         """this rank's rows of input_ids -- and, given an attention_mask ([B, T] like input_ids), (ids, the same rows of the mask)"""
         lo, hi = shard_rows(input_ids.shape[0], self.rank, self.world)
+        self.n_rows = input_ids.shape[0]
         if attention_mask is None:
             return input_ids[lo:hi]
         if attention_mask.shape[0] != input_ids.shape[0]:

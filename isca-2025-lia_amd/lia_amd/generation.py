@@ -18,6 +18,7 @@ import time
 import numpy as np
 import torch
 
+from . import sampling
 from .scheduler import KVState, OffloadScheduler
 
 LIA_KWARGS = ("prefill_policy", "decoding_policy", "no_overlap", "pin_weight", "gpu_percentage", "num_minibatch",
@@ -55,12 +56,23 @@ def _scheduler_of(model):
 
 
 def generate(model, input_ids, max_new_tokens=None, min_new_tokens=None, do_sample=False, num_beams=1,
-             eos_token_id=2, pad_token_id=1, token_latency=False, return_logits=False, **model_kwargs):
-    if do_sample or num_beams != 1:
-        raise ValueError("only greedy search carries the LIA kwargs (run.py --greedy; beam/sample paths are not plumbed "
-                         "in the reference either)")
+             eos_token_id=2, pad_token_id=1, token_latency=False, return_logits=False, temperature=None, top_k=None, top_p=None,
+             sample_seed=None, **model_kwargs):
+    """do_sample=True: sampled decoding (sampling.py) with HF's temperature / top_k / top_p (defaults 1.0 / 50 / 1.0); U comes from a
+    private generator seeded with sample_seed, else from the default CUDA generator.  do_sample=False ignores the three."""
+    if num_beams != 1:
+        raise ValueError(f"num_beams={num_beams}: beam search is not supported (greedy search and sampling carry the LIA kwargs; "
+                         "beam paths are not plumbed in the reference either)")
     if max_new_tokens is None or max_new_tokens < 1:
         raise ValueError("max_new_tokens must be >= 1")
+    sample = None
+    if do_sample:
+        sample = sampling.check_settings(temperature, top_k, top_p)
+        sampling.check_unsupported(model_kwargs)
+        if sample_seed is not None and (isinstance(sample_seed, bool) or not isinstance(sample_seed, int)):
+            raise ValueError(f"sample_seed must be an int or None, got {sample_seed!r}")
+        for k in sampling.UNSUPPORTED:
+            model_kwargs.pop(k, None)
     # unknown kwargs are NOT rejected: the reference disables that check so its flags reach forward()
     # (lia/generation_utils.py:1166-1170)
     lia = {k: model_kwargs.pop(k, None) for k in LIA_KWARGS}
@@ -85,6 +97,8 @@ def generate(model, input_ids, max_new_tokens=None, min_new_tokens=None, do_samp
         raise ValueError("attention_mask with padding (zeros) is not supported for Llama-family models: their RoPE positions "
                          "are not per row yet; pass equal-length prompts")
     sched = _scheduler_of(model)
+    if sample is not None and ids.dim() == 2:
+        hooks["sampler"] = _sampler(sched, ids.shape[0], max_new_tokens, sample, sample_seed)
     if starts is None:
         return _greedy_search(model, ids, max_new_tokens, min_new, eos_token_id, pad_token_id, token_latency,
                               return_logits, lia, **hooks)
@@ -98,8 +112,32 @@ def generate(model, input_ids, max_new_tokens=None, min_new_tokens=None, do_samp
         sched.set_key_starts(None)
 
 
+def _sampler(sched, B, max_new_tokens, settings, sample_seed):
+    """the generation's sampling.Sampler: U [max_new_tokens, B_global] drawn once, this process's columns of it.  Under data
+    parallelism (the scheduler's DataParallelGroup, whose shard() recorded the global row count) every rank draws the same U --
+    from sample_seed, else from a seed the root broadcasts -- and keeps the columns shard_rows gives it."""
+    dpg = getattr(sched, "dp", None)
+    n_rows = getattr(dpg, "n_rows", None) if dpg is not None else None
+    if n_rows is None:
+        lo, hi, n_rows = 0, B, B
+    else:
+        from .dp import shard_rows
+        lo, hi = shard_rows(n_rows, dpg.rank, dpg.world)
+        if hi - lo != B:
+            raise ValueError(f"rank {dpg.rank} holds rows {lo}..{hi} of {n_rows} (DataParallelGroup.shard), generate() got {B}")
+        if sample_seed is None:
+            sample_seed = sampling.shared_seed(dpg)
+    U = sampling.draw_uniforms(max_new_tokens, n_rows, sample_seed, device=sampling.DEVICE)
+    U = U[:, lo:hi].contiguous()
+    if U.is_cuda:
+        torch.cuda.current_stream().synchronize()      # the library's compute stream reads U
+    return sampling.Sampler(*settings, U)
+
+
 def _greedy_search(model, input_ids, max_new_tokens, min_new_tokens, eos_token_id, pad_token_id, token_latency,
-                   return_logits, lia, step_hook=None, max_steps=None):
+                   return_logits, lia, step_hook=None, max_steps=None, sampler=None):
+    """the greedy loop of greedy_search.py; with a sampler, the next ids of every step are its draw (sampled decoding) and the
+    EOS / pad bookkeeping is the same"""
     sched = _scheduler_of(model)
     ids = torch.as_tensor(input_ids, dtype=torch.int64).cpu()
     if ids.dim() != 2:
@@ -143,7 +181,10 @@ def _greedy_search(model, input_ids, max_new_tokens, min_new_tokens, eos_token_i
         tic = time.time()
         # EOS is suppressed while fewer than min_new_tokens were generated (HF MinNewTokensLengthLogitsProcessor)
         suppress = eos_token_id if (eos_token_id is not None and step < min_new_tokens) else -1
-        logits, nxt = sched.forward(cur, kv, max_new_tokens=max_new_tokens, suppress_token=suppress, **lia)
+        if sampler is None:
+            logits, nxt = sched.forward(cur, kv, max_new_tokens=max_new_tokens, suppress_token=suppress, **lia)
+        else:
+            logits, nxt = sched.forward(cur, kv, max_new_tokens=max_new_tokens, suppress_token=suppress, sampler=sampler.at(step), **lia)
         next_tokens = nxt.cpu()
         same_as_device = eos_token_id is None or all_unfinished        # no row was replaced by the pad token below
         if eos_token_id is not None:

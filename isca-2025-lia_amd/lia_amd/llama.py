@@ -221,7 +221,8 @@ class LlamaScheduler:
         return (ctypes.c_void_p * 9)(*[base + o for o in self.model.offsets])
 
     def forward(self, input_ids, kv_state, gpu_percentage=100, num_minibatch=1, pin_weight=True, enable_cxl=False,
-                suppress_token=-1, **_ignored):
+                suppress_token=-1, sampler=None, **_ignored):
+        """sampler (sampling.Sampler, generate(do_sample=True)): the returned ids are its draw from the logits instead of their argmax"""
         m, sh = self.model, self.model.shape
         lib = N.lib()
         B, T = input_ids.shape
@@ -300,6 +301,8 @@ class LlamaScheduler:
         N.check(lib.lia_llama_lm_head(ctx.handle, ctypes.c_void_p(x_lm.data_ptr()), B, T_lm, sh.hidden, ctypes.c_void_p(m.final_norm_w.data_ptr()),
                                       ctypes.c_void_p(m.lm_head.data_ptr()), sh.vocab, sh.rms_eps, suppress_token,
                                       ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(nxt_ids.data_ptr()), st), "lia_llama_lm_head")
+        if sampler is not None:
+            nxt_ids = sampler(ctx, logits, suppress_token)
         ctx.synchronize()
         kv_state.len = pos0 + T
         return logits, nxt_ids

@@ -151,6 +151,26 @@ class Context:
                                          _ptr(logits[b0:b0 + nb]), _ptr(nxt[b0:b0 + nb]), self._st(stream)), "lia_lm_head")
         return logits, nxt
 
+    def sample(self, logits, temperature, top_k, top_p, uniforms, suppress_token=-1, stats=None, stream=None):
+        """lia_sample: temperature -> top-k -> top-p -> one draw per row of logits [B, vocab] (bf16, rows may be strided) with
+        uniforms [B] (float32, in [0, 1)).  Returns the ids (int64 [B]); stats (float32 [B, 4], optional) receives per row t_k, the
+        top-p boundary, the kept count and the kept mass.  Any B: rows are independent."""
+        if not logits.is_cuda or logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+            raise ValueError(f"logits: expected a [B, vocab] bf16 CUDA tensor with unit column stride, got {logits.dtype} {logits.device} "
+                             f"shape {tuple(logits.shape)} strides {logits.stride()}")
+        B, vocab = logits.shape
+        _chk(uniforms, torch.float32)
+        if uniforms.numel() != B:
+            raise ValueError(f"uniforms has {uniforms.numel()} entries, logits {B} rows")
+        if stats is not None:
+            _chk(stats, torch.float32)
+            if tuple(stats.shape) != (B, 4):
+                raise ValueError(f"stats must be [{B}, 4], got {tuple(stats.shape)}")
+        nxt = torch.empty((B,), dtype=torch.int64, device=logits.device)
+        N.check(self.lib.lia_sample(self.handle, _ptr(logits), logits.stride(0), B, vocab, float(temperature), int(top_k), float(top_p),
+                                    int(suppress_token), _ptr(uniforms), _ptr(nxt), _ptr(stats), self._st(stream)), "lia_sample")
+        return nxt
+
     # ---- the operator boundary ------------------------------------------------------------------
     def layer_forward(self, desc, policy, weight_ptrs, x, y, kv, B, T, pos0, b0=0, stream=None):
         """weight_ptrs: (c_void_p * 16) of device pointers; kv: _native.KV.  x, y: [B,T,H] device."""

@@ -71,6 +71,12 @@ def build_parser():
                         "bytes / copy-engine time over the timed iterations, the library's per-launch brackets of the FIRST (warm-up) "
                         "iteration, the host-memory peak, the planner's pick for the same line; a run the box cannot hold (MemoryError) "
                         "is recorded with its reason instead of a traceback")
+    p.add_argument("--do-sample", action="store_true",
+                   help="sampled decoding (temperature -> top-k -> top-p -> multinomial, the lia_sample kernel) instead of greedy")
+    p.add_argument("--temperature", default=0.9, type=float, help="with --do-sample (the reference harness passes 0.9)")
+    p.add_argument("--top-k", default=50, type=int, help="with --do-sample; 0: off")
+    p.add_argument("--top-p", default=1.0, type=float, help="with --do-sample; 1: off")
+    p.add_argument("--sample-seed", default=0, type=int, help="with --do-sample: the seed of the generation's uniforms")
     p.add_argument("--seed", default=0, type=int)
     p.add_argument("--init", default="normal", choices=["normal", "uniform01", "trained-like"],
                    help="uniform01 = the reference's dummy-weight recipe (utils/opt-weight-gen.py:61-62)")
@@ -408,6 +414,16 @@ def plan_beside(args):
         return {"error": f"no placement fits: {e}"}
 
 
+SAMPLE_FLAGS = ("do_sample", "temperature", "top_k", "top_p", "sample_seed")
+
+
+def sampling_kwargs(args):
+    """generate()'s sampling kwargs of the command line: none without --do-sample"""
+    if not args.do_sample:
+        return {}
+    return dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, sample_seed=args.sample_seed)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if not args.result_json:
@@ -415,7 +431,10 @@ def main(argv=None):
     import json
     import resource
     from . import hostinfo
-    rec = {"argv": list(argv) if argv is not None else None, "flags": {k: v for k, v in vars(args).items() if k != "result_json"}}
+    rec = {"argv": list(argv) if argv is not None else None,
+           "flags": {k: v for k, v in vars(args).items() if k != "result_json" and (args.do_sample or k not in SAMPLE_FLAGS)}}
+    if args.do_sample:
+        rec["sampling"] = {k: getattr(args, k) for k in SAMPLE_FLAGS}
     t0 = time.time()
     mem0 = hostinfo.cgroup_memory()["current"]
     rec["_mem_samples"] = []
@@ -494,6 +513,7 @@ def _main(args, rec=None):
                            token_latency=args.token_latency, prefill_policy=args.prefill_policy,
                            decoding_policy=args.decoding_policy, no_overlap=args.no_overlap, pin_weight=args.pin_weight,
                            gpu_percentage=args.gpu_percentage, num_minibatch=args.num_minibatch, enable_cxl=args.enable_cxl)
+    generate_kwargs.update(sampling_kwargs(args))
     if args.cpu_layers:
         generate_kwargs["cpu_layers"] = args.cpu_layers
         if args.cpu_layers < 0 and args.cpu_layers_start is not None:

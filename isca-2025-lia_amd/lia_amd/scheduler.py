@@ -731,12 +731,13 @@ class OffloadScheduler:
     # the cooperative controller's sample).  Each phase reads and extends the step record `s`; none reaches back.
     def forward(self, input_ids, kv_state, prefill_policy=1, decoding_policy=1, no_overlap=False, pin_weight=False,
                 gpu_percentage=0, num_minibatch=1, enable_cxl=False, max_new_tokens=None, suppress_token=-1, cpu_layers=0,
-                cpu_layers_start=None):
+                cpu_layers_start=None, sampler=None):
         """cpu_layers (build-defined): with decoding policy 2, that many of the streamed layers run
         their decode step entirely on the host cores (policy 1, weights read in place) instead of crossing the link --
         the cooperative split of the reference taken per layer.  Prefill is unaffected (policy 0 for every layer).
         cpu_layers=-1: the count is chosen ONLINE (CoopController) from the measured decode steps, starting at cpu_layers_start
-        (default: planner.plan_cpu_layers for this shape and box defaults)."""
+        (default: planner.plan_cpu_layers for this shape and box defaults).
+        sampler (sampling.Sampler, generate(do_sample=True)): the returned ids are its draw from the logits instead of their argmax."""
         s = self._validate(input_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch)
         self._place(s, kv_state, pin_weight, enable_cxl, max_new_tokens, cpu_layers, cpu_layers_start)
         m, sh, ctx = self.model, self.model.shape, self.ctx
@@ -755,11 +756,15 @@ class OffloadScheduler:
             self._await_kv(kv_state)
             hidden = self._host_layers(s.x, kv_state, s.n_gpu, s.B, s.T, s.pos0)  # resident prefix on the GPU, the rest on the CPU
             logits, nxt = ctx.lm_head(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, sh.ln_eps, suppress_token)
+            if sampler is not None:
+                nxt = sampler(ctx, logits, suppress_token)
             ctx.synchronize()
             kv_state.len = s.pos0 + s.T
             return logits, nxt
         hidden = self._run_layers(s, kv_state)
         logits, nxt = ctx.lm_head(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, sh.ln_eps, suppress_token)
+        if sampler is not None:
+            nxt = sampler(ctx, logits, suppress_token)
         self._deliver(s, kv_state)
         return logits, nxt
 
