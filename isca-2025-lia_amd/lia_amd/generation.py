@@ -19,7 +19,10 @@ import numpy as np
 import torch
 
 from . import sampling
-from .scheduler import KVState, OffloadScheduler
+from .scheduler import OffloadScheduler
+
+# Two imports stay inside the functions that need them: `.dp` pulls in torch.distributed, which a single-process generation
+# never needs; `.llama` is looked up at call time because the CPU tests of the greedy loop replace llama.LlamaKVState.
 
 LIA_KWARGS = ("prefill_policy", "decoding_policy", "no_overlap", "pin_weight", "gpu_percentage", "num_minibatch",
               "enable_cxl")
@@ -145,27 +148,11 @@ def _greedy_search(model, input_ids, max_new_tokens, min_new_tokens, eos_token_i
     B, T = ids.shape
     if T + max_new_tokens > model.shape.max_pos:
         raise ValueError(f"prompt {T} + max_new_tokens {max_new_tokens} exceeds max positions {model.shape.max_pos}")
-    L = model.shape.layers
-    n_gpu = int(L * lia["gpu_percentage"] / 100)
     if getattr(model, "family", "opt") == "llama":
         from .llama import LlamaKVState
         kv = LlamaKVState(model, B, T + max_new_tokens)
     else:
-        # caches sized [T+new, B, h, d] like modeling_opt.py:1277-1278; in HBM for every layer when both policies are 3
-        on_dev = lia["prefill_policy"] == 3 and lia["decoding_policy"] == 3
-        host_layers, dual_layers = (), ()
-        if on_dev and lia.get("cpu_layers", 0) > 0:
-            host_layers = OffloadScheduler.cpu_layer_set(n_gpu, L, lia["cpu_layers"])
-        elif on_dev and lia.get("cpu_layers", 0) < 0 and getattr(sched, "dp", None) is None and n_gpu < L - 1:
-            # online count: every CANDIDATE host layer has a cache buffer on both sides; the cache lives where the layer is computed
-            coop = sched._coop_controller(n_gpu, L, B, T, max_new_tokens, lia["gpu_percentage"], 3, lia.get("cpu_layers_start"))
-            # (before the caches are pinned: a candidate costs its raw weight copy AND its host cache buffer; while copies are
-            # missing, the pooled blocks of an earlier generation with the caches on the host go back first -- with them in HBM
-            # only the candidates need one)
-            sched._fit_host_candidates(coop, bool(lia.get("enable_cxl") and lia.get("pin_weight")),
-                                       extra_per_layer=2 * (T + max_new_tokens) * B * model.shape.hidden * 2, trim_pool=True)
-            host_layers, dual_layers = coop.host_set(), coop.superset()
-        kv = KVState(model, n_gpu, B, T + max_new_tokens, all_on_device=on_dev, host_layers=host_layers, dual_layers=dual_layers)
+        kv = sched.new_kv_state(B, T, max_new_tokens, **lia)     # where each layer's cache lives: OffloadScheduler.new_kv_state
     unfinished = torch.ones(B, dtype=torch.int64)
     all_unfinished = True
     latency_list, logits_list = [], []

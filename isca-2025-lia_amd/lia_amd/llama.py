@@ -13,9 +13,11 @@ import numpy as np
 import torch
 
 from . import _native as N
-from . import ops
+from . import hostinfo, ops
+from .kvcache import KV_SERIAL
 from .model import LayerStore
-from .scheduler import WeightPipeline, _KV_SERIAL
+from .scheduler import default_stream_format, minibatch_bounds, wire_format_code
+from .streaming import HiddenPairs, ResidentRun, WeightPipeline, stream_order
 
 LLAMA_TENSORS = ("in_norm_w", "q_w", "k_w", "v_w", "o_w", "post_norm_w", "gate_w", "up_w", "down_w")
 
@@ -116,7 +118,6 @@ class LiaLlamaModel:
         """pack = 0 / 10: wire format of the pinned streamed layers (lia_pack10.hip), as for the OPT model"""
         self = cls(shape)
         n_gpu = shape.layers if n_gpu_layers is None else n_gpu_layers
-        from . import hostinfo
         hostinfo.check_host_allocation((shape.layers - n_gpu) * self.layer_bytes, f"{shape.name}: streamed layers")
         g = torch.Generator(device="cuda")
         g.manual_seed(seed * 100003)
@@ -171,7 +172,7 @@ class LlamaKVState:
     def __init__(self, model, B, smax):
         sh = model.shape
         self.B, self.smax, self.len = B, smax, 0
-        self.serial, self.version = next(_KV_SERIAL), 0
+        self.serial, self.version = next(KV_SERIAL), 0
         self.tensors, self.kv = [], []
         for _ in range(sh.layers):
             k = torch.empty((smax, B, sh.kv_heads, sh.head_dim), dtype=torch.bfloat16, device="cuda")
@@ -184,13 +185,11 @@ class LlamaScheduler:
     """forward(ids, kv, gpu_percentage=..., num_minibatch=...) -> (logits, next ids) on the device."""
 
     def __init__(self, model, device=0, n_slots=4, pack=None):
-        from .scheduler import default_stream_format
         self.model, self.device, self.n_slots = model, device, n_slots
         fmt = default_stream_format() if pack is None else pack
-        from .scheduler import wire_format_code
         self.pack = wire_format_code(fmt)
         self.ctx = self.pipe = None
-        self.hidden, self.resident, self.tables = {}, {}, None
+        self.hidden, self.resident, self.tables = HiddenPairs(model.shape.hidden), ResidentRun(model), None
         self.prefill_tail = True      # last layer of a prefill: last position only behind q|k|v (False: every position)
 
     def _ensure(self, rows, B, T, n_gpu, smax):
@@ -204,21 +203,12 @@ class LlamaScheduler:
             if self.ctx:
                 self.ctx.close()
             self.ctx = ops.Context(self.device, need)
-            from . import hostinfo
             hostinfo.cap_torch_threads()      # the token loop's CPU tensor ops: see hostinfo.cap_torch_threads
         if self.pipe is None and n_gpu < sh.layers:
             self.pipe = WeightPipeline(self.ctx, self.model, self.n_slots)
         if self.tables is None or self.tables[0].shape[0] < smax:
             self.tables = rope_tables(max(smax, 64), sh.head_dim, sh.rope_theta)
-        if (B, T) not in self.hidden:
-            if len(self.hidden) > 4:
-                self.hidden.clear()
-            self.hidden[(B, T)] = (torch.empty((B, T, sh.hidden), dtype=torch.bfloat16, device="cuda"),
-                                   torch.empty((B, T, sh.hidden), dtype=torch.bfloat16, device="cuda"))
-        return self.hidden[(B, T)]
-
-    def _ptrs(self, base):
-        return (ctypes.c_void_p * 9)(*[base + o for o in self.model.offsets])
+        return self.hidden.get(B, T)
 
     def forward(self, input_ids, kv_state, gpu_percentage=100, num_minibatch=1, pin_weight=True, enable_cxl=False,
                 suppress_token=-1, sampler=None, **_ignored):
@@ -228,14 +218,10 @@ class LlamaScheduler:
         B, T = input_ids.shape
         L = sh.layers
         n_gpu = L if gpu_percentage >= 100 else int(L * gpu_percentage / 100)
-        from .scheduler import minibatch_bounds
         minis = minibatch_bounds(B, num_minibatch) if T > 1 else [(0, B)]      # ragged last minibatch, num_minibatch clamped to B
         mini = max(n for _, n in minis)
         if m.placed_for != (n_gpu, bool(pin_weight), bool(enable_cxl), LayerStore._fmt_of(self.pack)):
-            if self.pipe is not None:
-                self.pipe.drain()          # copies in flight read the host buffers a re-placement frees
-            self.resident.clear()
-            self._run_key = None
+            self.resident.replaced(self.pipe)
         m.place(n_gpu, pin_weight, enable_cxl, self.pack)
         x, y = self._ensure(mini * T, B, T, n_gpu, kv_state.smax)
         ctx, pipe = self.ctx, self.pipe
@@ -247,26 +233,16 @@ class LlamaScheduler:
                                     ctypes.c_void_p(x.data_ptr()), B, T, sh.hidden, st), "lia_llama_embed")
         if n_gpu < L:
             pipe.prefetch(n_gpu)
-        def resident(i):
-            if i not in self.resident:
-                self.resident[i] = self._ptrs(m.layers[i].device_ptr())
-            return self.resident[i]
-
+        resident = self.resident.layer
         xlast = None
         first = 0
         if T == 1 and n_gpu > 0 and mini == B:
             # decode: the resident run in ONE library call (lia_llama_decode_layers: the per-op route layer by layer with the chained
             # norms, or with LIA_FUSED_DECODE=1 an attention launch and a persistent chain launch per layer, lia_chain.hip)
-            key = (n_gpu, kv_state.serial, kv_state.version, resident(0)[0])
-            if getattr(self, "_run_key", None) != key:
-                ptrs = []
-                for i in range(n_gpu):
-                    ptrs.extend(resident(i))
-                self._run = ((ctypes.c_void_p * (9 * n_gpu))(*ptrs), (ctypes.POINTER(N.KV) * n_gpu)(*[ctypes.pointer(kv_state.kv[i]) for i in range(n_gpu)]))
-                self._run_key = key
-            N.check(lib.lia_llama_decode_layers(ctx.handle, ctypes.byref(m.desc), n_gpu, ctypes.cast(self._run[0], ctypes.c_void_p),
-                                                ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()), ctypes.cast(self._run[1], ctypes.c_void_p),
-                                                ctypes.c_void_p(cos.data_ptr()), ctypes.c_void_p(sin.data_ptr()), B, pos0, st), "lia_llama_decode_layers")
+            wt, kvt = self.resident.decode_tables(n_gpu, kv_state)
+            N.check(lib.lia_llama_decode_layers(ctx.handle, ctypes.byref(m.desc), n_gpu, wt, ctypes.c_void_p(x.data_ptr()),
+                                                ctypes.c_void_p(y.data_ptr()), kvt, ctypes.c_void_p(cos.data_ptr()),
+                                                ctypes.c_void_p(sin.data_ptr()), B, pos0, st), "lia_llama_decode_layers")
             x, y = y, x
             first = n_gpu
         for idx in range(first, L):
@@ -275,13 +251,8 @@ class LlamaScheduler:
                 if T == 1 and idx + 1 < n_gpu:
                     ctx.chain_next_norm(resident(idx + 1)[0])      # decode: the next layer's input RMSNorm rides in this layer's down-proj combine
             else:
-                w = self._ptrs(pipe.slot_ptrs[self._acquire(pipe, idx)])
-                nxt = idx
-                for _ in range(pipe.n_slots - 1):
-                    nxt = nxt + 1 if nxt + 1 < L else n_gpu
-                    if nxt == idx or not pipe.can_prefetch():
-                        break
-                    pipe.prefetch(nxt)
+                w = pipe.acquire(idx)
+                pipe.prefetch_ahead(idx, stream_order(idx, n_gpu, L))
             tail = self.prefill_tail and T > 1 and pos0 == 0 and idx == L - 1
             if tail:
                 xlast = torch.empty((B, 1, sh.hidden), dtype=torch.bfloat16, device="cuda")
@@ -306,11 +277,6 @@ class LlamaScheduler:
         ctx.synchronize()
         kv_state.len = pos0 + T
         return logits, nxt_ids
-
-    @staticmethod
-    def _acquire(pipe, idx):
-        pipe.acquire(idx)
-        return pipe.held[idx]
 
     def stream_stats(self, reset=False):
         return self.pipe.stats(reset) if self.pipe else (0.0, 0.0)

@@ -125,13 +125,22 @@ class Context:
 
     def embed(self, ids, tok, pos, past_len, stream=None):
         _chk(ids, torch.int64)
+        B, T = ids.shape
+        y = torch.empty((B, T, tok.shape[1]), dtype=torch.bfloat16, device=tok.device)
+        self.embed_into(ids, tok, pos, y, past_len, stream=stream)
+        return y
+
+    def embed_into(self, ids, tok, pos, y, past_len, starts=None, stream=None):
+        """token + position embedding of ids [B, T] (int64, device) into y [B, T, H]; starts (int32 [B], device, or None): row b's
+        first real position of a left-padded batch, whose positions then count from it."""
         _chk(tok)
         _chk(pos)
         B, T = ids.shape
-        H = tok.shape[1]
-        y = torch.empty((B, T, H), dtype=torch.bfloat16, device=tok.device)
-        N.check(self.lib.lia_embed(_ptr(ids), _ptr(tok), _ptr(pos), _ptr(y), B, T, past_len, H, self._st(stream)), "lia_embed")
-        return y
+        args = (_ptr(ids), _ptr(tok), _ptr(pos), _ptr(y), B, T, past_len, tok.shape[1])
+        if starts is None:
+            N.check(self.lib.lia_embed(*args, self._st(stream)), "lia_embed")
+        else:
+            N.check(self.lib.lia_embed_padded(*args, _ptr(starts), self._st(stream)), "lia_embed")
 
     LM_HEAD_ROWS = 256       # rows per lia_lm_head call (its argmax scratch is sized for that many)
 
@@ -201,4 +210,5 @@ def workspace_bytes(desc, max_rows):
 
 
 def weight_ptr_array(base_ptr, offsets):
-    return (ctypes.c_void_p * 16)(*[base_ptr + o for o in offsets])
+    """the device (or host) pointers of one layer's tensors: 16 for an OPT layer, 9 for a Llama layer"""
+    return (ctypes.c_void_p * len(offsets))(*[base_ptr + o for o in offsets])

@@ -1,0 +1,276 @@
+"""What both schedulers (scheduler.OffloadScheduler, llama.LlamaScheduler) need to stream weights through HBM slots and to run
+the resident layers: the slot pipeline over lia_stream_*, the order it prefetches in, the (B, T) hidden-state buffers and the
+pointer tables of the one-call resident decode run."""
+import ctypes
+
+import torch
+
+from . import _native as N
+from . import ops
+from .model import LayerStore
+
+# (`.dp` is imported where a DataParallelGroup is in use, never at module level: it pulls in torch.distributed)
+
+
+class WeightPipeline:
+    """Slot bookkeeping over lia_stream_*: prefetch(layer) -> acquire(layer) -> release(layer)."""
+
+    def __init__(self, ctx, model, n_slots, dp_group=None):
+        self.ctx, self.model, self.lib = ctx, model, N.lib()
+        self.dp = dp_group
+        h = ctypes.c_void_p()
+        N.check(self.lib.lia_stream_create(ctx.handle, n_slots, model.layer_bytes, ctypes.byref(h)), "lia_stream_create")
+        self.handle, self.n_slots = h, n_slots
+        self.free_slots = list(range(n_slots))
+        self.inflight = []          # [(layer_idx, slot)] in issue order, not yet acquired
+        self.held = {}              # layer_idx -> slot (acquired, not yet released)
+        self.slot_ptrs = [self.lib.lia_stream_slot_ptr(h, s) for s in range(n_slots)]
+        self.ptr_arrays = [ops.weight_ptr_array(p, model.offsets) for p in self.slot_ptrs]
+        if dp_group is not None:
+            from .dp import RawDeviceBuffer
+            self.slot_tensors = [RawDeviceBuffer(p, model.layer_bytes).tensor() for p in self.slot_ptrs]
+            self.copy_stream = torch.cuda.ExternalStream(self.lib.lia_stream_copy_stream(h))
+            self.staging_tensors = None
+            # the root tells every rank which layers travel pack10-encoded and how many bytes each one ships
+            # (gloo validation runs without a GPU -- tests/test_dp_gloo.py -- keep the table on the host)
+            meta = torch.zeros((len(model.layers), 2), dtype=torch.int64, device="cuda" if torch.cuda.is_available() else "cpu")
+            if dp_group.is_root:
+                for i, st in enumerate(model.layers):
+                    if st.tier not in ("device", None):
+                        meta[i, 0], meta[i, 1] = int(st.packed), int(st.stream_bytes)
+            dp_group.dist.broadcast(meta, src=dp_group.root)
+            self.layer_meta = meta.cpu().tolist()
+            if dp_group.mode == "allgather" and dp_group.world > 1:
+                for i, st in enumerate(model.layers):
+                    if st.tier not in ("device", None, "remote") and [int(st.packed), int(st.stream_bytes)] != self.layer_meta[i]:
+                        raise RuntimeError(f"layer {i}: this rank's wire encoding differs from the root's (allgather streaming needs "
+                                           "identical weights and format on every rank)")
+
+    def can_prefetch(self):
+        return bool(self.free_slots)
+
+    def prefetch(self, layer_idx):
+        if any(li == layer_idx for li, _ in self.inflight) or layer_idx in self.held:
+            return
+        if not self.can_prefetch():
+            return
+        st = self.model.layers[layer_idx]
+        slot = self.free_slots.pop(0)
+        if self.dp is None and st.packed:
+            N.check(self.lib.lia_stream_prefetch_packed(self.handle, slot, ctypes.c_void_p(st.host_ptr()), st.stream_bytes, st.nbytes // 2,
+                                                        int(st.packed), int(st.is_dma_able())), "lia_stream_prefetch_packed")
+        elif self.dp is None:
+            N.check(self.lib.lia_stream_prefetch(self.handle, slot, ctypes.c_void_p(st.host_ptr()), st.nbytes, int(st.is_dma_able())),
+                    "lia_stream_prefetch")
+        elif self.dp.mode == "allgather" and self.dp.world > 1:        # (one rank: nothing to gather, the broadcast path serves)
+            self._prefetch_allgather(st, slot, layer_idx)
+        else:
+            self._prefetch_broadcast(st, slot, layer_idx)
+        self.inflight.append((layer_idx, slot))
+
+    def _prefetch_broadcast(self, st, slot, layer_idx):
+        """Root: host -> slot in chunks, each chunk RCCL-broadcast over xGMI as soon as it is enqueued, so chunk
+        k travels to the peers while chunk k+1 is still arriving over PCIe.  Peers: receive into the same slot.
+        Everything is ordered on the copy stream; the slot is declared ready after the last broadcast."""
+        from .dp import RawDeviceBuffer, broadcast_chunked
+        dp = self.dp
+        packed, nbytes = self.layer_meta[layer_idx]
+        N.check(self.lib.lia_stream_begin(self.handle, slot), "lia_stream_begin")
+        if packed:
+            target, copy_fn = self._staging()[slot][:nbytes], self.lib.lia_stream_copy_chunk_packed
+        else:
+            target, copy_fn = self.slot_tensors[slot][:self.model.layer_bytes], self.lib.lia_stream_copy_chunk
+        before = None
+        if dp.is_root:
+            base, pinned = st.host_ptr(), int(st.is_dma_able())
+
+            def before(off, n):
+                N.check(copy_fn(self.handle, slot, off, ctypes.c_void_p(base + off), n, pinned), "lia_stream_copy_chunk")
+        with torch.cuda.stream(self.copy_stream):
+            works = broadcast_chunked(dp.dist, target, dp.root, dp.chunk_bytes, before_chunk=before)
+            for w in works:
+                w.wait()              # the copy stream waits for RCCL's stream; the host does not block
+        if packed:
+            N.check(self.lib.lia_stream_decode_packed(self.handle, slot, self.model.layer_bytes // 2, int(packed)), "lia_stream_decode_packed")
+        N.check(self.lib.lia_stream_mark_ready(self.handle, slot), "lia_stream_mark_ready")
+
+    def _staging(self):
+        if self.staging_tensors is None:
+            from .dp import RawDeviceBuffer
+            cap = self.lib.lia_pack10_bound(self.model.layer_bytes // 2)
+            self.staging_tensors = [RawDeviceBuffer(self.lib.lia_stream_staging_ptr(self.handle, s), cap).tensor()
+                                    for s in range(self.n_slots)]
+        return self.staging_tensors
+
+    def _prefetch_allgather(self, st, slot, layer_idx):
+        """Every rank copies ITS slice of the layer's wire bytes host -> device over its own link, then one all-gather on
+        the copy stream assembles the layer in every rank's slot (or staging area, then the decode kernel)."""
+        dp = self.dp
+        packed, nbytes = self.layer_meta[layer_idx]
+        G, r = dp.world, dp.rank
+        sh = LayerStore.shard_bytes(nbytes, G)
+        if st.shard is None or st.shard != (r, G, sh):
+            raise ValueError(f"layer {layer_idx}: allgather streaming needs the host copy pinned as slice {r} of {G} "
+                             "(LiaOPTModel.random_init(..., shard=(rank, world)))")
+        N.check(self.lib.lia_stream_begin(self.handle, slot), "lia_stream_begin")
+        if packed:
+            full, copy_fn = self._staging()[slot], self.lib.lia_stream_copy_chunk_packed
+        else:
+            full, copy_fn = self.slot_tensors[slot], self.lib.lia_stream_copy_chunk
+        if G * sh > full.numel():
+            raise ValueError(f"layer {layer_idx}: {G} slices of {sh} bytes do not fit the {full.numel()}-byte slot")
+        full = full[:G * sh]
+        N.check(copy_fn(self.handle, slot, r * sh, ctypes.c_void_p(st.host_ptr()), sh, int(st.is_dma_able())), "lia_stream_copy_chunk")
+        mine = full[r * sh:(r + 1) * sh]
+        with torch.cuda.stream(self.copy_stream):
+            if dp.dist.get_backend() == "nccl":
+                dp.dist.all_gather_into_tensor(full, mine, async_op=True).wait()      # in place: `mine` is slice r of `full`
+            else:
+                parts = [torch.empty_like(mine) for _ in range(G)]                    # gloo (validation runs): out of place
+                dp.dist.all_gather(parts, mine.clone())
+                for g, p in enumerate(parts):
+                    if g != r:
+                        full[g * sh:(g + 1) * sh].copy_(p)
+        if packed:
+            N.check(self.lib.lia_stream_decode_packed(self.handle, slot, self.model.layer_bytes // 2, int(packed)), "lia_stream_decode_packed")
+        N.check(self.lib.lia_stream_mark_ready(self.handle, slot), "lia_stream_mark_ready")
+
+    def acquire(self, layer_idx):
+        """Make the compute stream wait for the layer's copy; returns the 16 device pointers."""
+        pos = next((j for j, (li, _) in enumerate(self.inflight) if li == layer_idx), None)
+        if pos is None:
+            # the layer was not prefetched (a prefill after a decode step with host-computed layers, a different gpu%):
+            # load it on demand.  Queued copies of OTHER layers are kept -- the copy stream runs them in order and they
+            # are acquired later in this forward; only when every slot is taken is the NEWEST of them given up
+            # (lia_stream_begin orders the slot's next copy behind the dropped one's decode kernel).
+            while not self.free_slots and self.inflight:
+                _, s_drop = self.inflight.pop()
+                self.free_slots.append(s_drop)
+            if not self.free_slots:
+                raise RuntimeError(f"no streamer slot free for layer {layer_idx}: {len(self.held)} layers are held")
+            self.prefetch(layer_idx)
+            pos = len(self.inflight) - 1
+        li, slot = self.inflight.pop(pos)
+        N.check(self.lib.lia_stream_wait(self.handle, slot, ctypes.c_void_p(self.ctx.stream)), "lia_stream_wait")
+        self.held[layer_idx] = slot
+        return self.ptr_arrays[slot]
+
+    def release(self, layer_idx):
+        slot = self.held.pop(layer_idx)
+        N.check(self.lib.lia_stream_release(self.handle, slot, ctypes.c_void_p(self.ctx.stream)), "lia_stream_release")
+        self.free_slots.append(slot)
+
+    def prefetch_ahead(self, idx, next_layer):
+        """Layer idx has just been acquired: fill every free slot with the layers that follow it (next_layer: an iterator,
+        stream_order below), n_slots - 1 of them at most, until a slot is missing or the order comes back to idx.  The weight
+        copies of the next streamed layer(s) overlap this layer's compute (:1305-1312, :1508-1515); behind the last layer the
+        order wraps to the first streamed layer of the NEXT forward, so the copy engine keeps running across token steps."""
+        for _, nxt in zip(range(self.n_slots - 1), next_layer):
+            if nxt == idx or not self.can_prefetch():
+                break
+            self.prefetch(nxt)
+
+    def forget(self, layer_idx):
+        """Give up a queued copy of layer_idx (it will not be used: the layer's decode step moved to the host cores).  The slot is
+        free again at once; lia_stream_begin orders its next copy behind the abandoned one."""
+        for j, (li, slot) in enumerate(self.inflight):
+            if li == layer_idx:
+                self.inflight.pop(j)
+                self.free_slots.append(slot)
+                return True
+        return False
+
+    def decode_stats(self, reset=False, block=True):
+        """wire-format decode kernel since the last reset: {"launches", "ms", "bytes_in", "bytes_out"} (lia_stream_decode_stats);
+        block=False: never waits for decodes in flight (lia_stream_poll_decode_stats) -- for the edge of a timed region"""
+        n, ms, bi, bo = ctypes.c_long(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        fn = self.lib.lia_stream_decode_stats if block else self.lib.lia_stream_poll_decode_stats
+        N.check(fn(self.handle, ctypes.byref(n), ctypes.byref(ms), ctypes.byref(bi), ctypes.byref(bo), int(reset)))
+        return {"launches": n.value, "ms": ms.value, "bytes_in": bi.value, "bytes_out": bo.value}
+
+    def poll_stats(self):
+        """(bytes, busy ms) of the copies that have COMPLETED so far -- never blocks (stats() waits for the queued copies)"""
+        b, ms = ctypes.c_double(), ctypes.c_double()
+        N.check(self.lib.lia_stream_poll_stats(self.handle, ctypes.byref(b), ctypes.byref(ms)))
+        return b.value, ms.value
+
+    def drain(self):
+        """Forget every queued copy and wait for the copy engine: called before the model re-tiers its layers."""
+        for _, slot in self.inflight:
+            self.free_slots.append(slot)
+        self.inflight = []
+        torch.cuda.synchronize()
+
+    def stats(self, reset=False):
+        b, ms = ctypes.c_double(), ctypes.c_double()
+        N.check(self.lib.lia_stream_stats(self.handle, ctypes.byref(b), ctypes.byref(ms), int(reset)))
+        return b.value, ms.value
+
+    def close(self):
+        if self.handle:
+            self.lib.lia_stream_destroy(self.handle)
+            self.handle = None
+
+
+def stream_order(idx, first, L, skip=frozenset(), skip_now=True):
+    """The streamed layers behind idx in the order they will be needed, without end: idx + 1 ... L - 1, then first ... L - 1 of
+    the next forward, and so on.  skip: the layers a decode step computes on the host cores, which need no slot; a prefill
+    streams every layer (skip_now=False), so for it they are left out only behind the wrap, where the next forward is a
+    decode step.  (skip never holds `first`: OffloadScheduler.cpu_layer_order.)"""
+    i, skipping = idx, skip_now
+    while True:
+        i += 1
+        if i >= L:
+            i, skipping = first, True
+        if not (skipping and i in skip):
+            yield i
+
+
+class HiddenPairs:
+    """(B, T) -> two [B, T, hidden] bf16 device buffers (a layer reads one and writes the other), kept across forwards; all are
+    dropped when a sixth shape arrives."""
+
+    def __init__(self, hidden):
+        self.hidden, self.pairs = hidden, {}
+
+    def get(self, B, T):
+        if (B, T) not in self.pairs:
+            if len(self.pairs) > 4:
+                self.pairs.clear()
+            x = torch.empty((B, T, self.hidden), dtype=torch.bfloat16, device="cuda")
+            self.pairs[(B, T)] = (x, torch.empty_like(x))
+        return self.pairs[(B, T)]
+
+
+class ResidentRun:
+    """Device pointers of the HBM-resident layers: one array per layer (16 pointers for OPT, 9 for Llama: len(model.offsets)),
+    built on first use, and the two tables lia_decode_layers / lia_llama_decode_layers take for the whole resident run of a
+    decode step, rebuilt only when the run, the KV caches (serial, version) or the first layer's address changed."""
+
+    def __init__(self, model):
+        self.model, self.ptrs, self.key, self.arrays, self.tables = model, {}, None, None, None
+
+    def layer(self, idx):
+        if idx not in self.ptrs:
+            self.ptrs[idx] = ops.weight_ptr_array(self.model.layers[idx].device_ptr(), self.model.offsets)
+        return self.ptrs[idx]
+
+    def decode_tables(self, n_gpu, kv_state):
+        """(weight pointers [n_gpu x pointers per layer], KV struct pointers [n_gpu]), each cast to void*"""
+        key = (n_gpu, kv_state.serial, kv_state.version, self.layer(0)[0])
+        if self.key != key:
+            ptrs = []
+            for i in range(n_gpu):
+                ptrs.extend(self.layer(i))
+            self.arrays = ((ctypes.c_void_p * len(ptrs))(*ptrs), (ctypes.POINTER(N.KV) * n_gpu)(*[ctypes.pointer(kv_state.kv[i]) for i in range(n_gpu)]))
+            self.tables = tuple(ctypes.cast(a, ctypes.c_void_p) for a in self.arrays)
+            self.key = key
+        return self.tables
+
+    def replaced(self, pipe):
+        """The model is about to re-tier its layers (another gpu%, wire format, host tier; policy 1 wants raw host copies):
+        copies in flight read host buffers that are about to be freed, and the cached device pointers go stale."""
+        if pipe is not None:
+            pipe.drain()
+        self.ptrs.clear()
+        self.key = None

@@ -166,6 +166,86 @@ def test_weight_pipeline_slot_order(monkeypatch, n_slots):
             held.discard(s)
 
 
+@pytest.mark.parametrize("n_slots", [2, 3])
+def test_weight_pipeline_prefetch_ahead(monkeypatch, n_slots):
+    """The schedulers' own prefetch loop (WeightPipeline.prefetch_ahead over streaming.stream_order), driven the way a forward
+    drives it: behind every acquire the n_slots - 1 layers needed next are in flight, in order; the order wraps to the first
+    streamed layer after the last; a decode step skips the host-computed layers, a prefill only behind its wrap; slots rotate and
+    none is refilled before its layer is released."""
+    from lia_amd import streaming, _native
+
+    fake = _FakeLib()
+    monkeypatch.setattr(_native, "lib", lambda: fake)
+
+    class Store:
+        nbytes = 64
+        packed = 0
+        stream_bytes = 64
+
+        def host_ptr(self):
+            return 0x9000
+
+        def is_dma_able(self):
+            return True
+
+    class Model:
+        layer_bytes = 64
+        offsets = list(range(16))
+        layers = [Store() for _ in range(6)]
+
+    class Ctx:
+        handle, stream = 1, 2
+
+    first, L = 2, 6
+    assert list(zip(range(6), streaming.stream_order(4, first, L))) == list(enumerate([5, 2, 3, 4, 5, 2]))
+    assert [i for _, i in zip(range(5), streaming.stream_order(3, first, L, {4}))] == [5, 2, 3, 5, 2]                 # a decode step
+    assert [i for _, i in zip(range(5), streaming.stream_order(3, first, L, {4}, skip_now=False))] == [4, 5, 2, 3, 5]  # a prefill
+
+    def run(forwards):
+        """forwards: [(host-computed layers, is a decode step)] -> the layers in flight behind every acquire"""
+        pipe = streaming.WeightPipeline(Ctx(), Model(), n_slots)
+        seen = []
+        for host, decode in forwards:
+            pipe.prefetch(first)
+            for idx in range(first, L):
+                if decode and idx in host:
+                    continue
+                pipe.acquire(idx)
+                pipe.prefetch_ahead(idx, streaming.stream_order(idx, first, L, host, skip_now=decode))
+                seen.append((idx, [li for li, _ in pipe.inflight]))
+                pipe.release(idx)
+        return seen
+
+    def check(seen, seq):
+        """seq: the layers in the order the forwards need them (one more forward than ran)"""
+        assert [idx for idx, _ in seen] == seq[:len(seen)]
+        for k, (_, inflight) in enumerate(seen):
+            assert inflight == seq[k + 1:k + n_slots], (k, inflight)          # depth n_slots - 1, nothing else queued
+        pf = [s for op, s in fake.log if op == "prefetch"]
+        assert len(pf) == len(seen) + n_slots - 1                          # one copy per layer use: nothing copied twice or dropped
+        assert pf == [i % n_slots for i in range(len(pf))]                 # slots rotate
+        waits = [s for op, s in fake.log if op == "wait"]
+        assert waits == pf[:len(waits)]                                    # layers are consumed in the order they were copied
+        held = set()
+        for op, s in fake.log:                                             # a slot is never re-filled before its layer was released
+            if op == "prefetch":
+                assert s not in held
+            elif op == "wait":
+                held.add(s)
+            elif op == "release":
+                held.discard(s)
+        del fake.log[:]
+
+    check(run([(frozenset(), False), (frozenset(), True), (frozenset(), True)]), [2, 3, 4, 5] * 4)
+    # the cooperative split computes layer 4's decode steps on the host cores: the prefill streams it, the decode steps never do
+    check(run([({4}, False), ({4}, True), ({4}, True)]), [2, 3, 4, 5] + [2, 3, 5] * 3)
+    # fewer streamed layers than slots: the order comes back to the layer in hand and the loop stops there
+    first = 4
+    assert run([(frozenset(), False), (frozenset(), True)]) == [(4, [5]), (5, [4]), (4, [5]), (5, [4])]
+    first = 5
+    assert run([(frozenset(), True), (frozenset(), True)]) == [(5, []), (5, [])]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # world 4 and 8 (gloo, CPU): row sharding with remainders, the id gather, per-rank host-core slices, and the two ways a
 # streamed layer reaches every rank -- WeightPipeline._prefetch_broadcast / _prefetch_allgather -- over a streamer whose slots
