@@ -352,11 +352,32 @@ int lia_pack10_validate(const void* header_host, size_t staged_bytes, size_t n_v
 #define LIA_P10_ESCAPE (-8)   /* more escape records than level-3 codes, or a record index >= n_values                     */
 /* Rebuild the raw bf16 values of an encoded buffer (device -> device), asynchronous on `stream` (NULL = the default
  * stream): the kernels the streamer runs, exposed for re-tiering a layer that the host holds in a packed format
- * (model placement, lia/modeling_opt.py:229-268) and for the round-trip tests.  format: 10 (the argument is kept so that a later
- * format needs no new entry point).  A buffer that lia_pack10_validate passed is decoded without a read outside src_device
- * when src_device holds lia_pack10_bound(n_values) bytes. */
+ * (model placement, lia/modeling_opt.py:229-268) and for the round-trip tests.  format: the codec the buffer holds, LIA_WIRE_PACK10
+ * or LIA_WIRE_PACK10A (lia_pack_codec reads it from a host copy's header); a call with another codec than the bytes hold decodes
+ * garbage, one with any other value is refused.  A buffer that its codec's validator passed is decoded without a read outside
+ * src_device when src_device holds lia_pack10_bound(n_values) bytes. */
 int lia_pack_decode(const char* src_device, lia_bf16* dst_device, size_t n_values, int format, void* stream);
-/* format: 10 */
+/* pack10a: the second codec of the pack10 wire family (lia_pack10a.hip): the same sign|mantissa byte plane, the exponents of every
+ * 65536-value chunk coded by a 64-lane interleaved range-ANS coder (32-bit states, 16-bit words, one word stream per chunk) against
+ * a 10-bit frequency table built per chunk over the exponents present in it -- 10.59 bits per value for N(0,sigma) weights.  Every
+ * exponent has a code (no escape records).  Buffer: [header 256][directory: (chunks + 1) x {u32 first word, u32 first table
+ * entry}][table entries u32: exponent | (f - 1) << 8][final states: chunks x 64 u32][sign|mantissa plane][u16 words].
+ * "pack10" as a wire format names the family; the codec of a buffer is told by its header.
+ * encode: as lia_pack10_encode (dst_capacity >= lia_pack10_bound(n_values)); returns 1 when the encoding would not fit
+ * lia_pack10_bound(n_values), the size of every staging buffer, or is not smaller than max_bytes (0: no limit) -- the caller then
+ * ships what it has (pack10 v2, or raw). */
+#define LIA_WIRE_PACK10 10
+#define LIA_WIRE_PACK10A 0x10a
+int lia_pack10a_encode(const lia_bf16* src_device, size_t n_values, char* dst_device, size_t dst_capacity, size_t max_bytes, size_t* out_bytes);
+/* Host-side consistency check, the counterpart of lia_pack10_validate (same arguments, same moment): header, sections inside
+ * staged_bytes and lia_pack10_bound(n_values), word offsets starting at 0, never decreasing, ending at the stream's length, every
+ * chunk's 1..256 frequencies summing to 1024.  O(chunks + table entries).  Returns 0 or LIA_P10_SHORT / _FORMAT / _COUNT / _OFFSET /
+ * _TABLE (the directory) / LIA_P10A_FREQ (a frequency table). */
+int lia_pack10a_validate(const void* header_host, size_t staged_bytes, size_t n_values);
+#define LIA_P10A_FREQ (-9)    /* a chunk's frequencies do not sum to 1024, or its exponents do not ascend                    */
+/* the codec of an encoded buffer from its first bytes on the host: LIA_WIRE_PACK10, LIA_WIRE_PACK10A, or 0 (neither) */
+int lia_pack_codec(const void* header_host, size_t bytes);
+/* format: LIA_WIRE_PACK10 | LIA_WIRE_PACK10A, the codec of the bytes shipped */
 int lia_stream_prefetch_packed(lia_streamer* s, int slot, const void* host_ptr, size_t packed_bytes, size_t n_values, int format,
                                int pinned);
 int lia_stream_copy_chunk_packed(lia_streamer* s, int slot, size_t offset, const void* host_ptr, size_t bytes, int pinned);

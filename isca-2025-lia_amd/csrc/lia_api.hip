@@ -1196,6 +1196,13 @@ extern "C" int lia_decode_layers(lia_ctx* ctx, const lia_layer_desc* d, int n_la
 // ------------------------------------------------------------------------------------------------
 extern "C" size_t lia_pack10_bound(size_t n_values);
 extern "C" void lia_packed_decode_launch(const char* src, bf16_t* dst, size_t n_values, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+extern "C" void lia_pack10a_decode_launch(const char* src, bf16_t* dst, size_t n_values, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+// the decode of one codec of the pack10 family (format: LIA_WIRE_PACK10 | LIA_WIRE_PACK10A, checked by the callers)
+static void wire_decode_launch(int format, const char* src, bf16_t* dst, size_t n_values, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+  if (format == LIA_WIRE_PACK10A) lia_pack10a_decode_launch(src, dst, n_values, st, ev0, ev1);
+  else lia_packed_decode_launch(src, dst, n_values, st, ev0, ev1);
+}
+static inline bool wire_format_known(int format) { return format == LIA_WIRE_PACK10 || format == LIA_WIRE_PACK10A; }
 
 struct lia_streamer {
   lia_ctx* ctx;
@@ -1399,7 +1406,7 @@ extern "C" int lia_stream_copy_chunk_packed(lia_streamer* s, int slot, size_t of
 }
 
 extern "C" int lia_stream_decode_packed(lia_streamer* s, int slot, size_t n_values, int format) {
-  if (!s || slot < 0 || slot >= s->n_slots || !s->staging || n_values * 2 > s->slot_bytes || format != 10 || (n_values % 1024)) {
+  if (!s || slot < 0 || slot >= s->n_slots || !s->staging || n_values * 2 > s->slot_bytes || !wire_format_known(format) || (n_values % 1024)) {
     lia_set_error("lia_stream_decode_packed: slot=%d n_values=%zu format=%d", slot, n_values, format);
     return LIA_ERR_INVALID;
   }
@@ -1415,8 +1422,8 @@ extern "C" int lia_stream_decode_packed(lia_streamer* s, int slot, size_t n_valu
   streamer_collect_decode(s, slot, false);
   (void)hipGetLastError();                                             // hipErrorNotReady from the query is an answer, not an error
   const bool timed = !s->decode_pending[slot];
-  lia_packed_decode_launch(s->staging + (size_t)slot * s->staging_bytes, (bf16_t*)(s->slots + (size_t)slot * s->slot_bytes), n_values, s->decode,
-                           timed ? s->d0[slot] : nullptr, timed ? s->d1[slot] : nullptr);
+  wire_decode_launch(format, s->staging + (size_t)slot * s->staging_bytes, (bf16_t*)(s->slots + (size_t)slot * s->slot_bytes), n_values, s->decode,
+                     timed ? s->d0[slot] : nullptr, timed ? s->d1[slot] : nullptr);
   HIP_TRY(hipGetLastError());
   if (timed) {
     s->decode_in[slot] = (double)s->pending_bytes[slot];
@@ -1429,11 +1436,11 @@ extern "C" int lia_stream_decode_packed(lia_streamer* s, int slot, size_t n_valu
 
 extern "C" int lia_pack_decode(const char* src_device, lia_bf16* dst_device, size_t n_values, int format, void* stream) {
   if (!src_device || !dst_device) { lia_set_error("lia_pack_decode: NULL buffer"); return LIA_ERR_MISSING; }
-  if (format != 10 || (n_values % 1024)) {
+  if (!wire_format_known(format) || (n_values % 1024)) {
     lia_set_error("lia_pack_decode: n_values=%zu format=%d", n_values, format);
     return LIA_ERR_INVALID;
   }
-  lia_packed_decode_launch(src_device, dst_device, n_values, (hipStream_t)stream, nullptr, nullptr);
+  wire_decode_launch(format, src_device, dst_device, n_values, (hipStream_t)stream, nullptr, nullptr);
   HIP_TRY(hipGetLastError());
   return LIA_OK;
 }

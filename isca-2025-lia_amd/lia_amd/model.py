@@ -132,11 +132,13 @@ def draw_layer(shape, offsets, layer_bytes, li, seed=0, init="normal"):
 class LayerStore:
     """One decoder layer's 16 tensors packed into a flat 256-byte-aligned buffer (lia_layer_pack_offsets),
     living in exactly one tier at a time."""
+    CODEC_V2, CODEC_RANS = 10, 0x10A      # LIA_WIRE_PACK10, LIA_WIRE_PACK10A: the codecs of wire format 10
 
     def __init__(self, desc, offsets, total_bytes):
         self.desc, self.offsets, self.nbytes = desc, offsets, total_bytes
         self.tier = None          # "device" | "pinned" | "cxl" | "mapped" | "pageable" | "remote"
-        self.packed = 0           # 0: host copy is raw bf16; 10: it holds the lossless pack10 encoding (lia_pack10.hip)
+        self.packed = 0           # 0: host copy is raw bf16; 10: it holds a lossless encoding of the pack10 family
+        self.codec = 0            # which one: CODEC_V2 (lia_pack10.hip) or CODEC_RANS (lia_pack10a.hip); 0 with a raw copy
         self.shard = None         # (rank, world, slice bytes) when the host copy is one slice of the wire bytes
         self.stream_bytes = total_bytes   # bytes that cross the host link per use
         self.want_fmt = 0         # wire format asked for by the last to_pinned / to_cxl (a layer that does not fit stays raw)
@@ -208,7 +210,7 @@ class LayerStore:
         enc = torch.empty(self._lib.lia_pack10_bound(self.nbytes // 2), dtype=torch.uint8, device="cuda")
         N.check(self._lib.lia_memcpy_h2d(enc.data_ptr(), self._ptr, self.stream_bytes), "lia_memcpy_h2d")
         N.check(self._lib.lia_pack_decode(ctypes.c_void_p(enc.data_ptr()), ctypes.c_void_p(dev.data_ptr()), self.nbytes // 2,
-                                          int(self.packed), None), "lia_pack_decode")
+                                          int(self.codec), None), "lia_pack_decode")
         torch.cuda.synchronize()
         return dev
 
@@ -233,9 +235,13 @@ class LayerStore:
         self._free()
         self._np, self.tier = host, "pageable"
 
-    def _encode_packed(self, fmt, src):
+    def _encode_packed(self, fmt, src, v2_only=False):
         """src: the raw layer on the device -> (device uint8 tensor with the encoded bytes, n bytes), or None when the layer
-        does not fit the format."""
+        does not fit the format.  A layer that pack10 v2 refuses (or does not shrink) travels raw, as it always did.  For the
+        others the codec is chosen per layer and left in self._enc_codec: the range-ANS codec (lia_pack10a.hip) where its encoding
+        is smaller than v2's and fits lia_pack10_bound, else v2; v2_only: never the first (layers streamed inside a data-parallel
+        group, whose remote ranks see no header)."""
+        self._enc_codec = 0
         if fmt in (10, 11):
             if self.nbytes % 2048:
                 return None
@@ -251,19 +257,27 @@ class LayerStore:
         enc = torch.empty(cap, dtype=torch.uint8, device="cuda")
         out = ctypes.c_size_t()
         rc = encode(ctypes.c_void_p(src.data_ptr()), self.nbytes // 2, ctypes.c_void_p(enc.data_ptr()), cap, ctypes.byref(out))
-        if rc == 1:
-            return None            # too many out-of-window values: ship this layer raw
-        if rc != 0:
+        if rc not in (0, 1):
             raise N.LiaHipError(f"lia_pack{fmt}_encode failed ({rc})")
-        if out.value >= self.nbytes:
-            return None            # the encoding is no smaller than the raw layer (very wide distribution): ship raw
-        return enc, out.value
+        # rc 1: too many out-of-window values; an encoding no smaller than the raw layer (very wide distribution) is no use either
+        v2 = (enc, out.value) if rc == 0 and out.value < self.nbytes else None
+        if v2 and not v2_only:
+            enc_a = torch.empty(cap, dtype=torch.uint8, device="cuda")
+            rc = self._lib.lia_pack10a_encode(ctypes.c_void_p(src.data_ptr()), self.nbytes // 2, ctypes.c_void_p(enc_a.data_ptr()), cap,
+                                              v2[1], ctypes.byref(out))
+            if rc not in (0, 1):
+                raise N.LiaHipError(f"lia_pack10a_encode failed ({rc})")
+            if rc == 0:
+                self._enc_codec = self.CODEC_RANS
+                return enc_a, out.value
+        self._enc_codec = self.CODEC_V2 if v2 else 0
+        return v2                  # None: ship this layer raw
 
     @staticmethod
     def _fmt_of(pack):
         return {False: 0, True: 10, None: 0, "raw": 0, "pack10": 10}.get(pack, pack)          # accepts False / True (= 10) / 0 / 10 / the names
 
-    def to_pinned(self, wire=False, shard=None, keep_raw=False):
+    def to_pinned(self, wire=False, shard=None, keep_raw=False, v2_only=False):
         """Tensor.pin_memory() for all 16 tensors at once (lia/modeling_opt.py:207-227); with a packed format the pinned copy
         is that lossless encoding (67-75 % of the bytes).  shard = (r, G): keep only the r-th of G equal slices of the wire
         bytes (data-parallel "allgather" streaming: every rank pulls its slice over its own link).  keep_raw (with a packed
@@ -275,7 +289,7 @@ class LayerStore:
             if self.tier == "pinned" and self.shard and self.shard[:2] == tuple(shard) and self.want_fmt == fmt:
                 return
             return self._to_pinned_shard(fmt, shard)
-        if (self.tier == "pinned" and not self.shard and self.want_fmt == fmt and
+        if (self.tier == "pinned" and not self.shard and self.want_fmt == fmt and not (v2_only and self.codec == self.CODEC_RANS) and
                 (not keep_raw or not self.packed or getattr(self, "_raw_ptr", None))):
             return
         src = self._raw_on_device()
@@ -283,7 +297,7 @@ class LayerStore:
         from . import hostinfo
         raw_ptr = ptr = None
         try:
-            enc = self._encode_packed(fmt, src)
+            enc = self._encode_packed(fmt, src, v2_only)
             if enc and keep_raw:
                 try:
                     hostinfo.guard_host_allocation(self.nbytes + enc[1], "raw + packed pinned copies of a host-computed layer", ceiling=0.85)
@@ -312,6 +326,7 @@ class LayerStore:
             raise
         self._ptr, self.tier, self._raw_ptr = ptr, "pinned", raw_ptr
         self.packed, self.stream_bytes, self.want_fmt = (fmt if enc else 0), nbytes, fmt
+        self.codec = self._enc_codec if enc else 0
 
     @staticmethod
     def shard_bytes(total, world):
@@ -324,7 +339,7 @@ class LayerStore:
         self._free()
         ptr = None
         try:
-            enc = self._encode_packed(fmt, src0)
+            enc = self._encode_packed(fmt, src0, v2_only=True)      # the all-gather peers agree on pack10 v2
             if enc:
                 src, total = enc
             else:
@@ -346,19 +361,20 @@ class LayerStore:
             raise
         self._ptr, self.tier = ptr, "pinned"
         self.packed, self.stream_bytes, self.shard, self.want_fmt = (fmt if enc else 0), total, (r, G, sh), fmt
+        self.codec = self._enc_codec if enc else 0
 
-    def to_cxl(self, pack=0):
+    def to_cxl(self, pack=0, v2_only=False):
         """realloc_to_numa (lia/modeling_opt.py:168-175) + hipHostRegister so the copy engine can DMA from it
         (the reference leaves the CXL copy pageable, lia/cxl/numa_alloc.py:49).  pack = 10: the tier holds
         that lossless wire format instead of raw bf16 (fewer bytes in the tier AND on the link)."""
         fmt = self._fmt_of(pack)
-        if self.tier == "cxl" and self.want_fmt == fmt:
+        if self.tier == "cxl" and self.want_fmt == fmt and not (v2_only and self.codec == self.CODEC_RANS):
             return
         src = self._raw_on_device()
         self._free()
         ptr, registered, nbytes = None, False, self.nbytes
         try:
-            enc = self._encode_packed(fmt, src)
+            enc = self._encode_packed(fmt, src, v2_only)
             nbytes = enc[1] if enc else self.nbytes
             from . import hostinfo
             hostinfo.guard_host_allocation(nbytes, "CXL-tier copy of a streamed layer")
@@ -380,6 +396,7 @@ class LayerStore:
             raise
         self._ptr, self.tier = ptr, "cxl"
         self.packed, self.stream_bytes, self.want_fmt = (fmt if enc else 0), nbytes, fmt
+        self.codec = self._enc_codec if enc else 0
 
     def set_from_mapped_file(self, path, offset, nbytes, fmt):
         """The layer's wire bytes straight from a checkpoint file of the build's on-disk format (lia_amd.packed_checkpoint):
@@ -420,19 +437,23 @@ class LayerStore:
         self.packed, self.stream_bytes, self.want_fmt = int(fmt), nbytes, int(fmt)
         if fmt:
             try:
-                self._validate_packed(self._ptr, nbytes, path)       # the decode kernel trusts the header: check it before the first stream
+                self.codec = self._validate_packed(self._ptr, nbytes, path)   # the decode kernel trusts the header: check it before the first stream
             except ValueError:
                 self._free()
                 raise
 
     def _validate_packed(self, host_ptr, nbytes, what):
-        rc = self._lib.lia_pack10_validate(ctypes.c_void_p(host_ptr), nbytes, self.nbytes // 2)
+        """the codec the header names, after that codec's validator has passed the buffer"""
+        codec = self._lib.lia_pack_codec(ctypes.c_void_p(host_ptr), nbytes)
+        validate = self._lib.lia_pack10a_validate if codec == self.CODEC_RANS else self._lib.lia_pack10_validate
+        rc = validate(ctypes.c_void_p(host_ptr), nbytes, self.nbytes // 2)
         if rc != 0:
             why = {-1: "shorter than a header", -2: "bad magic / version", -3: "value count differs from this model's layer",
                    -4: "an offset points outside the buffer", -5: "a count exceeds its capacity",
                    -6: "a region table is invalid", -7: "an offset table is inconsistent",
-                   -8: "an escape record is invalid"}.get(rc, f"code {rc}")       # LIA_P10_* (include/lia_hip.h)
+                   -8: "an escape record is invalid", -9: "a frequency table is invalid"}.get(rc, f"code {rc}")   # LIA_P10_* (include/lia_hip.h)
             raise ValueError(f"{what}: not a consistent pack10 layer of {self.nbytes // 2} values ({why}); the file is stale or corrupt")
+        return codec
 
     def set_from_file_to_device(self, path, offset, nbytes, fmt):
         """A RESIDENT layer of a packed checkpoint directory: plain read of the wire bytes, one H2D copy, decoded on the device when
@@ -444,13 +465,12 @@ class LayerStore:
             raise ValueError(f"{path}: short read ({host.size} of {nbytes} bytes)")
         if fmt not in (0, 10):
             raise ValueError(f"{path}: wire format {fmt} is not supported by this build (raw or pack10)")
-        if fmt:
-            self._validate_packed(host.ctypes.data, nbytes, path)
+        codec = self._validate_packed(host.ctypes.data, nbytes, path) if fmt else 0
         dev = torch.empty(self.nbytes, dtype=torch.uint8, device="cuda")
         if fmt:
             enc = torch.empty(self._lib.lia_pack10_bound(self.nbytes // 2), dtype=torch.uint8, device="cuda")   # (as _raw_on_device)
             N.check(self._lib.lia_memcpy_h2d(enc.data_ptr(), host.ctypes.data, nbytes), "lia_memcpy_h2d")
-            N.check(self._lib.lia_pack_decode(ctypes.c_void_p(enc.data_ptr()), ctypes.c_void_p(dev.data_ptr()), self.nbytes // 2, int(fmt),
+            N.check(self._lib.lia_pack_decode(ctypes.c_void_p(enc.data_ptr()), ctypes.c_void_p(dev.data_ptr()), self.nbytes // 2, int(codec),
                                               None), "lia_pack_decode")
             torch.cuda.synchronize()
         else:
@@ -478,7 +498,7 @@ class LayerStore:
             self._mm = None
         self._ptr = self._dev = self._np = None
         self.tier = None
-        self.packed, self.stream_bytes, self.shard, self.want_fmt = 0, self.nbytes, None, 0
+        self.packed, self.codec, self.stream_bytes, self.shard, self.want_fmt = 0, 0, self.nbytes, None, 0
 
     def close(self):
         self._free()

@@ -8,7 +8,9 @@ Here a model is written ONCE as a directory of per-layer wire buffers, exactly t
     <dir>/lia_model.json     format tag, model shape, the 16 tensor offsets inside a layer buffer, one entry per layer
                              {file, wire (0 raw | 10 pack10), bytes, raw_bytes}, the head file
     <dir>/head.bin           embed_tokens | embed_positions | final_ln_w | final_ln_b, raw bf16
-    <dir>/layer_NNN.bin      one packed layer: raw bf16 (lia_layer_pack_offsets layout) or its lossless pack10 encoding
+    <dir>/layer_NNN.bin      one packed layer: raw bf16 (lia_layer_pack_offsets layout) or its lossless pack10 encoding; which
+                             codec of the pack10 family (v2, lia_pack10.hip, or the range-ANS one, lia_pack10a.hip: whichever is
+                             smaller for the layer) is told by the file's own header, read on the host when the file is loaded
 
 and loaded without a second host copy: resident layers are read straight into HBM, streamed layers are `mmap`ed (read-only,
 shared) and the mapping is registered with the driver (hipHostRegister, read-only), so the copy engine DMAs out of the page

@@ -36,6 +36,12 @@ class WeightPipeline:
             meta = torch.zeros((len(model.layers), 2), dtype=torch.int64, device="cuda" if torch.cuda.is_available() else "cpu")
             if dp_group.is_root:
                 for i, st in enumerate(model.layers):
+                    if getattr(st, "codec", 0) == 0x10A:      # LayerStore.CODEC_RANS
+                        # the peers of a data-parallel group see no header: inside a group every packed layer travels as pack10 v2
+                        if st.tier == "cxl":
+                            st.to_cxl(st.want_fmt, v2_only=True)
+                        else:
+                            st.to_pinned(st.want_fmt, keep_raw=bool(getattr(st, "_raw_ptr", None)), v2_only=True)
                     if st.tier not in ("device", None):
                         meta[i, 0], meta[i, 1] = int(st.packed), int(st.stream_bytes)
             dp_group.dist.broadcast(meta, src=dp_group.root)
@@ -58,7 +64,7 @@ class WeightPipeline:
         slot = self.free_slots.pop(0)
         if self.dp is None and st.packed:
             N.check(self.lib.lia_stream_prefetch_packed(self.handle, slot, ctypes.c_void_p(st.host_ptr()), st.stream_bytes, st.nbytes // 2,
-                                                        int(st.packed), int(st.is_dma_able())), "lia_stream_prefetch_packed")
+                                                        int(getattr(st, "codec", 0) or st.packed), int(st.is_dma_able())), "lia_stream_prefetch_packed")
         elif self.dp is None:
             N.check(self.lib.lia_stream_prefetch(self.handle, slot, ctypes.c_void_p(st.host_ptr()), st.nbytes, int(st.is_dma_able())),
                     "lia_stream_prefetch")

@@ -4,6 +4,7 @@
 // 0.83 GB in + 1.23 GB out per launch is larger than L2 + Infinity Cache).
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I isca-2025-lia_amd/csrc -I include tools/pack10_decode_bench.hip -o tools/pack10_decode_bench
 #include "../isca-2025-lia_amd/csrc/lia_pack10.hip"
+#include "../isca-2025-lia_amd/csrc/lia_pack10a.hip"      // the range-ANS codec: third leg below (the v2 legs stay for the A/B)
 
 // the r01-r04 decode, kept for tools/pack10_decode_bench.hip only (bit-identity + timing of the two)
 __global__ __launch_bounds__(256) void lia_pack10_decode_v1_kernel(const char* __restrict__ src, bf16_t* __restrict__ dst) {
@@ -144,6 +145,35 @@ int main(int argc, char** argv) {
              traffic / (sum / reps * 1e-3) / 8e12);
       if (nd) return 2;
     }
+  }
+  // ---- the range-ANS codec (lia_pack10a.hip) on the same values: encode (timed: it runs once per layer at placement), decode
+  {
+    size_t abytes = 0;
+    CK(hipDeviceSynchronize());
+    CK(hipEventRecord(e0, 0));
+    const int arc = lia_pack10a_encode(srcv, n, enc, cap, 0, &abytes);
+    CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
+    float enc_ms; CK(hipEventElapsedTime(&enc_ms, e0, e1));
+    printf("pack10a encode rc %d: %zu values -> %zu bytes = %.3f bits per value (v2: %.3f), %.1f ms\n", arc, n, abytes, 8.0 * abytes / n, 8.0 * bytes / n, enc_ms);
+    if (arc != 0) return 1;
+    CK(hipMemsetAsync(out, 0xee, n * 2, st));
+    lia_pack10a_decode_launch(enc, (bf16_t*)out, n, st, nullptr, nullptr);
+    CK(hipMemsetAsync(dcount, 0, 8, st));
+    count_diff<<<2048, 256, 0, st>>>(srcv, out, n, dcount);
+    unsigned long long nd = 0;
+    CK(hipMemcpyAsync(&nd, dcount, 8, hipMemcpyDeviceToHost, st)); CK(hipStreamSynchronize(st));
+    float best = 1e9f, sum = 0.f;
+    const int reps = 10;
+    for (int it = 0; it < reps; ++it) {
+      lia_pack10a_decode_launch(enc, (bf16_t*)out, n, st, e0, e1);
+      CK(hipStreamSynchronize(st));
+      float ms; CK(hipEventElapsedTime(&ms, e0, e1)); best = ms < best ? ms : best; sum += ms;
+    }
+    const double traffic = (double)abytes + 2.0 * n;
+    printf("pack10a (rANS) grid %5zu: mismatches vs source %llu; decode kernel %.1f us best, %.1f us mean -> %.2f TB/s (in %.2f GB + out %.2f GB) = %.3f of 8 TB/s\n",
+           (size_t)lp10a_chunks(n), nd, best * 1e3, sum / reps * 1e3, traffic / (sum / reps * 1e-3) / 1e12, abytes / 1e9, 2.0 * n / 1e9,
+           traffic / (sum / reps * 1e-3) / 8e12);
+    if (nd) return 2;
   }
   return 0;
 }
