@@ -209,6 +209,35 @@ int lia_lm_head(lia_ctx* ctx, const lia_bf16* hidden, int B, int T, int H, const
 int lia_sample(lia_ctx* ctx, const lia_bf16* logits, long ld, int B, int vocab, float temperature, int top_k, float top_p,
                int suppress_token, const float* uniforms, int64_t* next_ids, float* stats, void* stream);
 
+/* ---- scoring (DESIGN.md "Scoring"): per-token log-probabilities instead of the last position's logits ---------------------
+ * lia_token_logprobs: per row r of logits [M, ld] (bf16, device, ld >= vocab; columns >= vocab are never read), on the logits
+ * read as fp32:  m = max_j l_j,  s = sum_j exp(l_j - m),  logprobs[r] = l_target - (m + log s)  with target = targets[r]
+ * (int64, device; -1 = no target -> 0.0; any other value outside [0, vocab) is treated as -1: the ids live on the device, the
+ * caller validates them against the vocabulary) and greedy_ids[r] = the first index holding m (lia_lm_head's tie rule).
+ * logprobs: fp32 [M], greedy_ids: int64 [M], device.  -inf logits carry no mass.  One LIA_SCORE_ROW_THREADS workgroup per row;
+ * a lane adds at most LIA_SCORE_SERIAL(vocab) terms of s before the balanced tree over the lanes.
+ * LIA_ERR_INVALID, by name: a NULL logits / targets / logprobs / greedy_ids, M <= 0, vocab <= 0, ld < vocab. */
+#define LIA_SCORE_ROW_THREADS 1024
+#define LIA_SCORE_SERIAL(vocab) (8 * (((vocab) + 8 * LIA_SCORE_ROW_THREADS - 1) / (8 * LIA_SCORE_ROW_THREADS)))
+int lia_token_logprobs(lia_ctx* ctx, const lia_bf16* logits, long ld, int M, int vocab, const int64_t* targets, float* logprobs,
+                       int64_t* greedy_ids, void* stream);
+/* lia_lm_score / lia_llama_lm_score: final LayerNorm / RMSNorm of EVERY row of hidden [M, ldh] (ldh >= H), the lm_head GEMM
+ * (one bf16 rounding of the fp32 accumulator, as lia_lm_head rounds; never split over K, so a row's logits do not depend on the
+ * workspace or on the rows beside it inside one GEMM kernel), then lia_token_logprobs.  Any M >= 1; vocab % 16 == 0, H % 64 == 0.
+ * The [M, vocab] logits are never materialised as a whole.  CHUNK RULE: rows go through in chunks of
+ *     c = min(M, LIA_SCORE_MAX_CHUNK, (workspace_bytes - 512) / (2 H + 2 vocab))   rows,
+ * rounded down to a multiple of 256 when c < M: the context's workspace holds one chunk's normed rows [c, H] and its logits
+ * [c, vocab], nothing else.  LIA_ERR_MEMORY (with a message, before anything is launched) when c < min(M, 256).
+ * lia_lm_score_chunk_rows returns c (0: does not fit); lia_lm_score_workspace_bytes what the largest useful chunk needs. */
+#define LIA_SCORE_MAX_CHUNK 4096
+int lia_lm_score_chunk_rows(size_t workspace_bytes, int M, int H, int vocab);
+size_t lia_lm_score_workspace_bytes(int M, int H, int vocab);
+int lia_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int M, int H, const lia_bf16* lnw, const lia_bf16* lnb,
+                 const lia_bf16* emb, int vocab, float eps, const int64_t* targets, float* logprobs, int64_t* greedy_ids,
+                 void* stream);
+int lia_llama_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int M, int H, const lia_bf16* normw, const lia_bf16* lm,
+                       int vocab, float eps, const int64_t* targets, float* logprobs, int64_t* greedy_ids, void* stream);
+
 /* ---- Llama-family layer (BASELINE.json config 4; build-defined: the reference's LlamaDecoderLayer_forward,
  * decoder.py:121-169, has no policy plumbing -- SURVEY.md quirk 3).  Arithmetic = HF transformers' eager bf16 Llama.
  * weights[9]: 0 input_norm.w  1 q.w [h*d,H]  2 k.w [kvh*d,H]  3 v.w  4 o.w [H,h*d]  5 post_norm.w  6 gate.w [F,H]

@@ -27,6 +27,8 @@ extern "C" void lia_embed_launch(const int64_t* ids, const bf16_t* tok, const bf
 extern "C" void lia_argmax_launch(const bf16_t* logits, int64_t* out, int B, int vocab, int suppress, hipStream_t st);
 extern "C" void lia_sample_launch(const bf16_t* logits, long ld, int B, int vocab, float tau, int top_k, float top_p, int suppress,
                                   const float* uniforms, int64_t* out, float* stats, hipStream_t st);
+extern "C" void lia_token_logprobs_launch(const bf16_t* logits, long ld, int M, int vocab, const int64_t* targets, float* logprobs,
+                                          int64_t* greedy, hipStream_t st);
 extern "C" void lia_blit_launch(void* dst, const void* src, size_t bytes, hipStream_t st);
 extern "C" int lia_attn_prefill_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
                                        int B, int T, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
@@ -1104,6 +1106,85 @@ extern "C" int lia_llama_lm_head(lia_ctx* ctx, const lia_bf16* hidden, int B, in
   lia_argmax_launch(logits, next_ids, B, vocab, suppress_token, st);
   HIP_TRY(hipGetLastError());
   return LIA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// scoring: log p(target) and the greedy token of every row (lia_score.hip; the chunk rule is stated in lia_hip.h)
+// ------------------------------------------------------------------------------------------------
+extern "C" int lia_token_logprobs(lia_ctx* ctx, const lia_bf16* logits, long ld, int M, int vocab, const int64_t* targets,
+                                  float* logprobs, int64_t* greedy_ids, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!logits || !targets || !logprobs || !greedy_ids) {
+    lia_set_error("lia_token_logprobs: NULL %s", !logits ? "logits" : !targets ? "targets" : !logprobs ? "logprobs" : "greedy_ids");
+    return LIA_ERR_INVALID;
+  }
+  if (M <= 0) { lia_set_error("lia_token_logprobs: M=%d must be >= 1", M); return LIA_ERR_INVALID; }
+  if (vocab <= 0) { lia_set_error("lia_token_logprobs: vocab=%d must be >= 1", vocab); return LIA_ERR_INVALID; }
+  if (ld < vocab) { lia_set_error("lia_token_logprobs: ld=%ld < vocab=%d", ld, vocab); return LIA_ERR_INVALID; }
+  lia_token_logprobs_launch(logits, ld, M, vocab, targets, logprobs, greedy_ids, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+extern "C" int lia_lm_score_chunk_rows(size_t workspace_bytes, int M, int H, int vocab) {
+  if (M <= 0 || H <= 0 || vocab <= 0 || workspace_bytes < 512) return 0;
+  const size_t per_row = 2 * (size_t)H + 2 * (size_t)vocab;
+  size_t c = std::min({(size_t)M, (size_t)LIA_SCORE_MAX_CHUNK, (workspace_bytes - 512) / per_row});
+  if (c < (size_t)M) c = c / 256 * 256;
+  return c < (size_t)std::min(M, 256) ? 0 : (int)c;
+}
+
+extern "C" size_t lia_lm_score_workspace_bytes(int M, int H, int vocab) {
+  if (M <= 0 || H <= 0 || vocab <= 0) return 0;
+  return 512 + (size_t)std::min(M, LIA_SCORE_MAX_CHUNK) * (2 * (size_t)H + 2 * (size_t)vocab);
+}
+
+// norm_b == nullptr: RMSNorm (Llama), else LayerNorm
+static int lm_score_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int M, int H, const bf16_t* norm_w,
+                         const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, const int64_t* targets, float* logprobs,
+                         int64_t* greedy_ids, hipStream_t st) {
+  if (M <= 0) { lia_set_error("%s: M=%d must be >= 1", who, M); return LIA_ERR_INVALID; }
+  if (H <= 0 || H % 64 || vocab <= 0 || vocab % 16) { lia_set_error("%s: H=%d (%%64) vocab=%d (%%16)", who, H, vocab); return LIA_ERR_INVALID; }
+  if (ldh < H || ldh % 8) { lia_set_error("%s: ldh=%ld must be >= H=%d and a multiple of 8", who, ldh, H); return LIA_ERR_INVALID; }
+  const int c = lia_lm_score_chunk_rows(ctx->ws_bytes, M, H, vocab);
+  if (c <= 0) {
+    lia_set_error("%s: a workspace of %zu bytes holds no chunk of %d rows (normed rows [c, %d] + logits [c, %d] in bf16 need %zu)", who,
+                  ctx->ws_bytes, std::min(M, 256), H, vocab, (size_t)512 + (size_t)std::min(M, 256) * (2 * (size_t)H + 2 * (size_t)vocab));
+    return LIA_ERR_MEMORY;
+  }
+  ctx->normed_src = nullptr; ctx->chain_armed = false;   // the workspace is about to be reused
+  bf16_t* lno = (bf16_t*)ctx->ws;
+  bf16_t* logits = (bf16_t*)(ctx->ws + align_up((size_t)c * H * 2, 256));
+  const LiaEpilogue ep{nullptr, nullptr, 0, 0};
+  for (int r0 = 0; r0 < M; r0 += c) {
+    const int n = std::min(c, M - r0);
+    const bf16_t* x = hidden + (long)r0 * ldh;
+    if (norm_b) lia_layernorm_launch(x, ldh, norm_w, norm_b, lno, H, n, H, eps, st);
+    else lia_rmsnorm_launch(x, ldh, norm_w, lno, H, n, H, eps, st);
+    const LiaOutMap om = plain_out(logits, vocab, vocab);
+    const int rc = gemm_checked(ctx, lno, H, emb, n, vocab, H, ep, om, nullptr, 0, 0, st);    // no slabs: never split over K
+    if (rc) return rc;
+    lia_token_logprobs_launch(logits, vocab, n, vocab, targets + r0, logprobs + r0, greedy_ids + r0, st);
+  }
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+extern "C" int lia_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int M, int H, const lia_bf16* lnw, const lia_bf16* lnb,
+                            const lia_bf16* emb, int vocab, float eps, const int64_t* targets, float* logprobs, int64_t* greedy_ids,
+                            void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!hidden || !lnw || !lnb || !emb || !targets || !logprobs || !greedy_ids) { lia_set_error("lia_lm_score: NULL tensor"); return LIA_ERR_MISSING; }
+  return lm_score_impl("lia_lm_score", ctx, hidden, ldh, M, H, lnw, lnb, emb, vocab, eps, targets, logprobs, greedy_ids, (hipStream_t)stream);
+}
+
+extern "C" int lia_llama_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int M, int H, const lia_bf16* normw,
+                                  const lia_bf16* lm, int vocab, float eps, const int64_t* targets, float* logprobs,
+                                  int64_t* greedy_ids, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!hidden || !normw || !lm || !targets || !logprobs || !greedy_ids) { lia_set_error("lia_llama_lm_score: NULL tensor"); return LIA_ERR_MISSING; }
+  return lm_score_impl("lia_llama_lm_score", ctx, hidden, ldh, M, H, normw, nullptr, lm, vocab, eps, targets, logprobs, greedy_ids,
+                       (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -78,6 +78,13 @@ SIGNATURES = {
                             c_int, c_void_p, c_void_p, c_void_p]),
     "lia_sample": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_float, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p,
                            c_void_p]),
+    "lia_token_logprobs": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lia_lm_score_chunk_rows": (c_int, [c_size_t, c_int, c_int, c_int]),
+    "lia_lm_score_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "lia_lm_score": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p,
+                             c_void_p, c_void_p, c_void_p]),
+    "lia_llama_lm_score": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
     "lia_host_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                    c_int, c_int, c_int, c_int, c_int]),
     "lia_llama_pack_offsets": (c_int, [ctypes.POINTER(LlamaDesc), ctypes.POINTER(c_size_t * 9), ctypes.POINTER(c_size_t)]),
@@ -156,6 +163,16 @@ SIGNATURES = {
     "lia_tpp_unblock": (c_int, [c_void_p, c_void_p, c_int, c_int]),
     "lia_tpp_block": (c_int, [c_void_p, c_void_p, c_int, c_int]),
 }
+
+# the row kernel of lia_score.hip (lia_hip.h: LIA_SCORE_ROW_THREADS, LIA_SCORE_SERIAL, LIA_SCORE_MAX_CHUNK)
+SCORE_ROW_THREADS = 1024
+SCORE_MAX_CHUNK = 4096
+
+
+def score_serial_terms(vocab):
+    """terms of sum exp(l - m) one lane adds before the tree over the SCORE_ROW_THREADS lanes"""
+    return 8 * ((vocab + 8 * SCORE_ROW_THREADS - 1) // (8 * SCORE_ROW_THREADS))
+
 
 _lib = None
 

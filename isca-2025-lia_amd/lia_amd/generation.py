@@ -28,6 +28,10 @@ LIA_KWARGS = ("prefill_policy", "decoding_policy", "no_overlap", "pin_weight", "
               "enable_cxl")
 
 
+LLAMA_PADDING_REFUSAL = ("attention_mask with padding (zeros) is not supported for Llama-family models: their RoPE positions "
+                         "are not per row yet; pass equal-length prompts")
+
+
 def left_padding_starts(attention_mask, shape):
     """Validate a left-padded HF attention_mask of input_ids' shape [B, T] and return the per-row starts s_b (int32 [B]: row b
     is s_b zeros, then ones), or None when the mask is absent or all ones -- the unpadded route.  ValueError names the problem."""
@@ -97,8 +101,7 @@ def generate(model, input_ids, max_new_tokens=None, min_new_tokens=None, do_samp
     ids = torch.as_tensor(input_ids, dtype=torch.int64).cpu()
     starts = left_padding_starts(attention_mask, ids.shape) if ids.dim() == 2 else None
     if starts is not None and getattr(model, "family", "opt") == "llama":
-        raise ValueError("attention_mask with padding (zeros) is not supported for Llama-family models: their RoPE positions "
-                         "are not per row yet; pass equal-length prompts")
+        raise ValueError(LLAMA_PADDING_REFUSAL)
     sched = _scheduler_of(model)
     if sample is not None and ids.dim() == 2:
         hooks["sampler"] = _sampler(sched, ids.shape[0], max_new_tokens, sample, sample_seed)

@@ -192,10 +192,12 @@ class LlamaScheduler:
         self.hidden, self.resident, self.tables = HiddenPairs(model.shape.hidden), ResidentRun(model), None
         self.prefill_tail = True      # last layer of a prefill: last position only behind q|k|v (False: every position)
 
-    def _ensure(self, rows, B, T, n_gpu, smax):
+    def _ensure(self, rows, B, T, n_gpu, smax, score_rows=0):
         sh, lib = self.model.shape, N.lib()
         lm_bytes = 2 * 256 * sh.hidden + 8 * min(B, 256) * sh.vocab * 4 + (1 << 20)
         need = max(lib.lia_llama_workspace_bytes(ctypes.byref(self.model.desc), rows), lm_bytes)
+        if score_rows:       # a scoring pass: room for one chunk of lia_llama_lm_score (normed rows + bf16 logits)
+            need = max(need, lib.lia_lm_score_workspace_bytes(score_rows, sh.hidden, sh.vocab))
         if self.ctx is None or need > self.ctx.workspace_bytes:
             if self.pipe:
                 self.pipe.close()
@@ -216,6 +218,44 @@ class LlamaScheduler:
         m, sh = self.model, self.model.shape
         lib = N.lib()
         B, T = input_ids.shape
+        x, xlast = self._layers(input_ids, kv_state, gpu_percentage, num_minibatch, pin_weight, enable_cxl)
+        ctx = self.ctx
+        st = ctypes.c_void_p(ctx.stream)
+        logits = torch.empty((B, sh.vocab), dtype=torch.bfloat16, device="cuda")
+        nxt_ids = torch.empty((B,), dtype=torch.int64, device="cuda")
+        x_lm, T_lm = (x, T) if xlast is None else (xlast, 1)     # (the last layer already reduced the block to its last position)
+        N.check(lib.lia_llama_lm_head(ctx.handle, ctypes.c_void_p(x_lm.data_ptr()), B, T_lm, sh.hidden, ctypes.c_void_p(m.final_norm_w.data_ptr()),
+                                      ctypes.c_void_p(m.lm_head.data_ptr()), sh.vocab, sh.rms_eps, suppress_token,
+                                      ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(nxt_ids.data_ptr()), st), "lia_llama_lm_head")
+        if sampler is not None:
+            nxt_ids = sampler(ctx, logits, suppress_token)
+        ctx.synchronize()
+        kv_state.len += T
+        return logits, nxt_ids
+
+    def score(self, input_ids, kv_state, targets, gpu_percentage=100, num_minibatch=1, pin_weight=True, enable_cxl=False, **_ignored):
+        """One prefill-shaped pass over input_ids [B, T] (T > 1, an empty kv_state sized for T: scratch) -> (logprobs float32 [B, T],
+        greedy ids int64 [B, T]) on the device: log p(targets[b, t] | ids[b, :t + 1]) (targets int64 [B, T], -1 = none -> 0.0) and the
+        greedy token at t.  forward()'s prefill with the last layer on every position, then lia_llama_lm_score."""
+        m, sh = self.model, self.model.shape
+        B, T = input_ids.shape
+        if T < 2 or kv_state.len != 0:
+            raise ValueError(f"score: a prefill over at least two tokens on an empty cache (T={T}, cache length {kv_state.len})")
+        if tuple(targets.shape) != (B, T):
+            raise ValueError(f"score: targets has shape {tuple(targets.shape)}, input_ids {(B, T)}")
+        x, _ = self._layers(input_ids, kv_state, gpu_percentage, num_minibatch, pin_weight, enable_cxl, every_pos=True)
+        tgt_dev = targets.to(device="cuda", dtype=torch.int64).contiguous()
+        lp, greedy = self.ctx.llama_lm_score(x, m.final_norm_w, m.lm_head, tgt_dev, sh.rms_eps)
+        self.ctx.synchronize()
+        kv_state.len += T
+        return lp.view(B, T), greedy.view(B, T)
+
+    def _layers(self, input_ids, kv_state, gpu_percentage, num_minibatch, pin_weight, enable_cxl, every_pos=False):
+        """embedding and every decoder layer of one forward -> (hidden [B, T, H], the last layer's [B, 1, H] output when it computed the
+        last position only, else None).  every_pos (a scoring pass): the last layer computes every position."""
+        m, sh = self.model, self.model.shape
+        lib = N.lib()
+        B, T = input_ids.shape
         L = sh.layers
         n_gpu = L if gpu_percentage >= 100 else int(L * gpu_percentage / 100)
         minis = minibatch_bounds(B, num_minibatch) if T > 1 else [(0, B)]      # ragged last minibatch, num_minibatch clamped to B
@@ -223,7 +263,7 @@ class LlamaScheduler:
         if m.placed_for != (n_gpu, bool(pin_weight), bool(enable_cxl), LayerStore._fmt_of(self.pack)):
             self.resident.replaced(self.pipe)
         m.place(n_gpu, pin_weight, enable_cxl, self.pack)
-        x, y = self._ensure(mini * T, B, T, n_gpu, kv_state.smax)
+        x, y = self._ensure(mini * T, B, T, n_gpu, kv_state.smax, score_rows=B * T if every_pos else 0)
         ctx, pipe = self.ctx, self.pipe
         st = ctypes.c_void_p(ctx.stream)
         pos0 = kv_state.len
@@ -253,7 +293,7 @@ class LlamaScheduler:
             else:
                 w = pipe.acquire(idx)
                 pipe.prefetch_ahead(idx, stream_order(idx, n_gpu, L))
-            tail = self.prefill_tail and T > 1 and pos0 == 0 and idx == L - 1
+            tail = self.prefill_tail and not every_pos and T > 1 and pos0 == 0 and idx == L - 1
             if tail:
                 xlast = torch.empty((B, 1, sh.hidden), dtype=torch.bfloat16, device="cuda")
             fn = lib.lia_llama_layer_forward_last if tail else lib.lia_llama_layer_forward
@@ -266,17 +306,7 @@ class LlamaScheduler:
             if idx >= n_gpu:
                 pipe.release(idx)
             x, y = y, x
-        logits = torch.empty((B, sh.vocab), dtype=torch.bfloat16, device="cuda")
-        nxt_ids = torch.empty((B,), dtype=torch.int64, device="cuda")
-        x_lm, T_lm = (x, T) if xlast is None else (xlast, 1)     # (the last layer already reduced the block to its last position)
-        N.check(lib.lia_llama_lm_head(ctx.handle, ctypes.c_void_p(x_lm.data_ptr()), B, T_lm, sh.hidden, ctypes.c_void_p(m.final_norm_w.data_ptr()),
-                                      ctypes.c_void_p(m.lm_head.data_ptr()), sh.vocab, sh.rms_eps, suppress_token,
-                                      ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(nxt_ids.data_ptr()), st), "lia_llama_lm_head")
-        if sampler is not None:
-            nxt_ids = sampler(ctx, logits, suppress_token)
-        ctx.synchronize()
-        kv_state.len = pos0 + T
-        return logits, nxt_ids
+        return x, xlast
 
     def stream_stats(self, reset=False):
         return self.pipe.stats(reset) if self.pipe else (0.0, 0.0)

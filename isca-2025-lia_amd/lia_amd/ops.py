@@ -180,6 +180,57 @@ class Context:
                                     int(suppress_token), _ptr(uniforms), _ptr(nxt), _ptr(stats), self._st(stream)), "lia_sample")
         return nxt
 
+    def token_logprobs(self, logits, targets, stream=None):
+        """lia_token_logprobs: per row of logits [M, vocab] (bf16, rows may be strided) the log-probability of targets[r] (int64
+        [M], -1: none -> 0.0) under the row's softmax, and the row's greedy token (first maximal index).  Returns (float32 [M],
+        int64 [M]) on the device."""
+        if not logits.is_cuda or logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+            raise ValueError(f"logits: expected a [M, vocab] bf16 CUDA tensor with unit column stride, got {logits.dtype} {logits.device} "
+                             f"shape {tuple(logits.shape)} strides {logits.stride()}")
+        M, vocab = logits.shape
+        _chk(targets, torch.int64)
+        if targets.numel() != M:
+            raise ValueError(f"targets has {targets.numel()} entries, logits {M} rows")
+        lp = torch.empty((M,), dtype=torch.float32, device=logits.device)
+        gr = torch.empty((M,), dtype=torch.int64, device=logits.device)
+        N.check(self.lib.lia_token_logprobs(self.handle, _ptr(logits), logits.stride(0), M, vocab, _ptr(targets), _ptr(lp), _ptr(gr),
+                                            self._st(stream)), "lia_token_logprobs")
+        return lp, gr
+
+    def _score_args(self, hidden, targets):
+        _chk(hidden)
+        _chk(targets, torch.int64)
+        H = hidden.shape[-1]
+        M = hidden.numel() // H
+        if targets.numel() != M:
+            raise ValueError(f"targets has {targets.numel()} entries, hidden {M} rows")
+        lp = torch.empty((M,), dtype=torch.float32, device=hidden.device)
+        gr = torch.empty((M,), dtype=torch.int64, device=hidden.device)
+        return M, H, lp, gr
+
+    def lm_score(self, hidden, lnw, lnb, emb, targets, eps=1e-5, stream=None):
+        """lia_lm_score: final LN + tied lm_head on EVERY row of hidden [..., H], then token_logprobs against targets (int64, one per
+        row); the logits exist one workspace chunk at a time (score_chunk_rows).  Returns (float32 [M], int64 [M]) on the device."""
+        for t in (lnw, lnb, emb):
+            _chk(t)
+        M, H, lp, gr = self._score_args(hidden, targets)
+        N.check(self.lib.lia_lm_score(self.handle, _ptr(hidden), H, M, H, _ptr(lnw), _ptr(lnb), _ptr(emb), emb.shape[0], eps,
+                                      _ptr(targets), _ptr(lp), _ptr(gr), self._st(stream)), "lia_lm_score")
+        return lp, gr
+
+    def llama_lm_score(self, hidden, normw, lm, targets, eps=1e-5, stream=None):
+        """lia_llama_lm_score: lm_score with the final RMSNorm and the untied lm_head of a Llama"""
+        for t in (normw, lm):
+            _chk(t)
+        M, H, lp, gr = self._score_args(hidden, targets)
+        N.check(self.lib.lia_llama_lm_score(self.handle, _ptr(hidden), H, M, H, _ptr(normw), _ptr(lm), lm.shape[0], eps,
+                                            _ptr(targets), _ptr(lp), _ptr(gr), self._st(stream)), "lia_llama_lm_score")
+        return lp, gr
+
+    def score_chunk_rows(self, M, H, vocab):
+        """rows per chunk lm_score would use for M rows in this context's workspace (0: not even min(M, 256) rows fit)"""
+        return self.lib.lia_lm_score_chunk_rows(self.workspace_bytes, M, H, vocab)
+
     # ---- the operator boundary ------------------------------------------------------------------
     def layer_forward(self, desc, policy, weight_ptrs, x, y, kv, B, T, pos0, b0=0, stream=None):
         """weight_ptrs: (c_void_p * 16) of device pointers; kv: _native.KV.  x, y: [B,T,H] device."""

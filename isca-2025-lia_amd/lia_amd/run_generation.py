@@ -19,10 +19,57 @@ from .model import LiaOPTModel, resolve_shape
 from .scheduler import default_stream_format
 
 
-def build_parser():
-    p = argparse.ArgumentParser("Generation script (bf16 path, MI355X)", add_help=True)
+def add_model_args(p):
+    """the model flags every harness shares (run_generation, run_accuracy)"""
     p.add_argument("-m", "--model-id", type=str, default="facebook/opt-30b", help="OPT shape name or local HF checkpoint dir")
     p.add_argument("--dtype", type=str, choices=["bfloat16"], default="bfloat16")
+
+
+def add_lia_args(p):
+    """the seven LIA flags, same names / types / defaults as run.py:195-215 and run_generation.py:111-117"""
+    p.add_argument("--prefill-policy", default=1, type=int)
+    p.add_argument("--decoding-policy", default=1, type=int)
+    p.add_argument("--no-overlap", action="store_true")
+    p.add_argument("--pin-weight", action="store_true")
+    p.add_argument("--gpu-percentage", default=0, type=int)
+    p.add_argument("--num-minibatch", default=1, type=int)
+    p.add_argument("--enable-cxl", action="store_true")
+
+
+def add_stream_format_arg(p):
+    p.add_argument("--stream-format", default=None, choices=["raw", "pack10"],
+                   help="wire format of the pinned streamed layers: a lossless packed format (default pack10, or $LIA_STREAM_FORMAT; same "
+                        "results bit for bit, fewer bytes over the host link; layers that do not pack are pinned raw) or raw bf16 (what the "
+                        "reference ships); a model directory in the build's packed format defaults to the format on disk")
+
+
+def add_init_args(p):
+    p.add_argument("--seed", default=0, type=int)
+    p.add_argument("--init", default="normal", choices=["normal", "uniform01", "trained-like"],
+                   help="uniform01 = the reference's dummy-weight recipe (utils/opt-weight-gen.py:61-62)")
+
+
+def lia_kwargs_of(args):
+    """generate()'s / score()'s LIA kwargs of the command line"""
+    return dict(prefill_policy=args.prefill_policy, decoding_policy=args.decoding_policy, no_overlap=args.no_overlap,
+                pin_weight=args.pin_weight, gpu_percentage=args.gpu_percentage, num_minibatch=args.num_minibatch,
+                enable_cxl=args.enable_cxl)
+
+
+def attach_scheduler(model, stream_format):
+    """the scheduler generate() / score() drive, with the wire format the command line names"""
+    if getattr(model, "family", "opt") == "llama":
+        from .llama import LlamaScheduler
+        model._lia_scheduler = LlamaScheduler(model, pack=stream_format)
+    else:
+        from .scheduler import OffloadScheduler
+        model._lia_scheduler = OffloadScheduler(model, wire=stream_format)
+    return model._lia_scheduler
+
+
+def build_parser():
+    p = argparse.ArgumentParser("Generation script (bf16 path, MI355X)", add_help=True)
+    add_model_args(p)
     p.add_argument("--input-tokens", default="32", type=str)
     p.add_argument("--max-new-tokens", default=32, type=int)
     p.add_argument("--greedy", action="store_true")
@@ -40,19 +87,9 @@ def build_parser():
     p.add_argument("--profile", action="store_true",
                    help="one profiled generate() before the timed loop (run_generation.py:103,290-307 runs torch.profiler over five "
                         "there); here the library's own HIP-event brackets: GEMM time / rates per phase, host attention, link traffic")
-    # the seven LIA flags, same names / types / defaults as run.py:195-215 and run_generation.py:111-117
-    p.add_argument("--prefill-policy", default=1, type=int)
-    p.add_argument("--decoding-policy", default=1, type=int)
-    p.add_argument("--no-overlap", action="store_true")
-    p.add_argument("--pin-weight", action="store_true")
-    p.add_argument("--gpu-percentage", default=0, type=int)
-    p.add_argument("--num-minibatch", default=1, type=int)
-    p.add_argument("--enable-cxl", action="store_true")
+    add_lia_args(p)
     # build-specific
-    p.add_argument("--stream-format", default=None, choices=["raw", "pack10"],
-                   help="wire format of the pinned streamed layers: a lossless packed format (default pack10, or $LIA_STREAM_FORMAT; same "
-                        "results bit for bit, fewer bytes over the host link; layers that do not pack are pinned raw) or raw bf16 (what the "
-                        "reference ships); a model directory in the build's packed format defaults to the format on disk")
+    add_stream_format_arg(p)
     p.add_argument("--auto-plan", action="store_true",
                    help="measure this box (lia_amd.planner.calibrate, a few seconds) and let the planner choose --gpu-percentage, "
                         "the policies and --cpu-layers instead of the hand-picked values of llm/scripts/lia_*.sh")
@@ -77,9 +114,7 @@ def build_parser():
     p.add_argument("--top-k", default=50, type=int, help="with --do-sample; 0: off")
     p.add_argument("--top-p", default=1.0, type=float, help="with --do-sample; 1: off")
     p.add_argument("--sample-seed", default=0, type=int, help="with --do-sample: the seed of the generation's uniforms")
-    p.add_argument("--seed", default=0, type=int)
-    p.add_argument("--init", default="normal", choices=["normal", "uniform01", "trained-like"],
-                   help="uniform01 = the reference's dummy-weight recipe (utils/opt-weight-gen.py:61-62)")
+    add_init_args(p)
     return p
 
 
@@ -501,18 +536,12 @@ def _main(args, rec=None):
         rec["_mem_samples"].append(_hi.cgroup_memory()["current"])
     if args.stream_format is None:
         args.stream_format = default_stream_format()
-    from .scheduler import OffloadScheduler
+    attach_scheduler(model, args.stream_format)                                     # generate() drives this scheduler
     if getattr(model, "family", "opt") == "llama":
-        from .llama import LlamaScheduler
-        model._lia_scheduler = LlamaScheduler(model, pack=args.stream_format)
         print(f"note: {model.shape.name} is a Llama: --prefill-policy / --decoding-policy have no counterpart (decoder.py:121-169); "
               f"gpu% {args.gpu_percentage} of the layers resident, the others streamed, every layer computed on the GPU")
-    else:
-        model._lia_scheduler = OffloadScheduler(model, wire=args.stream_format)     # generate() drives this scheduler
     generate_kwargs = dict(do_sample=False, num_beams=1, max_new_tokens=args.max_new_tokens, min_new_tokens=args.max_new_tokens,
-                           token_latency=args.token_latency, prefill_policy=args.prefill_policy,
-                           decoding_policy=args.decoding_policy, no_overlap=args.no_overlap, pin_weight=args.pin_weight,
-                           gpu_percentage=args.gpu_percentage, num_minibatch=args.num_minibatch, enable_cxl=args.enable_cxl)
+                           token_latency=args.token_latency, **lia_kwargs_of(args))
     generate_kwargs.update(sampling_kwargs(args))
     if args.cpu_layers:
         generate_kwargs["cpu_layers"] = args.cpu_layers

@@ -135,11 +135,14 @@ class OffloadScheduler:
         self.host.time = value
 
     # -- resources -----------------------------------------------------------------------------------
-    def _ensure(self, rows, B, T, n_gpu):
-        """Context workspace (sized by the largest layer call seen so far), streamer slots, hidden buffers."""
+    def _ensure(self, rows, B, T, n_gpu, score_rows=0):
+        """Context workspace (sized by the largest layer call seen so far), streamer slots, hidden buffers.  score_rows: a scoring
+        pass also needs room for one chunk of lm_score (its normed rows and bf16 logits, lia_lm_score_workspace_bytes)."""
         sh = self.model.shape
         lm_bytes = 2 * 256 * sh.hidden + 8 * min(B, 256) * sh.vocab * 4 + (1 << 20)
         need = max(ops.workspace_bytes(self.model.desc, rows), lm_bytes)
+        if score_rows:
+            need = max(need, N.lib().lia_lm_score_workspace_bytes(score_rows, sh.hidden, sh.vocab))
         if self.ctx is None or need > self.ctx.workspace_bytes:
             if self.pipe is not None:
                 self.pipe.close()
@@ -244,6 +247,35 @@ class OffloadScheduler:
         self._deliver(s, kv_state)
         return logits, nxt
 
+    def score(self, input_ids, kv_state, targets, prefill_policy=1, decoding_policy=1, no_overlap=False, pin_weight=False,
+              gpu_percentage=0, num_minibatch=1, enable_cxl=False, **_decode_only):
+        """One prefill-shaped pass over input_ids [B, T] (T > 1, an empty kv_state sized for T: the caches are scratch) that returns
+        (logprobs float32 [B, T], greedy ids int64 [B, T]) on the device: entry [b, t] is log p(targets[b, t] | ids[b, :t + 1]) and
+        the greedy token at position t (targets: int64 [B, T], -1 = none -> 0.0).  The phases are forward()'s, with the last layer
+        computing EVERY position for this call and lm_score in place of lm_head.  A policy-0 pass keeps the streamed layers' K/V
+        in the HBM holding caches and SKIPS their delivery to the host caches: nothing is outstanding when the call returns.
+        Decode-only flags (decoding_policy, cpu_layers, ...) are accepted and have no effect beyond naming where the cache lives
+        (policy 3 wants 3 for both, as in forward)."""
+        B, T = input_ids.shape
+        if T < 2 or kv_state.len != 0:
+            raise ValueError(f"score: a prefill over at least two tokens on an empty cache (T={T}, cache length {kv_state.len})")
+        if tuple(targets.shape) != (B, T):
+            raise ValueError(f"score: targets has shape {tuple(targets.shape)}, input_ids {(B, T)}")
+        s = self._validate(input_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch)
+        s.every_pos = True
+        self._place(s, kv_state, pin_weight, enable_cxl, None, 0, None)
+        m, sh, ctx = self.model, self.model.shape, self.ctx
+        ids_dev = input_ids.to("cuda", non_blocking=False).contiguous()
+        tgt_dev = targets.to(device="cuda", dtype=torch.int64).contiguous()
+        ctx.embed_into(ids_dev, m.embed_tokens, m.embed_positions, s.x, s.pos0, starts=self._key_starts_for(s.B)[1])
+        if s.on_host:
+            hidden = self._host_layers(s.x, kv_state, s.n_gpu, s.B, s.T, s.pos0)
+        else:
+            hidden = self._run_layers(s, kv_state)
+        lp, greedy = ctx.lm_score(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, tgt_dev, sh.ln_eps)
+        self._deliver(s, kv_state)
+        return lp.view(B, T), greedy.view(B, T)
+
     # -- left-padded batches (generation.generate(..., attention_mask=)) -----------------------------------------------------
     def set_key_starts(self, starts):
         """starts: int32 [B] (row b's first real cache position) for every forward until the next call, or None: the unpadded
@@ -304,6 +336,7 @@ class OffloadScheduler:
                                decoding_policy=decoding_policy, gpu_percentage=gpu_percentage, mini=mini, minis=minis, overlap=not no_overlap,
                                pos0=kv_state.len, coop=None, cpu_set=frozenset(), host_act=frozenset(), host_now=frozenset(),
                                t_fwd0=None, busy0=0.0, hold=None, x=None, y=None,
+                               every_pos=False,                          # a scoring pass (score): no last-position-only last layer, no K/V delivery
                                on_host=(policy == 1 and n_gpu < L))      # policy 1: the streamed layers run on the host cores (_host_layers)
 
     def _place(self, s, kv_state, pin_weight, enable_cxl, max_new_tokens, cpu_layers, cpu_layers_start):
@@ -351,7 +384,7 @@ class OffloadScheduler:
             # prefill sized the workspace for batch x max positions rows: 60 GB of HBM at batch 1050 x 288 positions, which is
             # what ran the planner's batch-1050 pick out of memory; the reference's scripts never use decode policy 0.)
             rows = max(rows, s.mini * kv_state.smax)
-        s.x, s.y = self._ensure(rows, B, T, n_gpu)
+        s.x, s.y = self._ensure(rows, B, T, n_gpu, score_rows=B * T if s.every_pos else 0)
         if is_prefill and s.policy == 0 and n_gpu < L and self.defer_kv and s.pos0 == 0:
             self._await_all_deliveries()          # (host-blocking: afterwards nothing on the D2H stream reads the holding caches)
             s.hold = self._hold_caches(B, T, n_gpu)
@@ -365,7 +398,7 @@ class OffloadScheduler:
         if n_gpu < L and overlap:
             pipe.prefetch(n_gpu)                                   # no-op if the previous step already wrapped to it
         # the prefill's last layer: only hidden[:, -1, :] feeds lm_head (models.py:424-431), its K/V of every position feed decode
-        tail_last = self.prefill_tail and is_prefill and T > 1 and pos0 == 0 and (policy in (0, 3) or n_gpu == L) and (L - 1) not in host_now
+        tail_last = self.prefill_tail and not s.every_pos and is_prefill and T > 1 and pos0 == 0 and (policy in (0, 3) or n_gpu == L) and (L - 1) not in host_now
         xlast = None
         first = 0
         if not is_prefill and n_gpu > 0:
@@ -432,6 +465,8 @@ class OffloadScheduler:
         B, T, L, n_gpu, hold = s.B, s.T, s.L, s.n_gpu, s.hold
         if s.on_host:
             ctx.synchronize()                     # policy 1: nothing was delivered, the host layers wrote their caches themselves
+        elif hold is not None and s.every_pos:
+            ctx.synchronize()                     # a scoring pass: the K/V in the holding caches were scratch, nothing is delivered
         elif hold is not None:
             # the deferred deliveries, in the order the first decode step will need them; tickets are awaited per layer there
             self._await_kv(kv_state)              # (a KVState reused for a second prefill: never drop a ticket unawaited)
