@@ -164,7 +164,7 @@ def silu_mul(g, u):
     return bits(rnd(s * f64(u)))                                                    # rounding 2: . * up
 
 
-def attention(q, kc, vc, S, heads, kv_heads, post_scale, b0=0, mask_shift=0, kv_head_of=None, round_qk=True):
+def attention(q, kc, vc, S, heads, kv_heads, post_scale, b0=0, mask_shift=0, kv_head_of=None, round_qk=True, round_p=True):
     """Causal attention of T query rows per batch row at positions S - T .. S - 1 against cache rows 0 .. S - 1.
 
     q [B, T, heads * d]; kc / vc the seq-major cache [Smax, Bc, kv_heads, d], batch rows b0 .. b0 + B - 1 read.  Query head hh
@@ -174,7 +174,7 @@ def attention(q, kc, vc, S, heads, kv_heads, post_scale, b0=0, mask_shift=0, kv_
         causal mask: key j visible to query t iff j <= S - T + t, the others -inf
         p = bf16(softmax(s))      o = bf16(p . v)
     Mutants: mask_shift (the mask off by that many keys), kv_head_of (another head map: hh -> K / V head), round_qk=False (the
-    rounding of the raw product dropped)."""
+    rounding of the raw product dropped), round_p=False (P not rounded to bf16)."""
     B, T, HD = q.shape
     d = HD // heads
     G = heads // kv_heads
@@ -192,7 +192,9 @@ def attention(q, kc, vc, S, heads, kv_heads, post_scale, b0=0, mask_shift=0, kv_
     visible = np.arange(S)[None, :] <= (S - T + np.arange(T) + mask_shift)[:, None]
     s = np.where(visible, s, -np.inf)
     e = np.exp(s - s.max(axis=-1, keepdims=True))
-    p = rnd(e / e.sum(axis=-1, keepdims=True))
+    p = e / e.sum(axis=-1, keepdims=True)
+    if round_p:
+        p = rnd(p)
     o = rnd(p @ vf)                                                                 # [B, h, T, d]
     return bits(o.transpose(0, 2, 1, 3).reshape(B, T, HD))
 

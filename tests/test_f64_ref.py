@@ -87,6 +87,21 @@ def test_attention_llama_scaling_matches_oracle(oracle, B, T, S, heads, kvh, d):
           f"attention (Llama) {B}x{T}/{S}x{heads}/{kvh}x{d}")
 
 
+@pytest.mark.parametrize("B,T,S,heads,kvh", [(2, 257, 257, 4, 2), (32, 1, 1037, 8, 2)])
+@pytest.mark.parametrize("d", (32, 64, 128))
+@pytest.mark.parametrize("family", ("exact", "ramp", "fall", "sink", "uniform", "hot"))
+def test_attention_matches_oracle_on_the_families(oracle, family, d, B, T, S, heads, kvh):
+    """the sink / ramp / one-hot / uniform inputs of attn_families.py (scores in the hundreds, exp underflowing for most keys):
+    f64_ref.attention against the oracle's GPU-branch restatements, OPT scaling (kv_heads == heads) and Llama scaling (grouped)"""
+    import attn_families as F
+    q, kc, vc = F.make(family, B, T, S, heads, heads, d, 0)
+    agree(R.attention(q, kc, vc, S, heads, heads, post_scale=0), oracle.attention(q, kc, vc, S, heads, policy_gpu=True, causal=True),
+          f"attention (OPT) {family} {B}x{T}/{S}x{heads}x{d}")
+    q, kc, vc = F.make(family, B, T, S, heads, kvh, d, 1)
+    agree(R.attention(q, kc, vc, S, heads, kvh, post_scale=1), oracle.attention_gqa(q, kc, vc, S, heads, kvh),
+          f"attention (Llama) {family} {B}x{T}/{S}x{heads}/{kvh}x{d}")
+
+
 def test_argmax_takes_the_first_maximum_and_skips_the_suppressed_token():
     x = rand_bits(70, (4, 50), 1.0)
     x[1, [3, 17]] = x[1, 40] = synth.f32_to_bf16_bits(np.float32([9.0]))[0]
