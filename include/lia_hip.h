@@ -114,21 +114,28 @@ typedef struct {
  *   policy 0 : everything on the GPU, K/V rows delivered to a HOST cache (prefill: rows [0,T) of batch
  *              rows [b0, b0+B) via the context's D2H stream; completion = lia_ctx_kv_store_wait)
  *   policy 3 : everything on the GPU, cache on the device (resident layers)
- *   policy 2 : LN + linears on the GPU, attention on the host over the host cache (decode only)
+ *   policy 2 : LN + linears on the GPU, attention on the host over the host cache (decode, or a block of T > 1
+ *              tokens appended at pos0 > 0: q, k, v of the B x T rows make the round trip)
  *   policy 1 : not a GPU policy -- LIA_ERR_INVALID (the all-CPU path lives in lia_host_*)
  *
  * weights[16]: DEVICE pointers (resident copy or a streamer slot).  x, y: device [B, T, H], may not
  * alias.  pos0 = tokens already in the cache; rows pos0..pos0+T-1 are written, 0..pos0+T-1 attended
  * (causal inside the new block).  b0 = first cache batch row served by this call (minibatch offset,
  * modeling_opt.py:1283-1339).  Asynchronous on `stream` except policy 2, which blocks the caller while
- * the host attends. */
+ * the host attends.
+ * T > 1 at pos0 > 0 appends a block to a live cache (build-defined: a follow-up turn, a continuation to score): policy 3
+ * scatters the block's K/V behind the cached rows and runs the append attention kernels (lia_attn_append_launch: query t at
+ * position pos0 + t sees keys 0 .. pos0 + t) over the device cache; policy 0 pulls the pos0 cached rows of the served batch rows
+ * into its slab -- (pos0 + T) x B rows, LIA_ERR_MEMORY before any launch when the workspace cannot hold them --, attends there
+ * and delivers rows pos0 .. pos0 + T - 1 to the host cache (completion = lia_ctx_kv_store_wait). */
 int lia_layer_forward(lia_ctx* ctx, const lia_layer_desc* d, int policy, const void* const weights[16],
                       const lia_bf16* x, lia_bf16* y, lia_kv* kv, int B, int T, int pos0, int b0, void* stream);
 /* The LAST decoder layer of a prefill (build-defined; the reference computes every position of every layer, decoder.py:172-335):
  * only hidden[:, -1, :] of the last layer feeds the final LayerNorm and lm_head (models.py:424-431), but its K/V rows of EVERY
  * position feed the decode steps.  So: LN1 and the q | k | v projection on all B x T rows (cache written exactly as by
  * lia_layer_forward), then attention -- one query per row over the T keys --, out-proj, LN2, fc1 and fc2 on the last position
- * of each row only.  y_last: device [B, 1, H].  policy 0 or 3, T > 1, pos0 == 0.  Saves 9/12 of the layer's GEMM flops. */
+ * of each row only.  y_last: device [B, 1, H].  policy 0 or 3, T > 1, any pos0 (the last query attends the pos0 + T keys through the decode kernel).  Saves 9/12 of the layer's
+ * GEMM flops. */
 int lia_layer_forward_last(lia_ctx* ctx, const lia_layer_desc* d, int policy, const void* const weights[16],
                            const lia_bf16* x, lia_bf16* y_last, lia_kv* kv, int B, int T, int pos0, int b0, void* stream);
 /* dst / src: device memory or pinned (mapped) host memory; bytes % 16 == 0; asynchronous on `stream`.  Kernel copy used for
@@ -180,7 +187,8 @@ int lia_embed(const int64_t* ids, const lia_bf16* tok, const lia_bf16* pos, lia_
  * pad position (i < s_b) gives a zero row.  Its GPU branch drops the mask (attentions.py:444-449, modeling_opt.py:1434,1469).
  * lia_ctx_set_key_starts: the table of s_b per cache batch row (host pointer, n_rows entries >= 0; NULL or 0 clears it).  The
  * context keeps a host copy and a device copy; lia_layer_forward, lia_layer_forward_last and lia_decode_layers then serve rows
- * b0 .. b0 + B - 1 through the padded attention (GPU policies and the policy-2 host attention); each s_b must be <= pos0 + T - 1.
+ * b0 .. b0 + B - 1 through the padded attention (GPU policies and the policy-2 host attention); each s_b must be <= pos0 + T - 1,
+ * and <= pos0 for a block of T > 1 tokens appended at pos0 > 0 (an appended block has no pad query rows).
  * Without a table they take the unpadded route, unchanged.
  * lia_embed_padded: position p - s_b + 2 for the token at cache position p = past_len + t >= s_b, position 1 at a pad position.
  * lia_attention_padded: lia_attention with the starts of the served rows.  starts: DEVICE pointers, B entries (row b <-> b0 + b). */
@@ -257,7 +265,7 @@ int lia_llama_layer_forward(lia_ctx* ctx, const lia_llama_desc* d, const void* c
                             lia_kv* kv, const lia_bf16* cos_table, const lia_bf16* sin_table, int B, int T, int pos0, int b0,
                             void* stream);
 /* the Llama counterpart of lia_layer_forward_last: the LAST layer of a prefill -- norm, q | k | v projection and RoPE on every row
- * (the cache holds every position), attention / o / MLP on the last position of each row; y_last: [B, 1, H]; T > 1, pos0 == 0 */
+ * (the cache holds every position), attention / o / MLP on the last position of each row; y_last: [B, 1, H]; T > 1, any pos0 */
 int lia_llama_layer_forward_last(lia_ctx* ctx, const lia_llama_desc* d, const void* const weights[9], const lia_bf16* x,
                                  lia_bf16* y_last, lia_kv* kv, const lia_bf16* cos_table, const lia_bf16* sin_table, int B, int T,
                                  int pos0, int b0, void* stream);

@@ -36,6 +36,9 @@ extern "C" int lia_attn_prefill_launch(const bf16_t* q, long ldq, const bf16_t* 
 extern "C" int lia_attn_prefill_padded_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
                                               int B, int T, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
                                               const int* starts, hipStream_t st);
+extern "C" int lia_attn_append_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T,
+                                      int pos0, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts,
+                                      hipStream_t st);
 extern "C" int lia_attn_decode_padded_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
                                              int B, int S, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
                                              const int* starts, hipStream_t st);
@@ -688,7 +691,6 @@ static int layer_forward_impl(lia_ctx* ctx, const lia_layer_desc* d, int policy,
     lia_set_error("lia_layer_forward: B=%d T=%d pos0=%d b0=%d vs cache batch=%d smax=%d", B, T, pos0, b0, kv->batch, kv->smax);
     return LIA_ERR_INVALID;
   }
-  if (T > 1 && pos0 != 0) { lia_set_error("lia_layer_forward: multi-token call must be a prefill (pos0 == 0)"); return LIA_ERR_INVALID; }
   if (tail && (policy == 2 || T < 2)) { lia_set_error("lia_layer_forward_last: a GPU-attention prefill (policy 0 / 3, T > 1) only"); return LIA_ERR_INVALID; }
   if ((policy == 3) != (kv->on_device != 0)) {
     lia_set_error("lia_layer_forward: policy %d needs a %s cache", policy, policy == 3 ? "device" : "host");
@@ -710,10 +712,18 @@ static int layer_forward_impl(lia_ctx* ctx, const lia_layer_desc* d, int policy,
         lia_set_error("lia_layer_forward: row %d starts at %d, beyond its last position %d", b0 + b, kst_host[b], pos0 + T - 1);
         return LIA_ERR_INVALID;
       }
+    // a block appended to a non-empty cache has no pad query rows: every row's sequence began at or before the block
+    if (T > 1 && pos0 > 0)
+      for (int b = 0; b < B; ++b)
+        if (kst_host[b] > pos0) {
+          lia_set_error("lia_layer_forward: row %d starts at %d, inside the block appended at %d", b0 + b, kst_host[b], pos0);
+          return LIA_ERR_INVALID;
+        }
   }
   const int H = d->hidden, F = d->ffn, hd = H / d->heads;
   const long M = (long)B * T;
-  // policy-0 decode parks the whole cached prefix [pos0+1][B][H] (K and V) in a slab
+  // policy 0 on a non-empty cache (a decode step, an appended block) parks the cached prefix and the call's rows, [pos0+T][B][H]
+  // (K and V), in a slab
   const WsLayout w = ws_layout(d, M, policy == 0 ? (long)(pos0 + T) * B : M);
   if (w.total > ctx->ws_bytes) {
     lia_set_error("lia_layer_forward: workspace %zu < %zu needed for %ld rows", ctx->ws_bytes, w.total, M);
@@ -813,8 +823,11 @@ static int layer_forward_impl(lia_ctx* ctx, const lia_layer_desc* d, int policy,
   } else {
     // GPU attention (attentions.py:443-536)
     // (tail: the last query of a causal block attends every key -- one decode-style query per row over the S rows just written)
+    // (a block of T > 1 queries behind pos0 > 0 cached positions: the append kernels, query frame offset from the key frame)
     int arc;
-    if (kst_dev)
+    if (T > 1 && pos0 > 0 && !tail)
+      arc = lia_attn_append_launch(qb, H, kdst, vdst, ao, H, B, T, pos0, d->heads, d->heads, hd, dst_batch, dst_b0, 0, kst_dev, st);
+    else if (kst_dev)
       arc = (T == 1 || tail) ? lia_attn_decode_padded_launch(qb + tail_off, tail_ld, kdst, vdst, ao, H, B, (int)S, d->heads, d->heads, hd, dst_batch, dst_b0, 0, kst_dev, st)
                              : lia_attn_prefill_padded_launch(qb, H, kdst, vdst, ao, H, B, T, d->heads, d->heads, hd, dst_batch, dst_b0, 0, kst_dev, st);
     else
@@ -955,7 +968,7 @@ static int llama_layer_forward_impl(lia_ctx* ctx, const lia_llama_desc* d, const
   for (int i = 0; i < 9; ++i)
     if (!weights[i]) { lia_set_error("lia_llama_layer_forward: weights[%d] is NULL", i); return LIA_ERR_MISSING; }
   if (!kv->on_device) { lia_set_error("lia_llama_layer_forward: the KV cache must live on the device"); return LIA_ERR_INVALID; }
-  if (B <= 0 || T <= 0 || pos0 < 0 || b0 < 0 || b0 + B > kv->batch || pos0 + T > kv->smax || (T > 1 && pos0 != 0)) {
+  if (B <= 0 || T <= 0 || pos0 < 0 || b0 < 0 || b0 + B > kv->batch || pos0 + T > kv->smax) {
     lia_set_error("lia_llama_layer_forward: B=%d T=%d pos0=%d b0=%d vs cache batch=%d smax=%d", B, T, pos0, b0, kv->batch, kv->smax);
     return LIA_ERR_INVALID;
   }
@@ -1024,6 +1037,7 @@ static int llama_layer_forward_impl(lia_ctx* ctx, const lia_llama_desc* d, const
     }
   }
   int arc = (T == 1 || tail) ? lia_attn_decode_launch(qb + tail_off, tail_ld, kv->k, kv->v, ao, H, B, pos0 + T, d->heads, d->kv_heads, hd, kv->batch, b0, 1, st)
+            : pos0 > 0       ? lia_attn_append_launch(qb, H, kv->k, kv->v, ao, H, B, T, pos0, d->heads, d->kv_heads, hd, kv->batch, b0, 1, nullptr, st)
                              : lia_attn_prefill_launch(qb, H, kv->k, kv->v, ao, H, B, T, d->heads, d->kv_heads, hd, kv->batch, b0, 1, st);
   if (arc) { lia_set_error("llama attention: unsupported head_dim %d / S %d", hd, pos0 + T); return LIA_ERR_INVALID; }
   int norm2_done = 0, silu_done = 0;

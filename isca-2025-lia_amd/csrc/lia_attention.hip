@@ -32,11 +32,25 @@
 // key tiles aligned to kstart (every tile wholly before kstart is never visited, no key needs a lower mask) -- and write query rows
 // 0 .. kstart - 1 as zeros without any K / V work.  A real row's result is bit for bit that of the same row unpadded.
 // starts: per served row b (the caller passes its table + b0); PADDED = 0 never reads it
-template <int D, int PADDED>
+//
+// Append (APPEND = 1): a block of Tq queries at cache positions pos0 .. pos0 + Tq - 1 over the keys kstart .. pos0 + Tq - 1 already in the
+// cache.  The key frame starts at kstart as above, the query frame at pos0: query i of the block sits at frame position qoff + i,
+// qoff = pos0 - kstart >= 0, and sees keys j <= qoff + i; q / out hold the block's rows only ([B][Tq], no pad query rows).  Key blocks
+// stay aligned to kstart and a row's sums run over them in the same order with the same operations, and a block a row sees nothing of
+// changes neither its maximum nor its sum nor its output (exp(-inf) = 0, P = 0) -- so a row's result is bit for bit that of the same
+// row in a prefill over pos0 + Tq tokens.  APPEND = 0: qoff folds to 0 and Tq to the frame's T -- the code above, unchanged.
+// One kernel template serves both: Pos0 is empty for the prefill (the kernel's parameters and code are then exactly those it had
+// before the append block existed -- a wrapper around a shared body moved its SGPR allocation) and one int, pos0, for the append.
+__device__ __forceinline__ int lia_pos0_of() { return 0; }
+__device__ __forceinline__ int lia_pos0_of(int pos0) { return pos0; }
+template <int D, int PADDED, typename... Pos0>
 __global__ __launch_bounds__(256) void lia_attn_prefill_kernel(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ kc,
                                                                 const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int Tp,
                                                                 int heads, int kv_heads, int Bc, int b0, float scaling, int post_scale,
-                                                                const int* __restrict__ starts) {
+                                                                const int* __restrict__ starts, Pos0... pos0_arg) {
+  constexpr int APPEND = sizeof...(Pos0);
+  static_assert(APPEND <= 1, "Pos0: nothing (prefill) or pos0 (append)");
+  const int pos0 = lia_pos0_of(pos0_arg...);
   constexpr int CH = D / 8;              // 16-byte chunks per K row
   constexpr int RPB = 16 / CH;           // K rows per 256-byte LDS bank row
   constexpr int KSTEPS = D / 16;         // MFMA k-steps over d for S^T
@@ -50,9 +64,11 @@ __global__ __launch_bounds__(256) void lia_attn_prefill_kernel(const bf16_t* __r
   const int hh = blockIdx.y, b = blockIdx.z;
   // Tp: the batch rows' pitch in q / out (tokens per row); T: the row's tokens from its start kstart on (the shifted frame, see above)
   const int kstart = PADDED ? __builtin_amdgcn_readfirstlane(starts[b]) : 0;   // (uniform: keeps the row start scalar)
-  const int T = Tp - kstart;
-  const int nqblk = PADDED ? (T + 127) / 128 : (int)gridDim.x;   // query blocks of the row
-  if (PADDED) {
+  const int T = (APPEND ? pos0 + Tp : Tp) - kstart;               // keys of the frame
+  const int Tq = APPEND ? Tp : T;                                // queries: the block's (append) or the frame's
+  const int qoff = APPEND ? pos0 - kstart : 0;                   // frame position of query 0
+  const int nqblk = (PADDED && !APPEND) ? (T + 127) / 128 : (int)gridDim.x;   // query blocks of the row
+  if (PADDED && !APPEND) {
     // pad query rows of this workgroup's 128 (unshifted) rows: zeros
     for (int idx = tid; idx < 128 * (D / 4); idx += 256) {
       const int row = (int)blockIdx.x * 128 + idx / (D / 4);
@@ -77,8 +93,8 @@ __global__ __launch_bounds__(256) void lia_attn_prefill_kernel(const bf16_t* __r
   // Qs fragments: B operand, lane holds Qs[q_wave + r][16 s + 8 h + j]
   bf16x8 qf[KSTEPS];
   {
-    const int qrow = min(q_wave + r, T - 1);
-    const bf16_t* qp = q + ((long)b * Tp + kstart + qrow) * ldq + (long)hh * D;
+    const int qrow = min(q_wave + r, Tq - 1);
+    const bf16_t* qp = q + ((long)b * Tp + (APPEND ? 0 : kstart) + qrow) * ldq + (long)hh * D;
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) {
 #ifdef P3X_NO_QLOAD
@@ -94,8 +110,9 @@ __global__ __launch_bounds__(256) void lia_attn_prefill_kernel(const bf16_t* __r
     }
   }
 
-  const int n_tiles_wg = min((q_wg + 128 + 31) / 32, (T + 31) / 32);  // causal: keys <= last query of the WG
-  const int my_q = q_wave + r;                                        // this lane's query (column of S^T)
+  const int n_tiles_wg = min((qoff + q_wg + 128 + 31) / 32, (T + 31) / 32);  // causal: keys <= last query of the WG
+  const int my_row = q_wave + r;                                      // this lane's query within q / out ...
+  const int my_q = qoff + my_row;                                     // ... and its frame position (column of S^T); prefill: the same
 
   auto stage_k = [&](int kt) {
     // 32 keys x D: thread -> (key = tid / CH', chunk); 256 threads move 4 KB per round
@@ -153,7 +170,7 @@ __global__ __launch_bounds__(256) void lia_attn_prefill_kernel(const bf16_t* __r
     __syncthreads();
     stage_k(kt);
     __syncthreads();
-    if (kt * 32 <= q_wave + 31) {  // wave-uniform: tile not entirely above the diagonal
+    if (kt * 32 <= qoff + q_wave + 31) {  // wave-uniform: tile not entirely above the diagonal
       f32x16 s;
       scores(kt, s);
       float tm = s[0];
@@ -182,7 +199,7 @@ __global__ __launch_bounds__(256) void lia_attn_prefill_kernel(const bf16_t* __r
     stage_k(kt);
     stage_vt(kt);
     __syncthreads();
-    if (kt * 32 <= q_wave + 31) {
+    if (kt * 32 <= qoff + q_wave + 31) {
       f32x16 s;
       scores(kt, s);
       uint32_t pk[8];
@@ -204,8 +221,8 @@ __global__ __launch_bounds__(256) void lia_attn_prefill_kernel(const bf16_t* __r
   }
   (void)inv_l;
 
-  if (my_q < T) {
-    bf16_t* op = out + ((long)b * Tp + kstart + my_q) * ldo + (long)hh * D;
+  if (my_row < Tq) {
+    bf16_t* op = out + ((long)b * Tp + (APPEND ? 0 : kstart) + my_row) * ldo + (long)hh * D;
 #pragma unroll
     for (int d = 0; d < DB; ++d)
 #pragma unroll
@@ -217,6 +234,7 @@ __global__ __launch_bounds__(256) void lia_attn_prefill_kernel(const bf16_t* __r
       }
   }
 }
+
 
 // ---------------------------------------------------------------------------------------------
 // prefill, d = 128, third generation (r05).  The arithmetic -- every product, rounding, max / sum update and its order -- is that
@@ -315,9 +333,13 @@ __device__ __forceinline__ uint2 p3_prob4(f32x4 r, float m, float l, float rl) {
   return uint2{p3_cvt_pk(q.x, q.y), p3_cvt_pk(q.z, q.w)};
 }
 
-template <int POST_SCALE, int PADDED>
+// APPEND = 1: Tp queries at cache positions pos0 .. pos0 + Tp - 1 over the keys kstart .. pos0 + Tp - 1 (the frames of
+// lia_attn_prefill_kernel: keys from kstart, queries from qoff = pos0 - kstart); q / out hold the block's rows only.  Staging, barriers,
+// order, pairing and the output path are the prefill's.  The mirror pairing still balances: block bx visits ~(qoff + 128 (bx + 1)) / 64
+// tiles -- a rectangle of qoff keys plus the triangle -- so cost(bx) + cost(nqb_all - 1 - bx) is the same for every pair.
+template <int POST_SCALE, int PADDED, int APPEND>
 __device__ __forceinline__ void lia_attn_prefill128_body(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ kc,
-                                                         const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int Tp,
+                                                         const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int Tp, int pos0,
                                                          int heads, int kv_heads, long kv_row, long kv_batch, int b0, float scaling,
                                                          int nqb, int n_groups, const int* __restrict__ starts) {
   constexpr int D = 128;
@@ -358,16 +380,18 @@ __device__ __forceinline__ void lia_attn_prefill128_body(const bf16_t* __restric
   // workgroup of a sequence costs the same (causal: 1 + ... keys), half as many workgroups are launched and drained -- the
   // launches alone were 75 us of the 313 us of OPT-30B's T = 256 launch (the kernel without loads, arithmetic and stores,
   // LABNOTES r06) -- and the second block's K / V tiles were just read by the first.
-  // PADDED: the row's T - kstart tokens from its start kstart on form the sequence (the shifted frame of lia_attn_prefill_body); its
+  // PADDED: the row's T - kstart tokens from its start kstart on form the sequence (the shifted frame of lia_attn_prefill_kernel); its
   // nqa query blocks are dealt to the first nqr workgroups of the row by the same pairing, Tp is the rows' pitch in q / out.
   // (With padding the pairs of one launch no longer cost the same: rows with later starts finish early.)
   const int kstart = PADDED ? __builtin_amdgcn_readfirstlane(starts[b]) : 0;   // (uniform: keeps the row start scalar)
-  const int T = Tp - kstart;
+  const int T = (APPEND ? pos0 + Tp : Tp) - kstart;               // keys of the frame
+  const int Tq = APPEND ? Tp : T;                                // queries: the block's (append, no pad rows) or the frame's
+  const int qoff = APPEND ? pos0 - kstart : 0;                   // frame position of query 0
   const int nqb_all = (Tp + 127) >> 7;
   const bool pairs = nqb != nqb_all;
-  const int nqa = PADDED ? (T + 127) >> 7 : nqb_all;
-  const int nqr = PADDED ? (pairs ? (nqa + 1) >> 1 : nqa) : nqb;
-  if (PADDED) {
+  const int nqa = (PADDED && !APPEND) ? (T + 127) >> 7 : nqb_all;
+  const int nqr = (PADDED && !APPEND) ? (pairs ? (nqa + 1) >> 1 : nqa) : nqb;
+  if (PADDED && !APPEND) {
     // pad query rows of the (unshifted) blocks this workgroup is dealt -- bx and, with pairs, its mirror: zeros, no K / V work
     for (int k = 0; k < (pairs ? 2 : 1); ++k) {
       const int ob = k ? nqb_all - 1 - bx : bx;
@@ -452,8 +476,8 @@ __device__ __forceinline__ void lia_attn_prefill128_body(const bf16_t* __restric
 
   bf16x8 qf[8];
   {
-    const int qrow = min(q_wave + r, T - 1);
-    const bf16_t* qp = q + ((long)b * Tp + kstart + qrow) * ldq + (long)hh * D;
+    const int qrow = min(q_wave + r, Tq - 1);
+    const bf16_t* qp = q + ((long)b * Tp + (APPEND ? 0 : kstart) + qrow) * ldq + (long)hh * D;
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       uint4 v = *(const uint4*)(qp + 16 * s + 8 * h);
@@ -465,10 +489,10 @@ __device__ __forceinline__ void lia_attn_prefill128_body(const bf16_t* __restric
     }
   }
 
-  const int n32 = min((q_wg + 128 + 31) / 32, (T + 31) / 32);   // 32-key blocks the workgroup needs (causal)
+  const int n32 = min((qoff + q_wg + 128 + 31) / 32, (T + 31) / 32);   // 32-key blocks the workgroup needs (causal)
   const int n64 = (n32 + 1) / 2;
-  const int my_q = q_wave + r;
-  const int nblk = min(q_wave + 31, T - 1) / 32 + 1;            // 32-key blocks THIS wave needs: 0 .. nblk - 1
+  const int my_q = qoff + q_wave + r;                           // (frame position)
+  const int nblk = min(qoff + q_wave + 31, T - 1) / 32 + 1;     // 32-key blocks THIS wave needs: 0 .. nblk - 1
   const int vis = min(my_q, T - 1) - 4 * h;                     // key 32 kt + 4 h + koff is visible iff koff <= vis - 32 kt
 
   // K^T fragment of 16-dim slice ss: key row 32 sb + r, chunk (2 ss + h) ^ (r & 15)
@@ -532,7 +556,7 @@ __device__ __forceinline__ void lia_attn_prefill128_body(const bf16_t* __restric
 #else
 #define P3X_MATH 1
 #endif
-#define P3_S1_TILE2(MASKED)                                                                                                \
+#define P3_S1_TILE2(MASK0, MASKED)                                                                                         \
   if (P3X_MATH) do {                                                                                                                     \
     uint4 kf0[8], kf1[8];                                                                                                  \
     f32x16 s0 = f32x16{0}, s1 = f32x16{0};                                                                                 \
@@ -544,6 +568,10 @@ __device__ __forceinline__ void lia_attn_prefill128_body(const bf16_t* __restric
       if (c < 4) {                                                                                                         \
         rp[2 * c] = p3_round2<POST_SCALE>(s0[4 * c], s0[4 * c + 1], scaling);                                              \
         rp[2 * c + 1] = p3_round2<POST_SCALE>(s0[4 * c + 2], s0[4 * c + 3], scaling);                                      \
+        if (MASK0) {                                                                                                       \
+          rp[2 * c] = p3_mask2(rp[2 * c], lim1 + 32, 2 * c);                                                               \
+          rp[2 * c + 1] = p3_mask2(rp[2 * c + 1], lim1 + 32, 2 * c + 1);                                                   \
+        }                                                                                                                  \
         tm = fmaxf(fmaxf(tm, fmaxf(rp[2 * c].x, rp[2 * c].y)), fmaxf(rp[2 * c + 1].x, rp[2 * c + 1].y));                   \
         if (c == 3) {                                                                                                      \
           tm = fmaxf(tm, __shfl_xor(tm, 32, 64));                                                                          \
@@ -574,7 +602,11 @@ __device__ __forceinline__ void lia_attn_prefill128_body(const bf16_t* __restric
   // hipcc also merged sweep 2's 64 accumulator registers at the latch: 64 v_mov out of the two-block body and 64 back on the
   // back-edge, 128 of ~400 vector instructions per iteration (found in the ISA).  Same operations on the same values in the same order.
   const int nfull = nblk >> 1;                                     // (<= n64: nblk <= n32 <= 2 n64)
-  const int nfree = min((min(q_wave, T - 1) + 1) >> 6, nfull);
+  const int nfree = min((min(qoff + q_wave, T - 1) + 1) >> 6, nfull);
+  // APPEND: the query frame is not aligned to the key blocks (qoff is any number), so the diagonal may cross BOTH blocks of a tile;
+  // block 0 of tile t is wholly visible to the wave's first query while 2 t < (its position + 1) / 32 -- tiles 0 .. nb0 - 1 -- and the
+  // one two-block tile behind them, if any, masks block 0 as well.  Prefill: q_wave is a multiple of 32, nb0 == nfull.
+  const int nb0 = APPEND ? min((((min(qoff + q_wave, T - 1) + 1) >> 5) + 1) >> 1, nfull) : nfull;
 #define P3_S1_STEP()                                                                                                       \
   P3X_WAIT();                                                                                                              \
   __syncthreads();                                                                                                         \
@@ -587,12 +619,17 @@ __device__ __forceinline__ void lia_attn_prefill128_body(const bf16_t* __restric
     int t = 0;
     for (; t < nfree; ++t) {
       P3_S1_STEP();
-      P3_S1_TILE2(0);
+      P3_S1_TILE2(0, 0);
       (void)lim1;
     }
-    for (; t < nfull; ++t) {
+    for (; t < nb0; ++t) {
       P3_S1_STEP();
-      P3_S1_TILE2(1);
+      P3_S1_TILE2(0, 1);
+    }
+    if (APPEND && t < nfull) {     // the diagonal in both blocks of a tile (at most one such tile)
+      P3_S1_STEP();
+      P3_S1_TILE2(1, 1);
+      ++t;
     }
     if (t < n64) {
       P3_S1_STEP();
@@ -633,7 +670,7 @@ __device__ __forceinline__ void lia_attn_prefill128_body(const bf16_t* __restric
 #define P3_PF(pk, c) __builtin_bit_cast(bf16x8, uint4{pk[4 * ((c) >> 2)], pk[4 * ((c) >> 2) + 1], pk[4 * ((c) >> 2) + 2], pk[4 * ((c) >> 2) + 3]})
   // two visible blocks: chain 1 under the softmax of block 0, P.V of block 0 under the softmax of block 1, then P.V of block 1; the
   // V^T pieces are fetched one phase ahead.  Every oacc[d] takes its four products in the order (block 0, ks 0), (0, 1), (1, 0), (1, 1).
-#define P3_S2_TILE2(MASKED)                                                                                                \
+#define P3_S2_TILE2(MASK0, MASKED)                                                                                         \
   if (P3X_MATH) do {                                                                                                                     \
     uint4 kf0[8], kf1[8];                                                                                                  \
     f32x16 s0 = f32x16{0}, s1 = f32x16{0};                                                                                 \
@@ -646,7 +683,7 @@ __device__ __forceinline__ void lia_attn_prefill128_body(const bf16_t* __restric
         P3_VFRAG(vfa[c], vb, 0, c);                                                                                        \
       }                                                                                                                    \
       {                                                                                                                    \
-        const uint2 p_ = p3_prob4(p3_round4<POST_SCALE, 0>(s0[4 * c2], s0[4 * c2 + 1], s0[4 * c2 + 2], s0[4 * c2 + 3], scaling, 0, 0), m, l, rl); \
+        const uint2 p_ = p3_prob4(p3_round4<POST_SCALE, MASK0>(s0[4 * c2], s0[4 * c2 + 1], s0[4 * c2 + 2], s0[4 * c2 + 3], scaling, MASK0 ? lim1 + 32 : 0, MASK0 ? 2 * c2 : 0), m, l, rl); \
         pk0[2 * c2] = p_.x;                                                                                                \
         pk0[2 * c2 + 1] = p_.y;                                                                                            \
       }                                                                                                                    \
@@ -678,12 +715,17 @@ __device__ __forceinline__ void lia_attn_prefill128_body(const bf16_t* __restric
   int t = 0;
   for (; t < nfree; ++t) {
     P3_S2_STEP();
-    P3_S2_TILE2(0);
+    P3_S2_TILE2(0, 0);
     (void)lim1;
   }
-  for (; t < nfull; ++t) {
+  for (; t < nb0; ++t) {
     P3_S2_STEP();
-    P3_S2_TILE2(1);
+    P3_S2_TILE2(0, 1);
+  }
+  if (APPEND && t < nfull) {
+    P3_S2_STEP();
+    P3_S2_TILE2(1, 1);
+    ++t;
   }
   if (t < n64) {
     P3_S2_STEP();
@@ -750,7 +792,7 @@ __device__ __forceinline__ void lia_attn_prefill128_body(const bf16_t* __restric
     for (int i = 0; i < 8; ++i) {
       const int rr = 4 * i + orow;
       const uint4 v = *(const uint4*)(ob + rr * 256 + ((oc ^ (rr & 15)) << 4));
-      if (q_wave + rr < T && st_on) *(uint4*)(out + ((long)b * Tp + kstart + q_wave + rr) * ldo + (long)hh * D + 8 * oc) = v;
+      if (q_wave + rr < Tq && st_on) *(uint4*)(out + ((long)b * Tp + (APPEND ? 0 : kstart) + q_wave + rr) * ldo + (long)hh * D + 8 * oc) = v;
     }
   }
   }   // pass
@@ -761,7 +803,7 @@ __global__ __launch_bounds__(256, 2) void lia_attn_prefill128_kernel(const bf16_
                                                                   const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int T,
                                                                   int heads, int kv_heads, long kv_row, long kv_batch, int b0, float scaling,
                                                                   int nqb, int n_groups) {
-  lia_attn_prefill128_body<POST_SCALE, 0>(q, ldq, kc, vc, out, ldo, T, heads, kv_heads, kv_row, kv_batch, b0, scaling, nqb, n_groups, nullptr);
+  lia_attn_prefill128_body<POST_SCALE, 0, 0>(q, ldq, kc, vc, out, ldo, T, 0, heads, kv_heads, kv_row, kv_batch, b0, scaling, nqb, n_groups, nullptr);
 }
 // starts: per served row b (the caller passes its table + b0)
 template <int POST_SCALE>
@@ -769,7 +811,15 @@ __global__ __launch_bounds__(256, 2) void lia_attn_prefill128_padded_kernel(cons
                                                                          const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int T,
                                                                          int heads, int kv_heads, long kv_row, long kv_batch, int b0, float scaling,
                                                                          int nqb, int n_groups, const int* __restrict__ starts) {
-  lia_attn_prefill128_body<POST_SCALE, 1>(q, ldq, kc, vc, out, ldo, T, heads, kv_heads, kv_row, kv_batch, b0, scaling, nqb, n_groups, starts);
+  lia_attn_prefill128_body<POST_SCALE, 1, 0>(q, ldq, kc, vc, out, ldo, T, 0, heads, kv_heads, kv_row, kv_batch, b0, scaling, nqb, n_groups, starts);
+}
+// the append block (APPEND = 1 of the body): Tq queries at pos0 .. pos0 + Tq - 1; PADDED reads the row starts, else starts is unused
+template <int POST_SCALE, int PADDED>
+__global__ __launch_bounds__(256, 2) void lia_attn_append128_kernel(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ kc,
+                                                                 const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int Tq,
+                                                                 int pos0, int heads, int kv_heads, long kv_row, long kv_batch, int b0,
+                                                                 float scaling, int nqb, int n_groups, const int* __restrict__ starts) {
+  lia_attn_prefill128_body<POST_SCALE, PADDED, 1>(q, ldq, kc, vc, out, ldo, Tq, pos0, heads, kv_heads, kv_row, kv_batch, b0, scaling, nqb, n_groups, starts);
 }
 
 
@@ -1039,6 +1089,47 @@ extern "C" int lia_attn_prefill_padded_launch(const bf16_t* q, long ldq, const b
                                               const int* starts, hipStream_t st) {
   if (!starts) return -1;
   return prefill_launch(q, ldq, kc, vc, out, ldo, B, T, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
+}
+
+// A block of T queries at cache positions pos0 .. pos0 + T - 1 of every served row, over the keys starts[b] (or 0) .. pos0 + T - 1 that the
+// cache already holds (the block's own K / V rows included).  q / out: [B][T][heads * d] with pitches ldq / ldo, the block's rows only.
+// starts: device, B entries, each <= pos0 -- or NULL.  Row t of the result is bit for bit row pos0 + t of the prefill launch over
+// pos0 + T tokens with the same q rows and cache (see lia_attn_prefill_kernel).  Grids, orders and the d = 128 limit are the prefill launcher's.
+extern "C" int lia_attn_append_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T,
+                                      int pos0, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts,
+                                      hipStream_t st) {
+  if (B <= 0 || T <= 0) return 0;
+  if (pos0 < 0 || kv_heads <= 0 || heads % kv_heads) return -1;
+  dim3 grid((T + 127) / 128, heads, B);
+  const float scaling = 1.0f / sqrtf((float)d);
+  switch (d) {
+    case 128: {
+      const long hd = (long)kv_heads * 128;
+      const int nqb_all = (T + 127) / 128;
+      const int nqb = (nqb_all + 1) / 2;
+      if ((long)Bc * hd * 2 * 64 + 256 >= (1L << 32)) return -1;
+      int n_groups = B * kv_heads;
+      const bool xcd_order = (n_groups % 8 == 0) || n_groups >= 64;
+      const unsigned nwg = xcd_order ? (unsigned)(((n_groups + 7) / 8) * 8 * nqb * (heads / kv_heads)) : (unsigned)(nqb * heads * B);
+      if (!xcd_order) n_groups = 0;
+      const dim3 grid128(nwg);
+#define LIA_APP128(PS, PD) hipLaunchKernelGGL((lia_attn_append128_kernel<PS, PD>), grid128, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, pos0, heads, kv_heads, (long)Bc * hd, hd, b0, scaling, nqb, n_groups, starts)
+      if (starts) { if (post_scale) LIA_APP128(1, 1); else LIA_APP128(0, 1); }
+      else { if (post_scale) LIA_APP128(1, 0); else LIA_APP128(0, 0); }
+#undef LIA_APP128
+      break;
+    }
+    case 64:
+      if (starts) hipLaunchKernelGGL((lia_attn_prefill_kernel<64, 1, int>), grid, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, Bc, b0, scaling, post_scale, starts, pos0);
+      else hipLaunchKernelGGL((lia_attn_prefill_kernel<64, 0, int>), grid, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, Bc, b0, scaling, post_scale, (const int*)nullptr, pos0);
+      break;
+    case 32:
+      if (starts) hipLaunchKernelGGL((lia_attn_prefill_kernel<32, 1, int>), grid, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, Bc, b0, scaling, post_scale, starts, pos0);
+      else hipLaunchKernelGGL((lia_attn_prefill_kernel<32, 0, int>), grid, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, Bc, b0, scaling, post_scale, (const int*)nullptr, pos0);
+      break;
+    default: return -1;
+  }
+  return 0;
 }
 
 template <int D>

@@ -236,18 +236,23 @@ class LlamaScheduler:
     def score(self, input_ids, kv_state, targets, gpu_percentage=100, num_minibatch=1, pin_weight=True, enable_cxl=False, **_ignored):
         """One prefill-shaped pass over input_ids [B, T] (T > 1, an empty kv_state sized for T: scratch) -> (logprobs float32 [B, T],
         greedy ids int64 [B, T]) on the device: log p(targets[b, t] | ids[b, :t + 1]) (targets int64 [B, T], -1 = none -> 0.0) and the
-        greedy token at t.  forward()'s prefill with the last layer on every position, then lia_llama_lm_score."""
+        greedy token at t.  forward()'s prefill with the last layer on every position, then lia_llama_lm_score.
+        On a NON-EMPTY cache the block is appended at kv_state.len .. and scored against the cached context; kv_state.len does not
+        advance (the block's K/V rows behind len are dead), the cache must hold len + T positions."""
         m, sh = self.model, self.model.shape
         B, T = input_ids.shape
-        if T < 2 or kv_state.len != 0:
-            raise ValueError(f"score: a prefill over at least two tokens on an empty cache (T={T}, cache length {kv_state.len})")
+        if T < 2:
+            raise ValueError(f"score: a block of at least two tokens (T={T}, cache length {kv_state.len})")
+        if kv_state.len + T > kv_state.smax:
+            raise ValueError(f"score: the cache holds {kv_state.smax} positions, the context {kv_state.len} + the block {T} need {kv_state.len + T}")
+        len0 = kv_state.len
         if tuple(targets.shape) != (B, T):
             raise ValueError(f"score: targets has shape {tuple(targets.shape)}, input_ids {(B, T)}")
         x, _ = self._layers(input_ids, kv_state, gpu_percentage, num_minibatch, pin_weight, enable_cxl, every_pos=True)
         tgt_dev = targets.to(device="cuda", dtype=torch.int64).contiguous()
         lp, greedy = self.ctx.llama_lm_score(x, m.final_norm_w, m.lm_head, tgt_dev, sh.rms_eps)
         self.ctx.synchronize()
-        kv_state.len += T
+        kv_state.len = len0 + T if len0 == 0 else len0
         return lp.view(B, T), greedy.view(B, T)
 
     def _layers(self, input_ids, kv_state, gpu_percentage, num_minibatch, pin_weight, enable_cxl, every_pos=False):
@@ -293,7 +298,7 @@ class LlamaScheduler:
             else:
                 w = pipe.acquire(idx)
                 pipe.prefetch_ahead(idx, stream_order(idx, n_gpu, L))
-            tail = self.prefill_tail and not every_pos and T > 1 and pos0 == 0 and idx == L - 1
+            tail = self.prefill_tail and not every_pos and T > 1 and idx == L - 1
             if tail:
                 xlast = torch.empty((B, 1, sh.hidden), dtype=torch.bfloat16, device="cuda")
             fn = lib.lia_llama_layer_forward_last if tail else lib.lia_llama_layer_forward

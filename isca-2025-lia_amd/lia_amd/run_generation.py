@@ -84,6 +84,14 @@ def build_parser():
     p.add_argument("--prompt-file", default=None, type=str,
                    help="a text file with one prompt per line: the batch is the prompts in file order, cycled to --batch-size, left "
                         "padded, with the matching attention_mask (needs the tokenizer files in the -m directory; not with --prompt)")
+    p.add_argument("--followup", action="append", default=None, type=str,
+                   help="with --prompt: a follow-up turn appended to the live KV cache of the conversation (generate(past=)); may be "
+                        "given several times, one turn each.  Every turn generates --max-new-tokens and is printed; no benchmark loop")
+    p.add_argument("--reserve-tokens", default=None, type=int,
+                   help="with --followup: cache positions kept free behind the first turn for the later ones (default: what the "
+                        "follow-ups and their new tokens need)")
+    p.add_argument("--append-policy", default=None, type=int, choices=(0, 2, 3),
+                   help="with --followup: 2 = a follow-up block's attention runs on the host cores (host caches only); default: the prefill policy")
     p.add_argument("--profile", action="store_true",
                    help="one profiled generate() before the timed loop (run_generation.py:103,290-307 runs torch.profiler over five "
                         "there); here the library's own HIP-event brackets: GEMM time / rates per phase, host attention, link traffic")
@@ -449,6 +457,53 @@ def plan_beside(args):
         return {"error": f"no placement fits: {e}"}
 
 
+def followup_ids(args, vocab, tokenizer):
+    """--followup texts -> [int64 [B, T2]] through the checkpoint's tokenizer, every row the same text (as --prompt); no BOS / EOS
+    of their own: a follow-up continues the conversation"""
+    if args.prompt is None:
+        raise SystemExit("[ERROR] --followup continues the conversation that --prompt starts: give --prompt")
+    if tokenizer is None:
+        raise SystemExit("[ERROR] --followup needs a tokenizer: point -m at a checkpoint directory that ships its tokenizer files "
+                         f"({', '.join(TOKENIZER_FILES[:3])}); {args.model_id!r} has none")
+    out = []
+    for text in args.followup:
+        row = tokenizer(text, return_tensors="pt", add_special_tokens=False).input_ids.to(torch.int64)
+        if row.numel() and (int(row.max()) >= vocab or int(row.min()) < 0):
+            raise SystemExit(f"[ERROR] the tokenizer produced ids outside the model's vocabulary of {vocab} entries")
+        out.append(row.reshape(1, -1).repeat(args.batch_size, 1))
+    return out
+
+
+def reserve_for(args, followups):
+    """--reserve-tokens, or what the follow-up turns need: their tokens and their new tokens"""
+    if args.reserve_tokens is not None:
+        return int(args.reserve_tokens)
+    return sum(int(f.shape[1]) + int(args.max_new_tokens) for f in followups)
+
+
+def run_conversation(model, input_ids, followups, generate_kwargs, args, tokenizer, out=print):
+    """--prompt P --followup F ...: turn 0 generates from the prompt and keeps its state, every follow-up is appended to the live
+    cache; each turn's new tokens (and text) are printed.  -> {"turns": [ids of the new tokens of row 0], "turn_s": [...]}"""
+    kw = {k: v for k, v in generate_kwargs.items() if k not in ("token_latency", "attention_mask")}
+    turns, secs = [], []
+    state, seen = None, int(input_ids.shape[1])
+    for i, block in enumerate([input_ids] + list(followups)):
+        tic = time.time()
+        if state is None:
+            ids, state = generate(model, block, return_state=True, reserve_tokens=reserve_for(args, followups), **kw)
+        else:
+            ids, state = generate(model, block, past=state, return_state=True, append_policy=args.append_policy, **kw)
+            seen += int(block.shape[1])
+        secs.append(time.time() - tic)
+        new = ids[0, seen:].tolist()
+        seen = int(ids.shape[1])
+        turns.append(new)
+        if tokenizer is not None:
+            out(f"turn {i}: {tokenizer.decode(new, skip_special_tokens=True)!r}")
+        out(f"turn {i}: {new} in {secs[-1]:.6f} sec")
+    return {"turns": turns, "turn_s": secs}
+
+
 SAMPLE_FLAGS = ("do_sample", "temperature", "top_k", "top_p", "sample_seed")
 
 
@@ -553,6 +608,10 @@ def _main(args, rec=None):
                                                                           generate_kwargs.get("pad_token_id", 1))
     else:
         input_ids = prompt_input_ids(args, model.shape.vocab, tokenizer)
+    if args.followup:
+        if args.prompt_file is not None:
+            raise SystemExit("[ERROR] --followup with --prompt-file is not supported: one conversation, every row the same (--prompt)")
+        return run_conversation(model, input_ids, followup_ids(args, model.shape.vocab, tokenizer), generate_kwargs, args, tokenizer)
     if args.profile:
         profile_once(model, input_ids, generate_kwargs)
     total_time, total_list = 0.0, []

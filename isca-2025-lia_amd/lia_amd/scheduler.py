@@ -224,14 +224,17 @@ class OffloadScheduler:
     # the step record `s`; none reaches back.
     def forward(self, input_ids, kv_state, prefill_policy=1, decoding_policy=1, no_overlap=False, pin_weight=False,
                 gpu_percentage=0, num_minibatch=1, enable_cxl=False, max_new_tokens=None, suppress_token=-1, cpu_layers=0,
-                cpu_layers_start=None, sampler=None):
+                cpu_layers_start=None, sampler=None, append_policy=None):
         """cpu_layers (build-defined): with decoding policy 2, that many of the streamed layers run
         their decode step entirely on the host cores (policy 1, weights read in place) instead of crossing the link --
         the cooperative split of the reference taken per layer.  Prefill is unaffected (policy 0 for every layer).
         cpu_layers=-1: the count is chosen ONLINE (CoopController) from the measured decode steps, starting at cpu_layers_start
         (default: planner.plan_cpu_layers for this shape and box defaults).
-        sampler (sampling.Sampler, generate(do_sample=True)): the returned ids are its draw from the logits instead of their argmax."""
-        s = self._validate(input_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch)
+        sampler (sampling.Sampler, generate(do_sample=True)): the returned ids are its draw from the logits instead of their argmax.
+        A multi-token call on a NON-EMPTY cache appends its block at positions kv_state.len .. (generate(past=)): it goes by the
+        prefill policy like every multi-token call, or by append_policy = 2 where the caches live on the host -- q, k, v of the
+        block travel to the host attention instead of the cached prefix to the GPU (the one multi-token policy 2)."""
+        s = self._validate(input_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch, append_policy)
         self._place(s, kv_state, pin_weight, enable_cxl, max_new_tokens, cpu_layers, cpu_layers_start)
         m, sh, ctx = self.model, self.model.shape, self.ctx
         ids_dev = input_ids.to("cuda", non_blocking=False).contiguous()
@@ -248,22 +251,30 @@ class OffloadScheduler:
         return logits, nxt
 
     def score(self, input_ids, kv_state, targets, prefill_policy=1, decoding_policy=1, no_overlap=False, pin_weight=False,
-              gpu_percentage=0, num_minibatch=1, enable_cxl=False, **_decode_only):
+              gpu_percentage=0, num_minibatch=1, enable_cxl=False, append_policy=None, **_decode_only):
         """One prefill-shaped pass over input_ids [B, T] (T > 1, an empty kv_state sized for T: the caches are scratch) that returns
         (logprobs float32 [B, T], greedy ids int64 [B, T]) on the device: entry [b, t] is log p(targets[b, t] | ids[b, :t + 1]) and
         the greedy token at position t (targets: int64 [B, T], -1 = none -> 0.0).  The phases are forward()'s, with the last layer
         computing EVERY position for this call and lm_score in place of lm_head.  A policy-0 pass keeps the streamed layers' K/V
         in the HBM holding caches and SKIPS their delivery to the host caches: nothing is outstanding when the call returns.
         Decode-only flags (decoding_policy, cpu_layers, ...) are accepted and have no effect beyond naming where the cache lives
-        (policy 3 wants 3 for both, as in forward)."""
+        (policy 3 wants 3 for both, as in forward).
+        On a NON-EMPTY cache the block is appended at positions kv_state.len .. and scored against the cached context (entry [b, t]
+        conditions on the context and ids[b, :t + 1]); the cache must hold len + T positions.  kv_state.len does NOT advance: the
+        block's K/V rows land behind len and are dead, so many continuations can be scored against one context.  A fixed cpu_layers
+        of the generation that owns the cache is passed through so that the layers keep their placement."""
         B, T = input_ids.shape
-        if T < 2 or kv_state.len != 0:
-            raise ValueError(f"score: a prefill over at least two tokens on an empty cache (T={T}, cache length {kv_state.len})")
+        if T < 2:
+            raise ValueError(f"score: a block of at least two tokens (T={T}, cache length {kv_state.len})")
+        if kv_state.len + T > kv_state.smax:
+            raise ValueError(f"score: the cache holds {kv_state.smax} positions, the context {kv_state.len} + the block {T} need {kv_state.len + T}")
         if tuple(targets.shape) != (B, T):
             raise ValueError(f"score: targets has shape {tuple(targets.shape)}, input_ids {(B, T)}")
-        s = self._validate(input_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch)
+        len0 = kv_state.len
+        s = self._validate(input_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch, append_policy)
         s.every_pos = True
-        self._place(s, kv_state, pin_weight, enable_cxl, None, 0, None)
+        cpu_layers = max(0, int(_decode_only.get("cpu_layers") or 0)) if len0 else 0
+        self._place(s, kv_state, pin_weight, enable_cxl, None, cpu_layers, None)
         m, sh, ctx = self.model, self.model.shape, self.ctx
         ids_dev = input_ids.to("cuda", non_blocking=False).contiguous()
         tgt_dev = targets.to(device="cuda", dtype=torch.int64).contiguous()
@@ -274,6 +285,8 @@ class OffloadScheduler:
             hidden = self._run_layers(s, kv_state)
         lp, greedy = ctx.lm_score(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, tgt_dev, sh.ln_eps)
         self._deliver(s, kv_state)
+        if len0:
+            kv_state.len = len0               # (an appended block is scored, not kept)
         return lp.view(B, T), greedy.view(B, T)
 
     # -- left-padded batches (generation.generate(..., attention_mask=)) -----------------------------------------------------
@@ -310,7 +323,7 @@ class OffloadScheduler:
             raise ValueError(f"the key-start table has {ks[0].shape[0]} rows, the forward {B}")
         return ks[:2]
 
-    def _validate(self, input_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch):
+    def _validate(self, input_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch, append_policy=None):
         """shapes and flags of one forward -> the step record; raises on the combinations the path does not have"""
         sh = self.model.shape
         B, T = input_ids.shape
@@ -318,12 +331,21 @@ class OffloadScheduler:
         n_gpu = int(L * gpu_percentage / 100)                      # lia/modeling_opt.py:1182
         is_prefill = T != 1                                        # :1186-1188
         policy = prefill_policy if is_prefill else decoding_policy
+        # a multi-token block behind a non-empty cache goes by the prefill policy, or by append_policy = 2 (host caches only)
+        is_append = is_prefill and kv_state.len > 0
+        if append_policy is not None and append_policy not in (prefill_policy, 2):
+            raise ValueError(f"append_policy {append_policy}: None (the prefill policy, {prefill_policy}) or 2")
+        if is_append and append_policy == 2 and n_gpu < L:
+            if kv_state.all_on_device:
+                raise ValueError("append_policy 2 computes the block's attention on the host cores: the KV cache must live on the host, "
+                                 "this generation keeps it in HBM (policy 3)")
+            policy = 2
         if n_gpu < L and policy not in (0, 1, 2, 3):
             raise ValueError(f"unsupported policy {policy} (prefill: 0, 1 or 3; decode: 0, 1, 2 or 3)")
         if n_gpu < L and (policy == 3) != bool(kv_state.all_on_device):
             raise ValueError("policy 3 on streamed layers (KV cache in HBM, SURVEY.md section 8 f-1) must be chosen for BOTH "
                              "phases: the cache of a generation lives either in HBM or on the host")
-        if is_prefill and policy == 2 and n_gpu < L:
+        if is_prefill and policy == 2 and n_gpu < L and not is_append:
             raise ValueError("prefill policy must be 0 on the GPU path (the reference has no prefill-2 branch)")
         # :1178 mini_bsz = int(bsz / num_minibatch), looped num_minibatch times: the reference leaves the rows behind the last full
         # minibatch unwritten when the division has a remainder and computes nothing at all for num_minibatch > bsz -- both happen in
@@ -384,6 +406,9 @@ class OffloadScheduler:
             # prefill sized the workspace for batch x max positions rows: 60 GB of HBM at batch 1050 x 288 positions, which is
             # what ran the planner's batch-1050 pick out of memory; the reference's scripts never use decode policy 0.)
             rows = max(rows, s.mini * kv_state.smax)
+        if is_prefill and s.policy == 0 and s.pos0 > 0 and n_gpu < L:
+            # a policy-0 block appended to a non-empty cache parks the cached prefix and its own rows in the slab: mini (pos0 + T) rows
+            rows = max(rows, s.mini * (s.pos0 + T))
         s.x, s.y = self._ensure(rows, B, T, n_gpu, score_rows=B * T if s.every_pos else 0)
         if is_prefill and s.policy == 0 and n_gpu < L and self.defer_kv and s.pos0 == 0:
             self._await_all_deliveries()          # (host-blocking: afterwards nothing on the D2H stream reads the holding caches)
@@ -398,7 +423,7 @@ class OffloadScheduler:
         if n_gpu < L and overlap:
             pipe.prefetch(n_gpu)                                   # no-op if the previous step already wrapped to it
         # the prefill's last layer: only hidden[:, -1, :] feeds lm_head (models.py:424-431), its K/V of every position feed decode
-        tail_last = self.prefill_tail and not s.every_pos and is_prefill and T > 1 and pos0 == 0 and (policy in (0, 3) or n_gpu == L) and (L - 1) not in host_now
+        tail_last = self.prefill_tail and not s.every_pos and is_prefill and T > 1 and (policy in (0, 3) or n_gpu == L) and (L - 1) not in host_now
         xlast = None
         first = 0
         if not is_prefill and n_gpu > 0:

@@ -6,6 +6,8 @@ of the offload scheduler (OffloadScheduler.score / LlamaScheduler.score) under g
     [(ll, is_greedy)] = loglikelihood(model, [(context_ids, continuation_ids), ...], batch_size=8, **lia_kwargs)
     ll = loglikelihood_rolling(model, token_ids, prefix_token, max_len=None, **lia_kwargs)
 
+    logprobs, greedy = continuation_logprobs(model, state, cont_ids, append_policy=None)   # against a cached conversation
+
 lm_eval itself is not a dependency; the two request kinds restate its meaning.
 """
 import numpy as np
@@ -85,6 +87,43 @@ def score(model, input_ids, attention_mask=None, **lia_kwargs):
     logprobs = torch.where(valid, lp, torch.zeros_like(lp))
     greedy = (gr == ids[:, 1:]) & valid
     return logprobs, greedy, valid
+
+
+def continuation_logprobs(model, state, cont_ids, append_policy=None):
+    """cont_ids [B, Tc >= 1] scored against the cached conversation of `state` (generation.GenerationState) -> (logprobs float32
+    [B, Tc], greedy bool [B, Tc]) on the CPU: logprobs[b, t] = log p(cont[b, t] | conversation, cont[b, :t]).  One appended block
+    [pending | cont[:, :-1]] through the scheduler's score(): the first continuation token is scored from the pending token's
+    position.  The state is not changed (its cache length stays; the block's K/V rows behind it are dead), so any number of
+    continuations can be scored against one context.  The cache must have room for the block (generate(reserve_tokens=))."""
+    from .generation import GenerationState
+    if not isinstance(state, GenerationState):
+        raise ValueError(f"state must be the GenerationState of generate(..., return_state=True), got {type(state).__name__}")
+    cont = torch.as_tensor(cont_ids, dtype=torch.int64).cpu()
+    if cont.dim() != 2 or cont.shape[0] != state.batch or cont.shape[1] < 1:
+        raise ValueError(f"cont_ids must be [batch = {state.batch}, Tc >= 1], got {tuple(cont.shape)}")
+    if int(cont.min()) < 0 or int(cont.max()) >= model.shape.vocab:
+        raise ValueError(f"cont_ids outside the model's vocabulary of {model.shape.vocab} entries")
+    B, Tc = cont.shape
+    # (the schedulers score blocks of at least two tokens: a single continuation token takes itself along as an unscored input)
+    block = torch.cat([state.pending[:, None], cont[:, :-1] if Tc > 1 else cont], dim=1)
+    T = block.shape[1]
+    if state.kv.len + T > state.kv.smax or state.kv.len + T > model.shape.max_pos:
+        raise ValueError(f"the continuation needs {T} cache positions behind the {state.kv.len} cached ones, the cache has "
+                         f"{state.room()} and the model {model.shape.max_pos} positions (give generate() a larger reserve_tokens)")
+    targets = torch.full((B, T), -1, dtype=torch.int64)
+    targets[:, :Tc] = cont
+    sched = _scheduler_of(model)
+    flags = dict(state.flags)
+    if append_policy is not None:
+        flags["append_policy"] = append_policy
+    if state.starts is not None:
+        sched.set_key_starts(state.starts)
+    try:
+        lp, gr = sched.score(block, state.kv, targets, **flags)
+    finally:
+        if state.starts is not None:
+            sched.set_key_starts(None)
+    return lp[:, :Tc].to(torch.float32).cpu(), gr[:, :Tc].cpu() == cont
 
 
 def _max_len(model, max_len):
