@@ -15,7 +15,7 @@
 // resident layers (device cache) and the streamed prefill (staging slab that is then copied to the
 // host cache).
 #include <cstdlib>
-#include "lia_common.h"
+#include "lia_internal.h"
 #include <type_traits>
 
 // ---------------------------------------------------------------------------------------------
@@ -1022,6 +1022,29 @@ __global__ __launch_bounds__(256) void lia_attn_decode_kernel(const bf16_t* __re
   }
 }
 
+// The d = 128 kernels' grid (prefill and append alike): nqb query-block slots per (row, head), the workgroup order, the grid size.
+struct LiaGrid128 { long hd; int nqb, n_groups; unsigned nwg; };   // nwg == 0: the cache is beyond the 32-bit staging offsets
+static LiaGrid128 grid128_of(int B, int T, int heads, int kv_heads, int Bc) {
+  LiaGrid128 g{(long)kv_heads * 128, 0, B * kv_heads, 0};
+  // (a token-major [B][T][h][d] K/V -- strides (hd, T hd) -- was measured: same time, so the cache layout stays)
+#ifdef LIA_ATTN_NO_PAIRS
+  g.nqb = (T + 127) / 128;
+#else
+  g.nqb = ((T + 127) / 128 + 1) / 2;        // two query blocks per workgroup: bx and its mirror image (see the kernel)
+#endif
+  // the staging addresses hold (row within a 64-key tile) x (bytes per key row) + chunk in 32 bits: 64 Bc hd 2 < 2^32, i.e. a
+  // cache batch x hidden of < 3.3e7 elements per key row (OPT-175B at Bc = 2048 is 2.5e7)
+  if ((long)Bc * g.hd * 2 * 64 + 256 >= (1L << 32)) return g;
+  // the XCD-aware order when the groups spread evenly over the 8 XCDs (a multiple of 8, or so many that the remainder does not
+  // matter); otherwise r05's order, which deals single workgroups round-robin (2 rows x 2 KV heads would use 4 XCDs of 8)
+  bool xcd_order = (g.n_groups % 8 == 0) || g.n_groups >= 64;
+#ifdef LIA_ATTN_LEGACY_GRID
+  xcd_order = false;
+#endif
+  g.nwg = xcd_order ? (unsigned)(((g.n_groups + 7) / 8) * 8 * g.nqb * (heads / kv_heads)) : (unsigned)(g.nqb * heads * B);
+  if (!xcd_order) g.n_groups = 0;
+  return g;
+}
 
 // starts == nullptr: the unpadded kernels; otherwise their PADDED instantiations with the row starts starts[0 .. B - 1]
 // (device memory, 0 <= starts[b] <= T - 1)
@@ -1033,34 +1056,15 @@ static int prefill_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf1
   const float scaling = 1.0f / sqrtf((float)d);
   switch (d) {
     case 128: {
-      const long hd = (long)kv_heads * 128;
-      // (a token-major [B][T][h][d] K/V -- strides (hd, T hd) -- was measured: same time, so the cache layout stays)
-      const int nqb_all = (T + 127) / 128;
-#ifdef LIA_ATTN_NO_PAIRS
-      const int nqb = nqb_all;
-#else
-      const int nqb = (nqb_all + 1) / 2;               // two query blocks per workgroup: bx and its mirror image (see the kernel)
-#endif
-      // the staging addresses hold (row within a 64-key tile) x (bytes per key row) + chunk in 32 bits: 64 Bc hd 2 < 2^32, i.e. a
-      // cache batch x hidden of < 3.3e7 elements per key row (OPT-175B at Bc = 2048 is 2.5e7)
-      if ((long)Bc * hd * 2 * 64 + 256 >= (1L << 32)) return -1;
-      int n_groups = B * kv_heads;
-      // the XCD-aware order when the groups spread evenly over the 8 XCDs (a multiple of 8, or so many that the remainder does not
-      // matter); otherwise r05's order, which deals single workgroups round-robin (2 rows x 2 KV heads would use 4 XCDs of 8)
-      bool xcd_order = (n_groups % 8 == 0) || n_groups >= 64;
-#ifdef LIA_ATTN_LEGACY_GRID
-      xcd_order = false;
-#endif
-      const unsigned nwg = xcd_order ? (unsigned)(((n_groups + 7) / 8) * 8 * nqb * (heads / kv_heads)) : (unsigned)(nqb * heads * B);
-      if (!xcd_order) n_groups = 0;
-      const dim3 grid128(nwg);
+      const LiaGrid128 g = grid128_of(B, T, heads, kv_heads, Bc);
+      if (!g.nwg) return -1;
       if (starts) {
-        if (post_scale) hipLaunchKernelGGL(lia_attn_prefill128_padded_kernel<1>, grid128, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, (long)Bc * hd, hd, b0, scaling, nqb, n_groups, starts);
-        else hipLaunchKernelGGL(lia_attn_prefill128_padded_kernel<0>, grid128, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, (long)Bc * hd, hd, b0, scaling, nqb, n_groups, starts);
+        if (post_scale) hipLaunchKernelGGL(lia_attn_prefill128_padded_kernel<1>, dim3(g.nwg), dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, (long)Bc * g.hd, g.hd, b0, scaling, g.nqb, g.n_groups, starts);
+        else hipLaunchKernelGGL(lia_attn_prefill128_padded_kernel<0>, dim3(g.nwg), dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, (long)Bc * g.hd, g.hd, b0, scaling, g.nqb, g.n_groups, starts);
         break;
       }
-      if (post_scale) hipLaunchKernelGGL(lia_attn_prefill128_kernel<1>, grid128, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, (long)Bc * hd, hd, b0, scaling, nqb, n_groups);
-      else hipLaunchKernelGGL(lia_attn_prefill128_kernel<0>, grid128, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, (long)Bc * hd, hd, b0, scaling, nqb, n_groups);
+      if (post_scale) hipLaunchKernelGGL(lia_attn_prefill128_kernel<1>, dim3(g.nwg), dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, (long)Bc * g.hd, g.hd, b0, scaling, g.nqb, g.n_groups);
+      else hipLaunchKernelGGL(lia_attn_prefill128_kernel<0>, dim3(g.nwg), dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, heads, kv_heads, (long)Bc * g.hd, g.hd, b0, scaling, g.nqb, g.n_groups);
       break;
     }
     case 64:
@@ -1076,17 +1080,15 @@ static int prefill_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf1
   return 0;
 }
 
-extern "C" int lia_attn_prefill_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
-                                       int B, int T, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
-                                       hipStream_t st) {
+extern "C" int lia_attn_prefill_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T,
+                                       int heads, int kv_heads, int d, int Bc, int b0, int post_scale, hipStream_t st) {
   return prefill_launch(q, ldq, kc, vc, out, ldo, B, T, heads, kv_heads, d, Bc, b0, post_scale, nullptr, st);
 }
 
 // left-padded rows (the reference's CPU branch with an HF padding mask, lia/modeling_opt.py:1133 + mha_fusion.py:532-566):
 // served row b's query i >= starts[b] attends keys starts[b] .. i; rows i < starts[b] are zeros.  starts: device, B entries.
-extern "C" int lia_attn_prefill_padded_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
-                                              int B, int T, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
-                                              const int* starts, hipStream_t st) {
+extern "C" int lia_attn_prefill_padded_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B,
+                                              int T, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, hipStream_t st) {
   if (!starts) return -1;
   return prefill_launch(q, ldq, kc, vc, out, ldo, B, T, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
 }
@@ -1104,16 +1106,9 @@ extern "C" int lia_attn_append_launch(const bf16_t* q, long ldq, const bf16_t* k
   const float scaling = 1.0f / sqrtf((float)d);
   switch (d) {
     case 128: {
-      const long hd = (long)kv_heads * 128;
-      const int nqb_all = (T + 127) / 128;
-      const int nqb = (nqb_all + 1) / 2;
-      if ((long)Bc * hd * 2 * 64 + 256 >= (1L << 32)) return -1;
-      int n_groups = B * kv_heads;
-      const bool xcd_order = (n_groups % 8 == 0) || n_groups >= 64;
-      const unsigned nwg = xcd_order ? (unsigned)(((n_groups + 7) / 8) * 8 * nqb * (heads / kv_heads)) : (unsigned)(nqb * heads * B);
-      if (!xcd_order) n_groups = 0;
-      const dim3 grid128(nwg);
-#define LIA_APP128(PS, PD) hipLaunchKernelGGL((lia_attn_append128_kernel<PS, PD>), grid128, dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, pos0, heads, kv_heads, (long)Bc * hd, hd, b0, scaling, nqb, n_groups, starts)
+      const LiaGrid128 g = grid128_of(B, T, heads, kv_heads, Bc);
+      if (!g.nwg) return -1;
+#define LIA_APP128(PS, PD) hipLaunchKernelGGL((lia_attn_append128_kernel<PS, PD>), dim3(g.nwg), dim3(256), 0, st, q, ldq, kc, vc, out, ldo, T, pos0, heads, kv_heads, (long)Bc * g.hd, g.hd, b0, scaling, g.nqb, g.n_groups, starts)
       if (starts) { if (post_scale) LIA_APP128(1, 1); else LIA_APP128(0, 1); }
       else { if (post_scale) LIA_APP128(1, 0); else LIA_APP128(0, 0); }
 #undef LIA_APP128
@@ -1137,9 +1132,7 @@ static int launch_decode(const bf16_t* q, long ldq, const bf16_t* kc, const bf16
                          int kv_heads, int Bc, int b0, float scaling, int post_scale, const int* starts, hipStream_t st) {
   const int G = heads / kv_heads;
   dim3 grid(kv_heads, B);
-  const int kpp = 256 / (D / 8);
   const int Spad = (S + 3) & ~3;
-  (void)kpp;
   size_t lds = ((size_t)G * Spad + (size_t)4 * G * D + (size_t)G * 8) * sizeof(float);
   if (lds > 160 * 1024) return -1;
 #define LIA_DEC(GV)                                                                                                            \
@@ -1176,16 +1169,23 @@ static int decode_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16
   }
 }
 
-extern "C" int lia_attn_decode_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
-                                      int B, int S, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
-                                      hipStream_t st) {
+extern "C" int lia_attn_decode_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int S,
+                                      int heads, int kv_heads, int d, int Bc, int b0, int post_scale, hipStream_t st) {
   return decode_launch(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, d, Bc, b0, post_scale, nullptr, st);
 }
 
 // one query per served row at position S - 1 over keys starts[b] .. S - 1 (starts: device, B entries, each <= S - 1)
-extern "C" int lia_attn_decode_padded_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo,
-                                             int B, int S, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
-                                             const int* starts, hipStream_t st) {
+extern "C" int lia_attn_decode_padded_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B,
+                                             int S, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, hipStream_t st) {
   if (!starts) return -1;
   return decode_launch(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
+}
+
+// The attention launch of a call with T queries per row behind pos0 cached positions: see lia_internal.h for the rule.
+int lia_attn_dispatch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T, int pos0,
+                      int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, int tail, hipStream_t st) {
+  if (T > 1 && pos0 > 0 && !tail) return lia_attn_append_launch(q, ldq, kc, vc, out, ldo, B, T, pos0, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
+  const LiaTail t = lia_tail(tail, B, T, ldq);
+  if (T == 1 || tail) return decode_launch(q + t.off, t.ld, kc, vc, out, ldo, B, pos0 + T, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
+  return prefill_launch(q, ldq, kc, vc, out, ldo, B, T, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
 }

@@ -1,7 +1,7 @@
 // Row-wise / gather kernels of the LIA hot path (HBM-bound, 16-byte vector accesses everywhere):
 // LayerNorm, token+position embedding, last-position gather, greedy argmax.
 #include <cstdlib>
-#include "lia_common.h"
+#include "lia_internal.h"
 
 // F.layer_norm on a bf16 tensor (decoder.py:107-119; final LN lia/modeling_opt.py:1563): statistics and
 // affine in fp32, ONE rounding at the output.  One wave per row; the row (<= 24 KB) is read three

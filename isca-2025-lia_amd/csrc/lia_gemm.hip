@@ -16,7 +16,7 @@
 //     (cdna_hip_programming.md rule 21), double-buffered, XCD-aware tile order.
 #include <cstdio>
 #include <cstring>
-#include "lia_common.h"
+#include "lia_internal.h"
 #include "lia_epilogue.h"
 
 #define GL_AS1(p) ((const __attribute__((address_space(1))) void*)(p))

@@ -19,9 +19,7 @@
 
 #include <vector>
 
-#include "../../include/lia_hip.h"
-
-extern "C" void lia_set_error(const char* fmt, ...);
+#include "lia_internal.h"
 
 // ------------------------------------------------------------------------------------------------
 // One OpenMP region per host layer.  The launchers park the OpenMP team between bursts (OMP_WAIT_POLICY=PASSIVE /
@@ -834,7 +832,7 @@ extern "C" int lia_host_layers_forward_padded(const lia_layer_desc* d, int n_lay
   return host_layers_forward(d, n_layers, weights, x, y, kcaches, vcaches, smax, cache_batch, B, T, pos0, b0, n_threads, starts);
 }
 
-// memcpy by a team (the streamer's staging of pageable sources, lia_api.hip::staged_copy): 1 MiB pieces dealt out statically;
+// memcpy by a team (the streamer's staging of pageable sources, lia_stream.hip::staged_copy): 1 MiB pieces dealt out statically;
 // n_threads <= 0 = at most 8 (a caller that never said how many CPUs it owns: the box may show 256 and grant 16).  One thread moves
 // ~10 GB/s, the link takes 53.
 extern "C" void lia_host_parallel_memcpy(void* dst, const void* src, size_t bytes, int n_threads) {

@@ -1,6 +1,6 @@
 // Llama-family element-wise kernels (BASELINE.json config 4; a build-defined extension -- the reference has no LIA
 // Llama path, decoder.py:121-169).  Rounding points follow HF transformers' eager bf16 Llama (modeling_llama.py).
-#include "lia_common.h"
+#include "lia_internal.h"
 
 // LlamaRMSNorm.forward: y = bf16( w * bf16( x * rsqrt(mean(x^2) + eps) ) ); one wave per row, 16-byte accesses.
 __global__ __launch_bounds__(256) void lia_rmsnorm_kernel(const bf16_t* __restrict__ x, long ldx, const bf16_t* __restrict__ w,

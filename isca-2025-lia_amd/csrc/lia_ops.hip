@@ -1,0 +1,298 @@
+// C ABI of liblia_hip.so (include/lia_hip.h), part 2: the sub-layer ops -- layernorm, linear, q | k | v projection, attention, embedding,
+// lm_head, sampling, scoring.  No kernels here: see lia_internal.h for the launchers.
+#include <algorithm>
+#include <cmath>
+
+#include "lia_internal.h"
+
+// ------------------------------------------------------------------------------------------------
+// sub-layer ops
+// ------------------------------------------------------------------------------------------------
+LiaOutMap plain_out(bf16_t* y, long ldy, int N) {
+  LiaOutMap om;
+  memset(&om, 0, sizeof(om));
+  om.base[0] = y;
+  om.ld[0] = ldy;
+  om.seg_n = N;
+  om.T = 1;
+  return om;
+}
+
+extern "C" int lia_layernorm(const lia_bf16* x, long ldx, const lia_bf16* g, const lia_bf16* b, lia_bf16* y, long ldy,
+                             long rows, int H, float eps, void* stream) {
+  if (!x || !g || !b || !y) { lia_set_error("lia_layernorm: NULL tensor"); return LIA_ERR_MISSING; }
+  if (rows < 0 || H <= 0 || H % 8) { lia_set_error("lia_layernorm: rows=%ld H=%d (H %% 8)", rows, H); return LIA_ERR_INVALID; }
+  lia_layernorm_launch(x, ldx, g, b, y, ldy, rows, H, eps, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+int gemm_checked(lia_ctx* ctx, const bf16_t* x, long ldx, const bf16_t* w, int M, int N, int K, const LiaEpilogue& ep, const LiaOutMap& om,
+                 float* ws, size_t ws_bytes, int split, hipStream_t st, const LiaPost* post, int* post_done) {
+  if (N % 16 || K % 64) {
+    lia_set_error("linear: N=%d must be a multiple of 16 and K=%d of 64", N, K);
+    return LIA_ERR_INVALID;
+  }
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int regime = 0;
+  const bool timed = ctx && ctx->prof_on && ctx->prof_recs->size() < ctx->prof_cap && (ctx->prof_seen++ % ctx->prof_stride) == 0;
+  if (timed) {
+    size_t i = ctx->prof_recs->size();
+    e0 = (*ctx->prof_events)[2 * i];
+    e1 = (*ctx->prof_events)[2 * i + 1];
+  }
+  int rc = lia_gemm_launch(x, ldx, w, (long)K, M, N, K, &ep, &om, ws, ws_bytes, ctx ? &ctx->gemm_opts : nullptr, split, st, e0, e1, &regime, post, post_done);
+  if (timed && rc == 0 && regime != 0) {
+    // algorithmic traffic of the op: the weight once, the activations in and out once
+    double bytes = 2.0 * ((double)N * K + (double)M * K + (double)M * N);
+    ctx->prof_recs->push_back({regime, bytes, 2.0 * M * (double)N * K});
+  }
+  if (rc) {
+    lia_set_error("linear: unsupported shape or layout M=%d N=%d K=%d ldx=%ld ldy=%ld ldr=%ld (lia_hip.h, lia_linear: 16-byte x / w rows, "
+                  "whole 8-byte stores, 16-byte ones unless M <= 256 and K %% 128 == 0)", M, N, K, ldx, om.ld[0], ep.residual ? ep.ldr : 0L);
+    return LIA_ERR_INVALID;
+  }
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+extern "C" int lia_linear(lia_ctx* ctx, const lia_bf16* x, long ldx, const lia_bf16* w, const lia_bf16* bias,
+                          const lia_bf16* residual, long ldr, lia_bf16* y, long ldy, int M, int N, int K, int relu,
+                          int split_k, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!x || !w || !y) { lia_set_error("lia_linear: NULL tensor"); return LIA_ERR_MISSING; }
+  if (M < 0 || N <= 0 || K <= 0) { lia_set_error("lia_linear: M=%d N=%d K=%d", M, N, K); return LIA_ERR_INVALID; }
+  LiaEpilogue ep{bias, residual, ldr, relu};
+  LiaOutMap om = plain_out(y, ldy, N);
+  size_t need = lia_gemm_workspace_bytes(M, N);          // split-K slabs: 8 for M <= 256, up to 4 for the tiled kernel below M = 2048
+  size_t have = std::min(need, ctx->ws_bytes);
+  ws_invalidate(ctx);
+  return gemm_checked(ctx, x, ldx, w, M, N, K, ep, om, (float*)ctx->ws, have, split_k, (hipStream_t)stream);
+}
+
+int qkv_project(lia_ctx* ctx, const bf16_t* x, const bf16_t* w, const bf16_t* bias, bf16_t* qout, bf16_t* kdst, bf16_t* vdst,
+                bool kv_cache_mode, int B, int T, int H, int cache_batch, int b0, int pos0, float* ws, size_t ws_bytes, hipStream_t st) {
+  LiaEpilogue ep{bias, nullptr, 0, 0};
+  LiaOutMap om;
+  memset(&om, 0, sizeof(om));
+  om.base[0] = qout; om.base[1] = kdst; om.base[2] = vdst;
+  om.ld[0] = om.ld[1] = om.ld[2] = H;
+  om.cache_mode[1] = om.cache_mode[2] = kv_cache_mode ? 1 : 0;
+  om.seg_n = H; om.T = T; om.Bc = cache_batch; om.b0 = b0; om.pos0 = pos0;
+  return gemm_checked(ctx, x, H, w, B * T, 3 * H, H, ep, om, ws, ws_bytes, 0, st);
+}
+
+extern "C" int lia_qkv_project(lia_ctx* ctx, const lia_bf16* x, const lia_bf16* w, const lia_bf16* bias, lia_bf16* qout,
+                               lia_bf16* kcache, lia_bf16* vcache, int B, int T, int H, int cache_batch, int b0, int pos0,
+                               void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!x || !w || !qout || !kcache || !vcache) { lia_set_error("lia_qkv_project: NULL tensor"); return LIA_ERR_MISSING; }
+  if (B <= 0 || T <= 0 || b0 < 0 || b0 + B > cache_batch || pos0 < 0) {
+    lia_set_error("lia_qkv_project: B=%d T=%d cache_batch=%d b0=%d pos0=%d", B, T, cache_batch, b0, pos0);
+    return LIA_ERR_INVALID;
+  }
+  size_t need = (size_t)B * T <= 256 ? (size_t)8 * B * T * 3 * H * 4 : 0;
+  ws_invalidate(ctx);
+  return qkv_project(ctx, x, w, bias, qout, kcache, vcache, true, B, T, H, cache_batch, b0, pos0, (float*)ctx->ws,
+                     std::min(need, ctx->ws_bytes), (hipStream_t)stream);
+}
+
+extern "C" int lia_attention(const lia_bf16* q, long ldq, const lia_bf16* kcache, const lia_bf16* vcache, lia_bf16* out,
+                             long ldo, int B, int T, int S, int heads, int head_dim, int cache_batch, int b0, void* stream) {
+  if (!q || !kcache || !vcache || !out) { lia_set_error("lia_attention: NULL tensor"); return LIA_ERR_MISSING; }
+  if (B <= 0 || T <= 0 || S < T || b0 < 0 || b0 + B > cache_batch) {
+    lia_set_error("lia_attention: B=%d T=%d S=%d cache_batch=%d b0=%d", B, T, S, cache_batch, b0);
+    return LIA_ERR_INVALID;
+  }
+  if (T > 1 && S != T) { lia_set_error("lia_attention: multi-token blocks only as a prefill (S == T), got S=%d T=%d", S, T); return LIA_ERR_INVALID; }
+  if (lia_attn_dispatch(q, ldq, kcache, vcache, out, ldo, B, T, S - T, heads, heads, head_dim, cache_batch, b0, 0, nullptr, 0, (hipStream_t)stream)) {
+    lia_set_error("lia_attention: head_dim %d unsupported (32/64/128), S=%d too long, or a cache of %d batch rows x %d values per key row beyond the d = 128 prefill kernel's 32-bit staging offsets (64 key rows < 4 GiB)",
+                  head_dim, S, cache_batch, heads * head_dim);
+    return LIA_ERR_INVALID;
+  }
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+extern "C" int lia_embed(const int64_t* ids, const lia_bf16* tok, const lia_bf16* pos, lia_bf16* y, int B, int T,
+                         int past_len, int H, void* stream) {
+  if (!ids || !tok || !pos || !y) { lia_set_error("lia_embed: NULL tensor"); return LIA_ERR_MISSING; }
+  if (B <= 0 || T <= 0 || past_len < 0 || H % 8) { lia_set_error("lia_embed: B=%d T=%d past=%d H=%d", B, T, past_len, H); return LIA_ERR_INVALID; }
+  lia_embed_launch(ids, tok, pos, y, B, T, past_len, H, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+extern "C" int lia_embed_padded(const int64_t* ids, const lia_bf16* tok, const lia_bf16* pos, lia_bf16* y, int B, int T,
+                                int past_len, int H, const int32_t* starts, void* stream) {
+  if (!ids || !tok || !pos || !y || !starts) { lia_set_error("lia_embed_padded: NULL tensor"); return LIA_ERR_MISSING; }
+  if (B <= 0 || T <= 0 || past_len < 0 || H % 8) { lia_set_error("lia_embed_padded: B=%d T=%d past=%d H=%d", B, T, past_len, H); return LIA_ERR_INVALID; }
+  lia_embed_padded_launch(ids, tok, pos, y, B, T, past_len, H, starts, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+extern "C" int lia_llama_embed(const int64_t* ids, const lia_bf16* tok, lia_bf16* y, int B, int T, int H, void* stream) {
+  if (!ids || !tok || !y) return LIA_ERR_MISSING;
+  if (B <= 0 || T <= 0 || H % 8) return LIA_ERR_INVALID;
+  lia_embed_tokens_launch(ids, tok, y, (long)B * T, H, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+extern "C" int lia_attention_padded(const lia_bf16* q, long ldq, const lia_bf16* kcache, const lia_bf16* vcache, lia_bf16* out,
+                                    long ldo, int B, int T, int S, int heads, int head_dim, int cache_batch, int b0,
+                                    const int32_t* starts, void* stream) {
+  if (!q || !kcache || !vcache || !out || !starts) { lia_set_error("lia_attention_padded: NULL tensor"); return LIA_ERR_MISSING; }
+  if (B <= 0 || T <= 0 || S < T || b0 < 0 || b0 + B > cache_batch || (T > 1 && S != T)) {
+    lia_set_error("lia_attention_padded: B=%d T=%d S=%d cache_batch=%d b0=%d (multi-token blocks only as a prefill, S == T)", B, T, S,
+                  cache_batch, b0);
+    return LIA_ERR_INVALID;
+  }
+  if (lia_attn_dispatch(q, ldq, kcache, vcache, out, ldo, B, T, S - T, heads, heads, head_dim, cache_batch, b0, 0, starts, 0, (hipStream_t)stream)) {
+    lia_set_error("lia_attention_padded: head_dim %d unsupported (32/64/128), S=%d too long, or a cache of %d batch rows x %d values per key row beyond the d = 128 prefill kernel's 32-bit staging offsets",
+                  head_dim, S, cache_batch, heads * head_dim);
+    return LIA_ERR_INVALID;
+  }
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+// norm_b == nullptr: RMSNorm (Llama), else LayerNorm
+static int lm_head_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, int B, int T, int H, const bf16_t* norm_w, const bf16_t* norm_b,
+                        const bf16_t* emb, int vocab, float eps, int suppress_token, bf16_t* logits, int64_t* next_ids, hipStream_t st) {
+  size_t scratch = align_up((size_t)B * H * 2, 256);
+  size_t gemm_need = (size_t)8 * B * vocab * 4;
+  if (ctx->ws_bytes < scratch) { lia_set_error("%s: workspace too small", who); return LIA_ERR_MEMORY; }
+  ws_invalidate(ctx);
+  bf16_t* lno = (bf16_t*)ctx->ws;
+  // hidden[:, -1, :] -> final LN (lia/modeling_opt.py:1563 applies it to all positions; only the last one feeds
+  // lm_head, models.py:424-431, and LN is row-wise, so the other rows are never needed)
+  if (norm_b) lia_layernorm_launch(hidden + (long)(T - 1) * H, (long)T * H, norm_w, norm_b, lno, H, B, H, eps, st);
+  else lia_rmsnorm_launch(hidden + (long)(T - 1) * H, (long)T * H, norm_w, lno, H, B, H, eps, st);
+  LiaEpilogue ep{nullptr, nullptr, 0, 0};
+  LiaOutMap om = plain_out(logits, vocab, vocab);
+  size_t have = ctx->ws_bytes - scratch;
+  int rc = gemm_checked(ctx, lno, H, emb, B, vocab, H, ep, om, (float*)(ctx->ws + scratch), std::min(have, gemm_need), 0, st);
+  if (rc) return rc;
+  lia_argmax_launch(logits, next_ids, B, vocab, suppress_token, st);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+extern "C" int lia_lm_head(lia_ctx* ctx, const lia_bf16* hidden, int B, int T, int H, const lia_bf16* lnw,
+                           const lia_bf16* lnb, const lia_bf16* emb, int vocab, float eps, int suppress_token,
+                           lia_bf16* logits, int64_t* next_ids, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!hidden || !lnw || !lnb || !emb || !logits || !next_ids) { lia_set_error("lia_lm_head: NULL tensor"); return LIA_ERR_MISSING; }
+  if (B <= 0 || B > 256 || T <= 0 || vocab % 16) { lia_set_error("lia_lm_head: B=%d (<=256) T=%d vocab=%d (%%16)", B, T, vocab); return LIA_ERR_INVALID; }
+  return lm_head_impl("lia_lm_head", ctx, hidden, B, T, H, lnw, lnb, emb, vocab, eps, suppress_token, logits, next_ids, (hipStream_t)stream);
+}
+
+extern "C" int lia_llama_lm_head(lia_ctx* ctx, const lia_bf16* hidden, int B, int T, int H, const lia_bf16* normw, const lia_bf16* lm,
+                                 int vocab, float eps, int suppress_token, lia_bf16* logits, int64_t* next_ids, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!hidden || !normw || !lm || !logits || !next_ids) { lia_set_error("lia_llama_lm_head: NULL tensor"); return LIA_ERR_MISSING; }
+  if (B <= 0 || B > 256 || T <= 0 || vocab % 16) { lia_set_error("lia_llama_lm_head: B=%d T=%d vocab=%d", B, T, vocab); return LIA_ERR_INVALID; }
+  return lm_head_impl("lia_llama_lm_head", ctx, hidden, B, T, H, normw, nullptr, lm, vocab, eps, suppress_token, logits, next_ids, (hipStream_t)stream);
+}
+
+// temperature -> top-k -> top-p -> one draw per row (lia_sample.hip).  Any B; the row is read a fixed number of times.
+#define LIA_SAMPLE_MAX_VOCAB (256 * 8192)   // lia_sample.hip keeps one running sum per 8192-token tile in LDS
+extern "C" int lia_sample(lia_ctx* ctx, const lia_bf16* logits, long ld, int B, int vocab, float temperature, int top_k, float top_p,
+                          int suppress_token, const float* uniforms, int64_t* next_ids, float* stats, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!logits || !uniforms || !next_ids) {
+    lia_set_error("lia_sample: NULL %s", !logits ? "logits" : !uniforms ? "uniforms" : "next_ids");
+    return LIA_ERR_INVALID;
+  }
+  if (B <= 0) { lia_set_error("lia_sample: B=%d must be >= 1", B); return LIA_ERR_INVALID; }
+  if (vocab <= 0 || vocab > LIA_SAMPLE_MAX_VOCAB) { lia_set_error("lia_sample: vocab=%d must be in [1, %d]", vocab, LIA_SAMPLE_MAX_VOCAB); return LIA_ERR_INVALID; }
+  if (ld < vocab) { lia_set_error("lia_sample: ld=%ld < vocab=%d", ld, vocab); return LIA_ERR_INVALID; }
+  if (!(temperature > 0.f) || !std::isfinite(temperature)) { lia_set_error("lia_sample: temperature=%g must be finite and > 0", (double)temperature); return LIA_ERR_INVALID; }
+  if (top_k < 0) { lia_set_error("lia_sample: top_k=%d must be >= 0 (0: off)", top_k); return LIA_ERR_INVALID; }
+  if (!(top_p > 0.f && top_p <= 1.f)) { lia_set_error("lia_sample: top_p=%g must be in (0, 1] (1: off)", (double)top_p); return LIA_ERR_INVALID; }
+  if (suppress_token < -1 || suppress_token >= vocab) { lia_set_error("lia_sample: suppress_token=%d must be -1 or in [0, vocab)", suppress_token); return LIA_ERR_INVALID; }
+  lia_sample_launch(logits, ld, B, vocab, temperature, top_k, top_p, suppress_token, uniforms, next_ids, stats, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// scoring: log p(target) and the greedy token of every row (lia_score.hip; the chunk rule is stated in lia_hip.h)
+// ------------------------------------------------------------------------------------------------
+extern "C" int lia_token_logprobs(lia_ctx* ctx, const lia_bf16* logits, long ld, int M, int vocab, const int64_t* targets,
+                                  float* logprobs, int64_t* greedy_ids, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!logits || !targets || !logprobs || !greedy_ids) {
+    lia_set_error("lia_token_logprobs: NULL %s", !logits ? "logits" : !targets ? "targets" : !logprobs ? "logprobs" : "greedy_ids");
+    return LIA_ERR_INVALID;
+  }
+  if (M <= 0) { lia_set_error("lia_token_logprobs: M=%d must be >= 1", M); return LIA_ERR_INVALID; }
+  if (vocab <= 0) { lia_set_error("lia_token_logprobs: vocab=%d must be >= 1", vocab); return LIA_ERR_INVALID; }
+  if (ld < vocab) { lia_set_error("lia_token_logprobs: ld=%ld < vocab=%d", ld, vocab); return LIA_ERR_INVALID; }
+  lia_token_logprobs_launch(logits, ld, M, vocab, targets, logprobs, greedy_ids, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+extern "C" int lia_lm_score_chunk_rows(size_t workspace_bytes, int M, int H, int vocab) {
+  if (M <= 0 || H <= 0 || vocab <= 0 || workspace_bytes < 512) return 0;
+  const size_t per_row = 2 * (size_t)H + 2 * (size_t)vocab;
+  size_t c = std::min({(size_t)M, (size_t)LIA_SCORE_MAX_CHUNK, (workspace_bytes - 512) / per_row});
+  if (c < (size_t)M) c = c / 256 * 256;
+  return c < (size_t)std::min(M, 256) ? 0 : (int)c;
+}
+
+extern "C" size_t lia_lm_score_workspace_bytes(int M, int H, int vocab) {
+  if (M <= 0 || H <= 0 || vocab <= 0) return 0;
+  return 512 + (size_t)std::min(M, LIA_SCORE_MAX_CHUNK) * (2 * (size_t)H + 2 * (size_t)vocab);
+}
+
+// norm_b == nullptr: RMSNorm (Llama), else LayerNorm
+static int lm_score_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int M, int H, const bf16_t* norm_w,
+                         const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, const int64_t* targets, float* logprobs,
+                         int64_t* greedy_ids, hipStream_t st) {
+  if (M <= 0) { lia_set_error("%s: M=%d must be >= 1", who, M); return LIA_ERR_INVALID; }
+  if (H <= 0 || H % 64 || vocab <= 0 || vocab % 16) { lia_set_error("%s: H=%d (%%64) vocab=%d (%%16)", who, H, vocab); return LIA_ERR_INVALID; }
+  if (ldh < H || ldh % 8) { lia_set_error("%s: ldh=%ld must be >= H=%d and a multiple of 8", who, ldh, H); return LIA_ERR_INVALID; }
+  const int c = lia_lm_score_chunk_rows(ctx->ws_bytes, M, H, vocab);
+  if (c <= 0) {
+    lia_set_error("%s: a workspace of %zu bytes holds no chunk of %d rows (normed rows [c, %d] + logits [c, %d] in bf16 need %zu)", who,
+                  ctx->ws_bytes, std::min(M, 256), H, vocab, (size_t)512 + (size_t)std::min(M, 256) * (2 * (size_t)H + 2 * (size_t)vocab));
+    return LIA_ERR_MEMORY;
+  }
+  ws_invalidate(ctx);
+  bf16_t* lno = (bf16_t*)ctx->ws;
+  bf16_t* logits = (bf16_t*)(ctx->ws + align_up((size_t)c * H * 2, 256));
+  const LiaEpilogue ep{nullptr, nullptr, 0, 0};
+  for (int r0 = 0; r0 < M; r0 += c) {
+    const int n = std::min(c, M - r0);
+    const bf16_t* x = hidden + (long)r0 * ldh;
+    if (norm_b) lia_layernorm_launch(x, ldh, norm_w, norm_b, lno, H, n, H, eps, st);
+    else lia_rmsnorm_launch(x, ldh, norm_w, lno, H, n, H, eps, st);
+    const LiaOutMap om = plain_out(logits, vocab, vocab);
+    const int rc = gemm_checked(ctx, lno, H, emb, n, vocab, H, ep, om, nullptr, 0, 0, st);    // no slabs: never split over K
+    if (rc) return rc;
+    lia_token_logprobs_launch(logits, vocab, n, vocab, targets + r0, logprobs + r0, greedy_ids + r0, st);
+  }
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+extern "C" int lia_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int M, int H, const lia_bf16* lnw, const lia_bf16* lnb,
+                            const lia_bf16* emb, int vocab, float eps, const int64_t* targets, float* logprobs, int64_t* greedy_ids,
+                            void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!hidden || !lnw || !lnb || !emb || !targets || !logprobs || !greedy_ids) { lia_set_error("lia_lm_score: NULL tensor"); return LIA_ERR_MISSING; }
+  return lm_score_impl("lia_lm_score", ctx, hidden, ldh, M, H, lnw, lnb, emb, vocab, eps, targets, logprobs, greedy_ids, (hipStream_t)stream);
+}
+
+extern "C" int lia_llama_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int M, int H, const lia_bf16* normw,
+                                  const lia_bf16* lm, int vocab, float eps, const int64_t* targets, float* logprobs,
+                                  int64_t* greedy_ids, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!hidden || !normw || !lm || !targets || !logprobs || !greedy_ids) { lia_set_error("lia_llama_lm_score: NULL tensor"); return LIA_ERR_MISSING; }
+  return lm_score_impl("lia_llama_lm_score", ctx, hidden, ldh, M, H, normw, nullptr, lm, vocab, eps, targets, logprobs, greedy_ids,
+                       (hipStream_t)stream);
+}

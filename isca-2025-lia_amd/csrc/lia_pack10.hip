@@ -10,8 +10,7 @@
 // History: pack12 (r01: one 4-bit code per value against a 14-binade window, 12 bits) and pack11 (r01: a 3-bit code in bit-planes
 // + a 4-bit overflow stream, 11.13 bits) were the first two generations; pack10 replaced them as the default in r02 and they were
 // removed in r05 (git history; LABNOTES.md has their measurements: 88.7 / 95.7 / 98.6 decode tokens/s for 12 / 11 / 10).
-#include "../../include/lia_hip.h"
-#include "lia_common.h"
+#include "lia_internal.h"
 #include <string.h>
 
 static inline size_t lp12_align(size_t v) { return (v + 255) / 256 * 256; }

@@ -23,12 +23,9 @@
 //   * Buffer: [header 256][directory: (chunks + 1) x {u32 first word, u32 first table entry}][table entries][final states: chunks x
 //     64 u32][plane a: n bytes][words: u16 + 2 bytes of padding], every section 256-byte aligned.
 //     Per value: 8 (plane) + 2.55 (words) + 0.031 (states) + 0.009 (tables) + 0.001 (directory) bits.
-#include "../../include/lia_hip.h"
-#include "lia_common.h"
+#include "lia_internal.h"
 #include <string.h>
 #include <vector>
-
-extern "C" size_t lia_pack10_bound(size_t n_values);
 
 constexpr uint32_t LP10A_MAGIC = 0x4131504cu;     // 'LP1A'
 constexpr int LP10A_CHUNK_SHIFT = 16;             // 65536 values per chunk

@@ -15,7 +15,7 @@
 // Membership is a key comparison: K = {key >= kappa_lo(t)}, kappa_lo(t) the smallest key whose s is >= t (a 16-step bisection by
 // one thread).  That is s_i >= t exactly, also where two keys give the same s (-0 / +0, or an s that rounds to 0 or inf).  A token
 // whose s is -inf (the suppressed one) carries no mass and is never kept.  Logits are finite or +-inf, not NaN.
-#include "lia_common.h"
+#include "lia_internal.h"
 
 #define SMP_TILE (LIA_ROW_THREADS * 8)   // tokens per pass-E tile: 8 consecutive tokens per thread
 #define SMP_MAX_TILES 256                // pass-E carries kept in LDS: vocab <= 256 * 8192 (lia_sample checks)

@@ -12,8 +12,7 @@
 // not taken -- its extra roundings have no bound as short as the one above.
 // exp is ocml's expf (about 1 ulp), log is logf.  -inf logits add exactly 0; a row of nothing but -inf has no distribution and
 // gives NaN.  A target outside [0, vocab) -- -1 is the documented "no target" -- gives 0.0.  Logits are finite or +-inf, not NaN.
-#include "../../include/lia_hip.h"
-#include "lia_common.h"
+#include "lia_internal.h"
 
 static_assert(LIA_ROW_THREADS == LIA_SCORE_ROW_THREADS, "lia_hip.h states the row kernel's lane count for the error bound of its tests");
 

@@ -199,7 +199,7 @@ def estimate(shape, B, T, new, gpu_percentage, decoding_policy, box=None, kv_in_
         prefill_ms += max(0.0, (n_gpu + 1) * pre_layer_ms - 2 * copy_ms)      # head bubble with two slots
     emb_gb = 2 * shape.vocab * H * 2 / 1e9
     # HBM beside the resident layers and the caches: four streamer slots + their wire-format staging areas, the context's workspace
-    # for the prefill's B x T rows (lia_api.hip ws_layout: 6 row buffers of H, one of F, two K/V slabs of 2 H), the two hidden-state
+    # for the prefill's B x T rows (lia_layer.hip ws_layout: 6 row buffers of H, one of F, two K/V slabs of 2 H), the two hidden-state
     # buffers, lm_head's logits.  (r06: the estimate carried two slots and a constant; at --batch-size 900 the planner's pick ran
     # out of HBM in lia_ctx_create -- results/r06_matrix_offline_opt30b_32_256_b900_p02_g0_autoplan.json of the first attempt)
     rows = B * T

@@ -5,13 +5,11 @@ test_gpu_attention_families.py's own comparison and plumbing; and the property t
 for bit rows pos0 .. pos0 + T - 1 of the prefill launch over pos0 + T tokens.
 
 S = pos0 + T is what attn_families.make / reference take: T queries at positions S - T .. S - 1 over S keys."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import attn_families as F
-from test_gpu_attention_families import ATTN, B0, BC_EXTRA, OUT_SLACK, VARIANTS, _bind_padded, check_case, dev  # noqa: F401
+from test_gpu_attention_families import ATTN, B0, BC_EXTRA, OUT_SLACK, VARIANTS, check_case, dev  # noqa: F401
 from test_gpu_kernel_variants import (DECODE_G, SENTINEL, X_GAP, gpu, host, pitched, prefill_variant,  # noqa: F401  (gpu: fixture)
                                       sentinel_buf)
 
@@ -45,19 +43,10 @@ def starts_for(B, pos0):
     return np.array([pool[(b + 1) % len(pool)] for b in range(B)], np.int32)
 
 
-def _bind():
-    from lia_amd import _native as N
-    vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-    fn = N.lib().lia_attn_append_launch                                                     # copied from the .hip signature
-    fn.restype, fn.argtypes = ci, [vp, cl, vp, vp, vp, cl, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]
-    _bind_padded()
-
-
 def append(gpu, q, kc, vc, pos0, heads, kvh, d, ps, starts=None):
     """q [B, T, H], caches [.., Bc = B + 2, kvh, d] (bf16 bits) through lia_attn_append_launch, test_gpu_attention_families.run_case's
     plumbing: pitched q / out with NaN / sentinel gaps, served rows b0 = 1 .. B, the cache unchanged.  -> out [B, T, H]"""
     torch, launch = gpu
-    _bind()
     B, T, H = q.shape
     Bc = kc.shape[1]
     assert Bc == B + BC_EXTRA
@@ -126,7 +115,6 @@ def test_append_is_the_prefill_rows_bit_for_bit(gpu, family, variant, ps, pos0, 
     ldq, ldo = H + 16, H + 24
     for starts in (None, starts_for(B, pos0)):
         q, kc, vc = F.make(family, B, S, S, heads, kvh, d, ps, starts=starts, b0=B0, Bc=Bc)
-        _bind()
         qd = pitched(torch, dev(torch, q.reshape(B * S, H)), ldq, X_GAP)
         kd, vd = dev(torch, kc), dev(torch, vc)
         full = sentinel_buf(torch, (B * S + OUT_SLACK, ldo))
@@ -147,7 +135,6 @@ def test_launcher_refusals(gpu):
     """-1 where the prefill launcher returns it: an unsupported head_dim, heads not a multiple of kv_heads, and at d = 128 a cache
     whose 64 key rows reach 4 GiB (nothing is launched, so no cache of that size is needed)"""
     torch, launch = gpu
-    _bind()
     z = torch.zeros(8, dtype=torch.int16, device="cuda")
     assert launch("lia_attn_append_launch", z, 48, z, z, z, 48, 1, 2, 3, 1, 1, 48, 1, 0, 0, None) == -1
     assert launch("lia_attn_append_launch", z, 128, z, z, z, 128, 1, 2, 3, 3, 2, 64, 1, 0, 0, None) == -1

@@ -52,15 +52,6 @@ def starts_for(B, n):
     return np.array([pool[b % len(pool)] for b in range(B)], np.int32)
 
 
-def _bind_padded():
-    import ctypes
-    from lia_amd import _native as N
-    vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-    for name in ("lia_attn_prefill_padded_launch", "lia_attn_decode_padded_launch"):       # copied from the .hip signatures
-        fn = getattr(N.lib(), name)
-        fn.restype, fn.argtypes = ci, [vp, cl, vp, vp, vp, cl, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]
-
-
 def dev(torch, a):
     return torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).cuda()
 
@@ -71,7 +62,6 @@ def run_case(gpu, family, B, T, S, heads, kvh, d, ps, starts=None, shifted=False
     shifted: every row of the padded prefill is launched once more alone, UNPADDED, on its own shifted sequence (pointers moved to
     the row's start) and must equal the padded launch's row bit for bit."""
     torch, launch = gpu
-    _bind_padded()
     Bc, H = B + BC_EXTRA, heads * d
     ldq, ldo = H + 16, H + 24
     q, kc, vc = F.make(family, B, T, S, heads, kvh, d, ps, starts=starts, b0=B0, Bc=Bc)

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import f64_ref as R
+import launchers
 
 pytestmark = pytest.mark.gpu
 
@@ -29,11 +30,11 @@ RMS_REG = (4, 8, 16)                # (lia_llama.hip:108-112)
 ROPE_VEC_D, ROPE_VEC_STRIDE = 16, 8     # the vector kernel needs d % 16 == 0 and row_stride % 8 == 0 (lia_llama.hip:171)
 SILU_MAX_BLOCKS = 4096              # grid of at most this many 256-thread blocks, grid-stride beyond (lia_llama.hip:205-207)
 GU_BLOCK = 32                       # LIA_GU_BLOCK, lia_common.h
-ATTN_QBLOCK = 128                   # query rows per block of the prefill kernels (lia_attention.hip:927)
-XCD_GROUPS = 8                      # B * kv_heads % 8 == 0 or >= 64: the XCD-aware order (lia_attention.hip:942)
+ATTN_QBLOCK = 128                   # query rows per block of the prefill kernels (lia_attention.hip:1055)
+XCD_GROUPS = 8                      # B * kv_heads % 8 == 0 or >= 64: the XCD-aware order (lia_attention.hip:1040)
 XCD_MANY_GROUPS = 64
-DECODE_LDS = 160 * 1024             # decode's LDS need (G Spad + 4 G D + 8 G) floats must fit (lia_attention.hip:966-969)
-DECODE_G = (1, 2, 4, 8)             # the instantiated group sizes (lia_attention.hip:976-981)
+DECODE_LDS = 160 * 1024             # decode's LDS need (G Spad + 4 G D + 8 G) floats must fit (lia_attention.hip:1136-1137)
+DECODE_G = (1, 2, 4, 8)             # the instantiated group sizes (lia_attention.hip:1148-1154)
 ARGMAX_VEC = 8                      # vocab % 8 == 0: 16-byte loads, else the scalar loop (lia_elementwise.hip:202)
 
 # ---- bounds (see the module docstring; margins measured in the docstrings) --------------------------------------------------
@@ -77,20 +78,7 @@ def gpu():
     import torch
     assert torch.cuda.is_available(), "these tests need the MI355X"
     from lia_amd import _native as N, ops
-    lib = N.lib()
-    vp, ci, cl, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
-    sig = {   # copied from the .hip signatures
-        "lia_layernorm_launch": (None, [vp, cl, vp, vp, vp, cl, cl, ci, cf, vp]),
-        "lia_rmsnorm_launch": (None, [vp, cl, vp, vp, cl, cl, ci, cf, vp]),
-        "lia_rope_launch": (None, [vp, cl, vp, vp, cl, ci, ci, ci, ci, ci, vp]),
-        "lia_silu_mul_launch": (None, [vp, vp, cl, ci, ci, vp]),
-        "lia_attn_prefill_launch": (ci, [vp, cl, vp, vp, vp, cl, ci, ci, ci, ci, ci, ci, ci, ci, vp]),
-        "lia_attn_decode_launch": (ci, [vp, cl, vp, vp, vp, cl, ci, ci, ci, ci, ci, ci, ci, ci, vp]),
-        "lia_argmax_launch": (None, [vp, vp, ci, ci, ci, vp]),
-    }
-    for name, (res, args) in sig.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
+    lib = launchers.bind(N.lib())
     ctx = ops.Context(0, 1 << 20)
 
     def launch(name, *args):
@@ -205,7 +193,7 @@ ROPE_CASES = ([(d, heads, m, 8) for d in (64, 128) for heads in (1, 8, 40) for m
 
 
 def rope_map(m):
-    """(rows, pos0, pos_mod, pos_div) of the three position maps lia_llama_layer_forward uses (lia_api.hip:897-903):
+    """(rows, pos0, pos_mod, pos_div) of the three position maps lia_llama_layer_forward uses (lia_layer.hip, the RoPE launches):
     q rows b*T + t; cache rows t*Bc + b; one minibatch's rows of one cache position (pos_div = Bc + B)"""
     if m == "q":
         return ROPE_B * ROPE_T, ROPE_MAX_POS - ROPE_T, ROPE_T, 0

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import launchers
 import synth
 from test_gpu_ops import assert_close, to_bits, to_dev
 
@@ -92,10 +93,7 @@ def test_grouped_decode_attention_d128(B, S, kvh, oracle):
     step, against a plain fp32 restatement of HF's eager grouped attention at one query position."""
     import torch
     from lia_amd import _native as N, ops
-    lib = N.lib()
-    vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-    lib.lia_attn_decode_launch.argtypes = [vp, cl, vp, vp, vp, cl, ci, ci, ci, ci, ci, ci, ci, ci, vp]
-    lib.lia_attn_decode_launch.restype = ci
+    lib = launchers.bind(N.lib())
     ctx = ops.Context(0, 1 << 20)
     G, d = 4, 128
     heads = kvh * G

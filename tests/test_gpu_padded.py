@@ -1,8 +1,6 @@
 """Left-padded batches on the MI355X: every padded kernel instantiation against tests/padded_ref.py, the padded embedding, and
 generate(..., attention_mask=) on small OPTs (d 128: the tuned prefill kernel, d 64: the generic one) -- each row of a padded
 batch against the oracle's run of that row ALONE and unpadded, and against the product's own B = 1 run of the row."""
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -17,13 +15,6 @@ GARBAGE_K, GARBAGE_V = 30000.0, -20000.0        # K / V rows at pad positions: l
 START_POOL = (0, 1, 31, 32, 63, 64, 65, 127, 128, 129)
 
 
-def _bind(lib):
-    vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-    for name in ("lia_attn_prefill_padded_launch", "lia_attn_decode_padded_launch"):
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = ci, [vp, cl, vp, vp, vp, cl, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]
-
-
 def _starts(B, n, seed):
     pool = [s for s in START_POOL if s <= n - 1] + [n - 1]
     rs = np.random.RandomState(seed)
@@ -36,8 +27,6 @@ def _bf16_fill(torch, v):
 
 def run_padded(gpu, B, T, S, heads, kvh, d, ps, starts, seed=7):
     torch, launch = gpu
-    from lia_amd import _native as N
-    _bind(N.lib())
     Bc, b0, H = B + 2, 1, heads * d
     q, kc, vc, out = KV.attn_buffers(torch, seed, B, T, S, heads, kvh, d, Bc, b0)
     for b, s in enumerate(starts):
