@@ -245,6 +245,21 @@ int lia_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int M, int H, c
                  void* stream);
 int lia_llama_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int M, int H, const lia_bf16* normw, const lia_bf16* lm,
                        int vocab, float eps, const int64_t* targets, float* logprobs, int64_t* greedy_ids, void* stream);
+/* ---- speculative verification: the greedy token behind every position of a draft block, and how much of the
+ * draft it confirms.  hidden [B * T, ldh]: the last layer's output for the block [pending | d_1 .. d_{T-1}] of every row.
+ * Final norm + lm_head GEMM per chunk exactly as lia_lm_score (same CHUNK RULE, same workspace, logits never materialised), then
+ *   greedy[b, t]  = first index of the row's maximum (lia_lm_head's tie rule); suppress_token >= 0 counts as -inf at t < n_suppress
+ *   accepted[b]   = the largest a <= T - 1 with block_ids[b, i + 1] == greedy[b, i] for all i < a; T - 1 where active[b] == 0
+ *   common[0]     = min_b accepted[b]          next[b] = greedy[b, common]
+ * block_ids: int64 [B, T]; active: int32 [B] or NULL (all active); greedy: int64 [B, T]; accepted, common: int32 [B], [1]; next:
+ * int64 [B] -- all on the device.  LIA_ERR_INVALID, by name: a NULL tensor other than active, B <= 0, T < 2, n_suppress outside
+ * [0, T], suppress_token not -1 or in [0, vocab), H % 64, vocab % 16, ldh < H or ldh % 8.  LIA_ERR_MEMORY as lia_lm_score. */
+int lia_lm_verify(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* lnw, const lia_bf16* lnb,
+                  const lia_bf16* emb, int vocab, float eps, int suppress_token, int n_suppress, const int64_t* block_ids,
+                  const int32_t* active, int64_t* greedy, int32_t* accepted, int32_t* common, int64_t* next, void* stream);
+int lia_llama_lm_verify(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* normw,
+                        const lia_bf16* lm, int vocab, float eps, int suppress_token, int n_suppress, const int64_t* block_ids,
+                        const int32_t* active, int64_t* greedy, int32_t* accepted, int32_t* common, int64_t* next, void* stream);
 
 /* ---- Llama-family layer (BASELINE.json config 4; build-defined: the reference's LlamaDecoderLayer_forward,
  * decoder.py:121-169, has no policy plumbing -- SURVEY.md quirk 3).  Arithmetic = HF transformers' eager bf16 Llama.
@@ -292,9 +307,14 @@ int lia_llama_decode_layers(lia_ctx* ctx, const lia_llama_desc* d, int n_layers,
  *     finished row, SiLU(gate) * up, RoPE); 0: every such op is a kernel of its own -- the same device functions on the same
  *     values, so the two routes agree bit for bit (tests/test_gpu_fused_combine.py).
  *   lia_ctx_get_counter(ctx, LIA_CNT_FUSED_COMBINE + kind), kind = 1 LayerNorm, 2 RMSNorm, 3 SiLU*up, 4 RoPE: fused combines
- *     launched through this context (tests assert the route was taken); -1 for an unknown key. */
-enum { LIA_OPT_FUSE_COMBINE = 1 };
-enum { LIA_CNT_FUSED_COMBINE = 100 };
+ *     launched through this context (tests assert the route was taken); -1 for an unknown key.
+ *   LIA_OPT_BLOCK_ATTENTION (default 0): a block of T > 1 queries behind a non-empty cache takes the decode-shaped block
+ *     attention kernel where (heads / kv_heads) * T <= 16 and its scores fit the LDS, the append kernels otherwise; row t is then
+ *     bit for bit the decode attention over pos0 + t + 1 keys.  The speculative verify pass sets it around its layer calls, for
+ *     the shapes where the kernel was measured faster (speculative.block_attention_pays).
+ *   lia_ctx_get_counter(ctx, LIA_CNT_BLOCK_ATTENTION): block attention launches through this context. */
+enum { LIA_OPT_FUSE_COMBINE = 1, LIA_OPT_BLOCK_ATTENTION = 2 };
+enum { LIA_CNT_FUSED_COMBINE = 100, LIA_CNT_BLOCK_ATTENTION = 200 };
 int lia_ctx_set_option(lia_ctx* ctx, int key, long value);
 long lia_ctx_get_counter(lia_ctx* ctx, int key);
 

@@ -1181,9 +1181,259 @@ extern "C" int lia_attn_decode_padded_launch(const bf16_t* q, long ldq, const bf
   return decode_launch(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
 }
 
+// ---------------------------------------------------------------------------------------------
+// block (2 <= T <= 16 queries per row behind pos0 > 0 cached positions: the verification block of speculative decoding).  The decode
+// kernel, once, for the Q = G * T query slots of a (batch row, KV head): slot s = t * G + g is query t of head g of the group and
+// sees keys 0 .. lim[s] - 1, lim[s] = pos0 + t + 1 - kstart.  Every K / V row is read once for all slots.  A slot keeps the decode
+// kernel's assignment of keys to threads (key j: slot j % KPP of the workgroup; exp / sum: thread j % 256), its order of every sum
+// and its rounding points, and only gains the limit -- so row t is bit for bit lia_attn_decode_kernel over S = pos0 + t + 1 keys with
+// that query row (U, the rows in flight, batches the loads and is not part of any order).  Slots >= G * T (Q is the next
+// instantiated size) have lim = 0: no key, no output.
+// ---------------------------------------------------------------------------------------------
+template <int D, int Q, int PADDED>
+__global__ __launch_bounds__(256) void lia_attn_block_kernel(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ kc,
+                                                              const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int T,
+                                                              int pos0, int G, int kv_heads, int Bc, int b0, float scaling,
+                                                              int post_scale, const int* __restrict__ starts) {
+  constexpr int LPK = D / 8;          // lanes per key
+  constexpr int KPP = 256 / LPK;      // keys per pass of the workgroup
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int kstart = PADDED ? __builtin_amdgcn_readfirstlane(starts[blockIdx.y]) : 0;
+  const int S = pos0 + T - kstart;          // the keys of the last query of the block
+  const int Smin = S - T + 1;               // ... of the first: below it no slot needs a limit
+  const int Spad = (S + 3) & ~3;
+  float* sc = (float*)smem;                                   // [Q][Spad] scores -> probabilities
+  float* red = sc + (size_t)Q * Spad;                         // [4 waves][Q][D] partial outputs
+  float* scratch = red + (size_t)4 * Q * D;                   // [Q][8]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int kh = blockIdx.x, b = blockIdx.y;
+  const long kv_row = (long)Bc * kv_heads * D;
+  const bf16_t* kbase = kc + ((long)(b0 + b) * kv_heads + kh) * D + (long)kstart * kv_row;
+  const bf16_t* vbase = vc + ((long)(b0 + b) * kv_heads + kh) * D + (long)kstart * kv_row;
+  const float qscale = post_scale ? 1.0f : scaling;
+  const int sub = tid % LPK, kslot = tid / LPK;
+  const int n_slots = G * T;
+
+  typedef __attribute__((ext_vector_type(2))) __bf16 lia_bf16x2;
+  int lim[Q];
+  uint32_t qp[Q][4];
+#pragma unroll
+  for (int s = 0; s < Q; ++s) {
+    const int t = s / G, g = s - t * G;
+    lim[s] = s < n_slots ? Smin + t : 0;
+    uint4 v = uint4{0u, 0u, 0u, 0u};
+    if (s < n_slots) v = *(const uint4*)(q + ((long)b * T + t) * ldq + (long)(kh * G + g) * D + 8 * sub);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) qp[s][j] = pack_bf16x2(bf2f(w[j] & 0xffff) * qscale, bf2f(w[j] >> 16) * qscale);
+  }
+  float lmax[Q];
+#pragma unroll
+  for (int s = 0; s < Q; ++s) lmax[s] = -INFINITY;
+  constexpr int U = Q > 8 ? 4 : 8;   // key rows in flight per thread (the decode kernel's 8 while the slots' registers allow it)
+  // full passes end below Smin: every slot sees all of their keys, no checks; the passes behind carry the load bound and the limits
+  auto k_pass = [&](const int j0, auto tail) {
+    constexpr bool TAIL = decltype(tail)::value;
+    uint4 kv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int j = j0 + u * KPP + kslot;
+      if constexpr (TAIL) {
+        kv[u] = uint4{0u, 0u, 0u, 0u};
+        if (j < S) kv[u] = lia_ldg_stream(kbase + (long)j * kv_row + 8 * sub);
+      } else {
+        kv[u] = lia_ldg_stream(kbase + (long)j * kv_row + 8 * sub);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int j = j0 + u * KPP + kslot;
+      const uint32_t w[4] = {kv[u].x, kv[u].y, kv[u].z, kv[u].w};
+#pragma unroll
+      for (int s = 0; s < Q; ++s) {
+        float a = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          a = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(lia_bf16x2, qp[s][e]), __builtin_bit_cast(lia_bf16x2, w[e]), a, false);
+        if constexpr (LPK == 16) {
+          a += dpp_f32<0x128>(a);     // row_ror:8   (the decode kernel's butterfly)
+          a += dpp_f32<0x124>(a);     // row_ror:4
+          a += dpp_f32<0x4E>(a);      // quad_perm:[2,3,0,1]  (xor 2)
+          a += dpp_f32<0xB1>(a);      // quad_perm:[1,0,3,2]  (xor 1)
+        } else {
+#pragma unroll
+          for (int o = LPK / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+        }
+        if (!TAIL || j < lim[s]) {
+          float sv = rbf(a);
+          if (post_scale) sv = rbf(sv * scaling);
+          if (sub == 0) sc[s * Spad + j] = sv;
+          lmax[s] = fmaxf(lmax[s], sv);
+        }
+      }
+    }
+  };
+  const int s_full = Smin - Smin % (U * KPP);
+  for (int j0 = 0; j0 < s_full; j0 += U * KPP) k_pass(j0, std::false_type{});
+  for (int j0 = s_full; j0 < S; j0 += U * KPP) k_pass(j0, std::true_type{});
+#pragma unroll
+  for (int s = 0; s < Q; ++s) {
+    float m = wave_max(lmax[s]);
+    if (lane == 0) scratch[s * 8 + wave] = m;
+  }
+  __syncthreads();
+  float lrow[Q];
+#pragma unroll
+  for (int s = 0; s < Q; ++s) {
+    const float mrow = fmaxf(fmaxf(scratch[s * 8], scratch[s * 8 + 1]), fmaxf(scratch[s * 8 + 2], scratch[s * 8 + 3]));
+    float ls = 0.f;
+    for (int j = tid; j < lim[s]; j += 256) {
+      float e = __expf(sc[s * Spad + j] - mrow);
+      sc[s * Spad + j] = e;
+      ls += e;
+    }
+    ls = wave_sum(ls);
+    if (lane == 0) scratch[s * 8 + 4 + wave] = ls;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < Q; ++s) lrow[s] = scratch[s * 8 + 4] + scratch[s * 8 + 5] + scratch[s * 8 + 6] + scratch[s * 8 + 7];
+#pragma unroll
+  for (int s = 0; s < Q; ++s)
+    for (int j = tid; j < lim[s]; j += 256) sc[s * Spad + j] = rbf(sc[s * Spad + j] / lrow[s]);
+  __syncthreads();
+
+  float o[Q][8];
+#pragma unroll
+  for (int s = 0; s < Q; ++s)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[s][e] = 0.f;
+  auto v_pass = [&](const int j0, auto tail) {
+    constexpr bool TAIL = decltype(tail)::value;
+    uint4 vv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if constexpr (TAIL) {
+        vv[u] = uint4{0u, 0u, 0u, 0u};
+        if (j0 + u * KPP < S) vv[u] = lia_ldg_stream(vbase + (long)(j0 + u * KPP) * kv_row + 8 * sub);
+      } else {
+        vv[u] = lia_ldg_stream(vbase + (long)(j0 + u * KPP) * kv_row + 8 * sub);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int j = j0 + u * KPP;
+      const uint32_t w[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
+#pragma unroll
+      for (int s = 0; s < Q; ++s) {
+        if (!TAIL || j < lim[s]) {
+          const float p = sc[s * Spad + j];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { o[s][2 * e] += p * bf2f(w[e] & 0xffff); o[s][2 * e + 1] += p * bf2f(w[e] >> 16); }
+        }
+      }
+    }
+  };
+  for (int j0 = 0; j0 < s_full; j0 += U * KPP) v_pass(j0 + kslot, std::false_type{});
+  for (int j0 = s_full; j0 < S; j0 += U * KPP) v_pass(j0 + kslot, std::true_type{});
+#pragma unroll
+  for (int s = 0; s < Q; ++s)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float v = o[s][e];
+#pragma unroll
+      for (int off = LPK; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+      o[s][e] = v;
+    }
+  if (lane < LPK) {
+#pragma unroll
+    for (int s = 0; s < Q; ++s)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) red[((size_t)wave * Q + s) * D + 8 * sub + e] = o[s][e];
+  }
+  __syncthreads();
+  for (int idx = tid; idx < n_slots * D; idx += 256) {
+    const int s = idx / D, dd = idx - s * D;
+    const int t = s / G, g = s - t * G;
+    const float acc = (red[(size_t)s * D + dd] + red[((size_t)Q + s) * D + dd]) +
+                      (red[((size_t)2 * Q + s) * D + dd] + red[((size_t)3 * Q + s) * D + dd]);
+    out[((long)b * T + t) * ldo + (long)(kh * G + g) * D + dd] = f2bf(acc);
+  }
+}
+
+// the instantiated slot counts: every G * T up to LIA_BLOCK_MAX_Q runs in the smallest of them that holds it
+#define LIA_BLOCK_MAX_Q 16
+static int block_q_of(int n_slots) {
+  static const int qs[] = {2, 3, 4, 5, 6, 7, 8, 12, 16};
+  for (int v : qs)
+    if (n_slots <= v) return v;
+  return 0;
+}
+
+template <int D>
+static int launch_block(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T, int pos0,
+                        int heads, int kv_heads, int Bc, int b0, float scaling, int post_scale, const int* starts, hipStream_t st) {
+  const int G = heads / kv_heads;
+  const int Qv = block_q_of(G * T);
+  if (!Qv) return -1;
+  dim3 grid(kv_heads, B);
+  const int Spad = (pos0 + T + 3) & ~3;     // (a padded row holds fewer keys: the unpadded size bounds it)
+  size_t lds = ((size_t)Qv * Spad + (size_t)4 * Qv * D + (size_t)Qv * 8) * sizeof(float);
+  if (lds > 160 * 1024) return -1;
+#define LIA_BLK(QV)                                                                                                            \
+  if (starts) {                                                                                                                \
+    static bool attr = false;                                                                                                  \
+    if (!attr) { (void)hipFuncSetAttribute((const void*)lia_attn_block_kernel<D, QV, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
+    hipLaunchKernelGGL((lia_attn_block_kernel<D, QV, 1>), grid, dim3(256), lds, st, q, ldq, kc, vc, out, ldo, T, pos0, G, kv_heads, Bc, b0, scaling, post_scale, starts); \
+  } else {                                                                                                                     \
+    static bool attr = false;                                                                                                  \
+    if (!attr) { (void)hipFuncSetAttribute((const void*)lia_attn_block_kernel<D, QV, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
+    hipLaunchKernelGGL((lia_attn_block_kernel<D, QV, 0>), grid, dim3(256), lds, st, q, ldq, kc, vc, out, ldo, T, pos0, G, kv_heads, Bc, b0, scaling, post_scale, nullptr); \
+  }
+  switch (Qv) {
+    case 2: LIA_BLK(2) break;
+    case 3: LIA_BLK(3) break;
+    case 4: LIA_BLK(4) break;
+    case 5: LIA_BLK(5) break;
+    case 6: LIA_BLK(6) break;
+    case 7: LIA_BLK(7) break;
+    case 8: LIA_BLK(8) break;
+    case 12: LIA_BLK(12) break;
+    case 16: LIA_BLK(16) break;
+    default: return -1;
+  }
+#undef LIA_BLK
+  return 0;
+}
+
+// lia_attn_append_launch's arguments and meaning, for blocks of a few queries: row t of the result is bit for bit the decode launch
+// (padded, with starts) over S = pos0 + t + 1 keys with that query row.  Returns -1, nothing launched, for a d other than 32 / 64 /
+// 128, heads % kv_heads != 0, T < 2 or pos0 < 1, (heads / kv_heads) * T > LIA_BLOCK_MAX_Q, or scores + partials beyond 160 KB of LDS.
+extern "C" int lia_attn_block_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T,
+                                     int pos0, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts,
+                                     hipStream_t st) {
+  if (T < 2 || pos0 < 1 || kv_heads <= 0 || heads <= 0 || heads % kv_heads) return -1;
+  if (d != 32 && d != 64 && d != 128) return -1;
+  if ((long)(heads / kv_heads) * T > LIA_BLOCK_MAX_Q) return -1;
+  if (B <= 0) return 0;
+  const float scaling = 1.0f / sqrtf((float)d);
+  switch (d) {
+    case 128: return launch_block<128>(q, ldq, kc, vc, out, ldo, B, T, pos0, heads, kv_heads, Bc, b0, scaling, post_scale, starts, st);
+    case 64: return launch_block<64>(q, ldq, kc, vc, out, ldo, B, T, pos0, heads, kv_heads, Bc, b0, scaling, post_scale, starts, st);
+    default: return launch_block<32>(q, ldq, kc, vc, out, ldo, B, T, pos0, heads, kv_heads, Bc, b0, scaling, post_scale, starts, st);
+  }
+}
+
 // The attention launch of a call with T queries per row behind pos0 cached positions: see lia_internal.h for the rule.
 int lia_attn_dispatch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T, int pos0,
-                      int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, int tail, hipStream_t st) {
+                      int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, int tail, hipStream_t st,
+                      LiaAttnOpts* opts) {
+  // LIA_OPT_BLOCK_ATTENTION: the decode-shaped block launch where it takes the shape (-1: nothing was launched), else the append launch
+  if (T > 1 && pos0 > 0 && !tail && opts && opts->block_attention &&
+      lia_attn_block_launch(q, ldq, kc, vc, out, ldo, B, T, pos0, heads, kv_heads, d, Bc, b0, post_scale, starts, st) == 0) {
+    ++opts->block_launches;
+    return 0;
+  }
   if (T > 1 && pos0 > 0 && !tail) return lia_attn_append_launch(q, ldq, kc, vc, out, ldo, B, T, pos0, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
   const LiaTail t = lia_tail(tail, B, T, ldq);
   if (T == 1 || tail) return decode_launch(q + t.off, t.ld, kc, vc, out, ldo, B, pos0 + T, heads, kv_heads, d, Bc, b0, post_scale, starts, st);

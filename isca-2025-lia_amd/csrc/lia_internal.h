@@ -38,6 +38,10 @@ extern "C" void lia_sample_launch(const bf16_t* logits, long ld, int B, int voca
                                   const float* uniforms, int64_t* out, float* stats, hipStream_t st);
 extern "C" void lia_token_logprobs_launch(const bf16_t* logits, long ld, int M, int vocab, const int64_t* targets, float* logprobs,
                                           int64_t* greedy, hipStream_t st);
+extern "C" void lia_verify_argmax_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress, int T, int r0,
+                                         int64_t* greedy, hipStream_t st);
+extern "C" void lia_verify_accept_launch(const int64_t* block_ids, const int64_t* greedy, const int* active, int B, int T, int* accepted,
+                                         int* common, int64_t* next, hipStream_t st);
 // lia_llama.hip
 extern "C" void lia_rmsnorm_launch(const bf16_t* x, long ldx, const bf16_t* w, bf16_t* y, long ldy, long rows, int H, float eps,
                                    hipStream_t st);
@@ -62,6 +66,10 @@ extern "C" int lia_attn_decode_launch(const bf16_t* q, long ldq, const bf16_t* k
 extern "C" int lia_attn_decode_padded_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B,
                                              int S, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts,
                                              hipStream_t st);
+// the append launch's arguments for a block of (heads / kv_heads) * T <= 16 query slots; -1 (nothing launched) for any other shape
+extern "C" int lia_attn_block_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T,
+                                     int pos0, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts,
+                                     hipStream_t st);
 
 // ---- helpers shared by the API files: C++ linkage, kept out of the dynamic symbol table
 #define LIA_HIDDEN __attribute__((visibility("hidden")))
@@ -87,9 +95,14 @@ static inline LiaTail lia_tail(int tail, int B, int T, long H) {
 // lia_attention.hip: the one place that picks the attention launch of a call with T queries per row behind pos0 cached positions
 //   T > 1 && pos0 > 0 && !tail -> append;  T == 1 || tail -> decode over S = pos0 + T keys (tail: the last query of each row);
 //   otherwise -> prefill;  starts != NULL: the padded instantiations.  Returns the launcher's 0 / -1.
+//   opts (nullable = defaults), LIA_OPT_BLOCK_ATTENTION set: the append case goes to the block launch where that takes the shape
+struct LiaAttnOpts {
+  int block_attention;      // 0 (default): append launch; 1: lia_attn_block_launch first (the speculative verify pass sets it)
+  long block_launches;      // LIA_CNT_BLOCK_ATTENTION
+};
 LIA_HIDDEN int lia_attn_dispatch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T,
                                  int pos0, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, int tail,
-                                 hipStream_t st);
+                                 hipStream_t st, LiaAttnOpts* opts = nullptr);
 
 // ---- context (lia_ctx.hip)
 struct lia_ctx {
@@ -117,6 +130,7 @@ struct lia_ctx {
   long prof_host_attn_calls;
   double prof_host_attn_ms;
   LiaGemmOpts gemm_opts;     // per-context switches / counters of the GEMM launcher (lia_ctx_set_option, lia_ctx_get_counter)
+  LiaAttnOpts attn_opts;     // ... of the attention dispatch
   std::vector<hipEvent_t>* deliver_events;   // lia_kv_deliver tickets (events on the d2h stream), recycled round-robin
   std::vector<char>* deliver_pending;
   hipEvent_t deliver_t0, deliver_t1;         // timing events on the d2h stream around one batch of deliveries (lia_kv_deliver_batch_ms)

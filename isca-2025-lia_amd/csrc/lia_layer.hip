@@ -237,7 +237,7 @@ static int layer_forward_impl(lia_ctx* ctx, const lia_layer_desc* d, int policy,
     // GPU attention (attentions.py:443-536)
     // (tail: the last query of a causal block attends every key -- one decode-style query per row over the S rows just written)
     // (a block of T > 1 queries behind pos0 > 0 cached positions: the append kernels, query frame offset from the key frame)
-    if (lia_attn_dispatch(qb, H, kdst, vdst, ao, H, B, T, pos0, d->heads, d->heads, hd, dst_batch, dst_b0, 0, kst_dev, tail, st)) {
+    if (lia_attn_dispatch(qb, H, kdst, vdst, ao, H, B, T, pos0, d->heads, d->heads, hd, dst_batch, dst_b0, 0, kst_dev, tail, st, &ctx->attn_opts)) {
       lia_set_error("attention: unsupported head_dim %d / S %zu", hd, S);
       return LIA_ERR_INVALID;
     }
@@ -433,7 +433,7 @@ static int llama_layer_forward_impl(lia_ctx* ctx, const lia_llama_desc* d, const
                         kv->batch + B, st);
     }
   }
-  if (lia_attn_dispatch(qb, H, kv->k, kv->v, ao, H, B, T, pos0, d->heads, d->kv_heads, hd, kv->batch, b0, 1, nullptr, tail, st)) {
+  if (lia_attn_dispatch(qb, H, kv->k, kv->v, ao, H, B, T, pos0, d->heads, d->kv_heads, hd, kv->batch, b0, 1, nullptr, tail, st, &ctx->attn_opts)) {
     lia_set_error("llama attention: unsupported head_dim %d / S %d", hd, pos0 + T);
     return LIA_ERR_INVALID;
   }

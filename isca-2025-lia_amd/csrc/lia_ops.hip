@@ -249,10 +249,13 @@ extern "C" size_t lia_lm_score_workspace_bytes(int M, int H, int vocab) {
   return 512 + (size_t)std::min(M, LIA_SCORE_MAX_CHUNK) * (2 * (size_t)H + 2 * (size_t)vocab);
 }
 
+// Final norm + lm_head GEMM over EVERY row of hidden [M, ldh], one workspace chunk at a time (the CHUNK RULE of lia_hip.h): per
+// chunk, per_chunk(logits [n, vocab], r0, n) consumes the bf16 logits of rows r0 .. r0 + n - 1 before the next chunk overwrites them.
+// The one place that carves the workspace and words the refusals: lia_lm_score and lia_lm_verify cannot drift apart.
 // norm_b == nullptr: RMSNorm (Llama), else LayerNorm
-static int lm_score_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int M, int H, const bf16_t* norm_w,
-                         const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, const int64_t* targets, float* logprobs,
-                         int64_t* greedy_ids, hipStream_t st) {
+template <typename PerChunk>
+static int lm_rows_chunked(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int M, int H, const bf16_t* norm_w,
+                           const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, hipStream_t st, PerChunk per_chunk) {
   if (M <= 0) { lia_set_error("%s: M=%d must be >= 1", who, M); return LIA_ERR_INVALID; }
   if (H <= 0 || H % 64 || vocab <= 0 || vocab % 16) { lia_set_error("%s: H=%d (%%64) vocab=%d (%%16)", who, H, vocab); return LIA_ERR_INVALID; }
   if (ldh < H || ldh % 8) { lia_set_error("%s: ldh=%ld must be >= H=%d and a multiple of 8", who, ldh, H); return LIA_ERR_INVALID; }
@@ -274,8 +277,18 @@ static int lm_score_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, lo
     const LiaOutMap om = plain_out(logits, vocab, vocab);
     const int rc = gemm_checked(ctx, lno, H, emb, n, vocab, H, ep, om, nullptr, 0, 0, st);    // no slabs: never split over K
     if (rc) return rc;
-    lia_token_logprobs_launch(logits, vocab, n, vocab, targets + r0, logprobs + r0, greedy_ids + r0, st);
+    per_chunk(logits, r0, n);
   }
+  return LIA_OK;
+}
+
+static int lm_score_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int M, int H, const bf16_t* norm_w,
+                         const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, const int64_t* targets, float* logprobs,
+                         int64_t* greedy_ids, hipStream_t st) {
+  const int rc = lm_rows_chunked(who, ctx, hidden, ldh, M, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
+    lia_token_logprobs_launch(logits, vocab, n, vocab, targets + r0, logprobs + r0, greedy_ids + r0, st);
+  });
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return LIA_OK;
 }
@@ -295,4 +308,54 @@ extern "C" int lia_llama_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh
   if (!hidden || !normw || !lm || !targets || !logprobs || !greedy_ids) { lia_set_error("lia_llama_lm_score: NULL tensor"); return LIA_ERR_MISSING; }
   return lm_score_impl("lia_llama_lm_score", ctx, hidden, ldh, M, H, normw, nullptr, lm, vocab, eps, targets, logprobs, greedy_ids,
                        (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// speculative verification: lm_score's chunks (lm_rows_chunked) with a per-row argmax behind them, then the acceptance kernel (lia_score.hip)
+// ------------------------------------------------------------------------------------------------
+// norm_b == nullptr: RMSNorm (Llama), else LayerNorm
+static int lm_verify_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int B, int T, int H, const bf16_t* norm_w,
+                          const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, int suppress_token, int n_suppress,
+                          const int64_t* block_ids, const int32_t* active, int64_t* greedy, int32_t* accepted, int32_t* common,
+                          int64_t* next, hipStream_t st) {
+  if (B <= 0) { lia_set_error("%s: B=%d must be >= 1", who, B); return LIA_ERR_INVALID; }
+  if (T < 2) { lia_set_error("%s: T=%d must be >= 2 (the pending token and at least one draft token)", who, T); return LIA_ERR_INVALID; }
+  if ((long)B * T > 0x7fffffffL) { lia_set_error("%s: B=%d x T=%d rows", who, B, T); return LIA_ERR_INVALID; }
+  if (n_suppress < 0 || n_suppress > T) { lia_set_error("%s: n_suppress=%d must be in [0, T=%d]", who, n_suppress, T); return LIA_ERR_INVALID; }
+  if (suppress_token < -1 || (vocab > 0 && suppress_token >= vocab)) { lia_set_error("%s: suppress_token=%d must be -1 or in [0, vocab)", who, suppress_token); return LIA_ERR_INVALID; }
+  const int rc = lm_rows_chunked(who, ctx, hidden, ldh, B * T, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
+    lia_verify_argmax_launch(logits, vocab, n, vocab, suppress_token, n_suppress, T, r0, greedy, st);
+  });
+  if (rc) return rc;
+  lia_verify_accept_launch(block_ids, greedy, active, B, T, accepted, common, next, st);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+#define LIA_VERIFY_NULL(who, ...)                                                             \
+  do {                                                                                        \
+    const void* const ptrs[] = {__VA_ARGS__};                                                 \
+    static const char* const names[] = {"hidden", "norm weight", "lm_head weight", "block_ids", "greedy", "accepted", "common", "next"}; \
+    for (int i = 0; i < 8; ++i)                                                               \
+      if (!ptrs[i]) { lia_set_error("%s: NULL %s", who, names[i]); return LIA_ERR_INVALID; }  \
+  } while (0)
+
+extern "C" int lia_lm_verify(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* lnw, const lia_bf16* lnb,
+                             const lia_bf16* emb, int vocab, float eps, int suppress_token, int n_suppress, const int64_t* block_ids,
+                             const int32_t* active, int64_t* greedy, int32_t* accepted, int32_t* common, int64_t* next, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  LIA_VERIFY_NULL("lia_lm_verify", hidden, lnw, emb, block_ids, greedy, accepted, common, next);
+  if (!lnb) { lia_set_error("lia_lm_verify: NULL norm bias"); return LIA_ERR_INVALID; }
+  return lm_verify_impl("lia_lm_verify", ctx, hidden, ldh, B, T, H, lnw, lnb, emb, vocab, eps, suppress_token, n_suppress, block_ids,
+                        active, greedy, accepted, common, next, (hipStream_t)stream);
+}
+
+extern "C" int lia_llama_lm_verify(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* normw,
+                                   const lia_bf16* lm, int vocab, float eps, int suppress_token, int n_suppress,
+                                   const int64_t* block_ids, const int32_t* active, int64_t* greedy, int32_t* accepted,
+                                   int32_t* common, int64_t* next, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  LIA_VERIFY_NULL("lia_llama_lm_verify", hidden, normw, lm, block_ids, greedy, accepted, common, next);
+  return lm_verify_impl("lia_llama_lm_verify", ctx, hidden, ldh, B, T, H, normw, nullptr, lm, vocab, eps, suppress_token, n_suppress,
+                        block_ids, active, greedy, accepted, common, next, (hipStream_t)stream);
 }

@@ -89,3 +89,80 @@ extern "C" void lia_token_logprobs_launch(const bf16_t* logits, long ld, int M, 
   const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
   hipLaunchKernelGGL(lia_token_logprobs_kernel, dim3(M), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, targets, logprobs, greedy);
 }
+
+// ------------------------------------------------------------------------------------------------
+// speculative verification (lia_lm_verify): the argmax of a chunk of block rows, then what the block's rows accept
+// ------------------------------------------------------------------------------------------------
+// lia_argmax_kernel's scan and tie rule over row r0 + blockIdx.x of the block; `suppress` counts as -inf where the row's block
+// position (r0 + blockIdx.x) % T is below n_suppress
+__global__ __launch_bounds__(LIA_ROW_THREADS) void lia_verify_argmax_kernel(const bf16_t* __restrict__ logits, long ld, int vocab, int vec,
+                                                                            int suppress, int n_suppress, int T, int r0,
+                                                                            int64_t* __restrict__ greedy) {
+  __shared__ float sv[LIA_ROW_WAVES];
+  __shared__ int si[LIA_ROW_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const bf16_t* row = logits + (long)blockIdx.x * ld;
+  const int sup = (r0 + (int)blockIdx.x) % T < n_suppress ? suppress : -1;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int i = tid * 8; i < vocab; i += LIA_ROW_THREADS * 8) {
+    float f[8];
+    load_logits8(row, i, vocab, vec, f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float v = i + e == sup ? -INFINITY : f[e];
+      if (i + e < vocab && (v > best || (v == best && i + e < bi))) { best = v; bi = i + e; }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+  }
+  if (lane == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < LIA_ROW_WAVES; ++w)
+      if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+    greedy[r0 + blockIdx.x] = bi == 0x7fffffff ? 0 : bi;
+  }
+}
+
+// one workgroup: accepted[b] per row, their minimum, next[b] = greedy[b, common]
+__global__ __launch_bounds__(256) void lia_verify_accept_kernel(const int64_t* __restrict__ block_ids, const int64_t* __restrict__ greedy,
+                                                                const int* __restrict__ active, int B, int T, int* __restrict__ accepted,
+                                                                int* __restrict__ common, int64_t* __restrict__ next) {
+  __shared__ int smin[4];
+  const int tid = threadIdx.x;
+  int lo = T - 1;
+  for (int b = tid; b < B; b += 256) {
+    int a = T - 1;
+    if (!active || active[b]) {
+      a = 0;
+      while (a < T - 1 && block_ids[(long)b * T + a + 1] == greedy[(long)b * T + a]) ++a;
+    }
+    accepted[b] = a;
+    lo = min(lo, a);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) lo = min(lo, __shfl_xor(lo, o, 64));
+  if ((tid & 63) == 0) smin[tid >> 6] = lo;
+  __syncthreads();
+  lo = min(min(smin[0], smin[1]), min(smin[2], smin[3]));
+  if (tid == 0) common[0] = lo;
+  for (int b = tid; b < B; b += 256) next[b] = greedy[(long)b * T + lo];
+}
+
+extern "C" void lia_verify_argmax_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress, int T, int r0,
+                                         int64_t* greedy, hipStream_t st) {
+  if (n <= 0) return;
+  const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
+  hipLaunchKernelGGL(lia_verify_argmax_kernel, dim3(n), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, suppress, n_suppress, T, r0, greedy);
+}
+
+extern "C" void lia_verify_accept_launch(const int64_t* block_ids, const int64_t* greedy, const int* active, int B, int T, int* accepted,
+                                         int* common, int64_t* next, hipStream_t st) {
+  if (B <= 0) return;
+  hipLaunchKernelGGL(lia_verify_accept_kernel, dim3(1), dim3(256), 0, st, block_ids, greedy, active, B, T, accepted, common, next);
+}

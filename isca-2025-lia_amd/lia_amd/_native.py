@@ -16,6 +16,8 @@ LIB_PATH = os.path.join(_HERE, "_lib", "liblia_hip.so")
 
 LIA_OK, LIA_ERR_INVALID, LIA_ERR_MEMORY, LIA_ERR_HIP, LIA_ERR_MISSING = 0, -1, -2, -3, -4
 LIA_OPT_FUSE_COMBINE = 1           # lia_ctx_set_option keys (include/lia_hip.h)
+LIA_OPT_BLOCK_ATTENTION = 2        # the decode-shaped block attention kernel for a few queries behind a non-empty cache (verify)
+LIA_CNT_BLOCK_ATTENTION = 200      # block attention launches through the context
 LIA_CNT_FUSED_COMBINE = 100        # lia_ctx_get_counter(ctx, LIA_CNT_FUSED_COMBINE + kind), kind = 1 LayerNorm, 2 RMSNorm, 3 SiLU*up, 4 RoPE
 
 c_void_p, c_int, c_long, c_size_t, c_float, c_double = (ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_size_t,
@@ -85,6 +87,10 @@ SIGNATURES = {
                              c_void_p, c_void_p, c_void_p]),
     "lia_llama_lm_score": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p,
                                    c_void_p, c_void_p]),
+    "lia_lm_verify": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_int,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lia_llama_lm_verify": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lia_host_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                    c_int, c_int, c_int, c_int, c_int]),
     "lia_llama_pack_offsets": (c_int, [ctypes.POINTER(LlamaDesc), ctypes.POINTER(c_size_t * 9), ctypes.POINTER(c_size_t)]),

@@ -16,7 +16,7 @@ from . import _native as N
 from . import hostinfo, ops
 from .kvcache import KV_SERIAL
 from .model import LayerStore
-from .scheduler import default_stream_format, minibatch_bounds, wire_format_code
+from .scheduler import check_verify_block, default_stream_format, minibatch_bounds, wire_format_code
 from .streaming import HiddenPairs, ResidentRun, WeightPipeline, stream_order
 
 LLAMA_TENSORS = ("in_norm_w", "q_w", "k_w", "v_w", "o_w", "post_norm_w", "gate_w", "up_w", "down_w")
@@ -191,6 +191,7 @@ class LlamaScheduler:
         self.ctx = self.pipe = None
         self.hidden, self.resident, self.tables = HiddenPairs(model.shape.hidden), ResidentRun(model), None
         self.prefill_tail = True      # last layer of a prefill: last position only behind q|k|v (False: every position)
+        self.block_attention = "measured"     # a verify pass's attention: OffloadScheduler.block_attention
 
     def _ensure(self, rows, B, T, n_gpu, smax, score_rows=0):
         sh, lib = self.model.shape, N.lib()
@@ -255,7 +256,30 @@ class LlamaScheduler:
         kv_state.len = len0 + T if len0 == 0 else len0
         return lp.view(B, T), greedy.view(B, T)
 
-    def _layers(self, input_ids, kv_state, gpu_percentage, num_minibatch, pin_weight, enable_cxl, every_pos=False):
+    def verify(self, block_ids, kv_state, suppress_token=-1, n_suppress=0, active=None, gpu_percentage=100, num_minibatch=1,
+               pin_weight=True, enable_cxl=False, **_ignored):
+        """Speculative verification: OffloadScheduler.verify for a Llama -- the block [pending | draft] appended at kv_state.len,
+        every position through the last layer with the block attention kernel, lia_llama_lm_verify; -> (ops.VerifyResult, common),
+        kv_state.len = pos0 + common + 1."""
+        check_verify_block(block_ids, kv_state)
+        m, sh = self.model, self.model.shape
+        pos0 = kv_state.len
+        try:
+            x, _ = self._layers(block_ids, kv_state, gpu_percentage, num_minibatch, pin_weight, enable_cxl, every_pos=True,
+                                block_attention=True)
+        finally:
+            if self.ctx is not None:
+                self.ctx.set_option(N.LIA_OPT_BLOCK_ATTENTION, 0)
+        ids_dev = block_ids.to(device="cuda", dtype=torch.int64).contiguous()
+        act_dev = None if active is None else torch.as_tensor(active).to(device="cuda", dtype=torch.int32).contiguous()
+        res = self.ctx.llama_lm_verify(x, m.final_norm_w, m.lm_head, ids_dev, sh.rms_eps, suppress_token, n_suppress, act_dev)
+        self.ctx.synchronize()
+        common = int(res.common.item())
+        kv_state.len = pos0 + common + 1
+        return res, common
+
+    def _layers(self, input_ids, kv_state, gpu_percentage, num_minibatch, pin_weight, enable_cxl, every_pos=False,
+                block_attention=False):
         """embedding and every decoder layer of one forward -> (hidden [B, T, H], the last layer's [B, 1, H] output when it computed the
         last position only, else None).  every_pos (a scoring pass): the last layer computes every position."""
         m, sh = self.model, self.model.shape
@@ -273,6 +297,9 @@ class LlamaScheduler:
         st = ctypes.c_void_p(ctx.stream)
         pos0 = kv_state.len
         cos, sin = self.tables
+        if block_attention:          # (verify: set on the context that serves this call; the caller clears it)
+            from . import speculative
+            ctx.set_option(N.LIA_OPT_BLOCK_ATTENTION, int(speculative.block_attention_for(self, sh, B, T, pos0)))
         ids_dev = input_ids.to("cuda").contiguous()
         N.check(lib.lia_llama_embed(ctypes.c_void_p(ids_dev.data_ptr()), ctypes.c_void_p(m.embed_tokens.data_ptr()),
                                     ctypes.c_void_p(x.data_ptr()), B, T, sh.hidden, st), "lia_llama_embed")

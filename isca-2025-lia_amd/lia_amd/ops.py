@@ -4,6 +4,7 @@ torch provides device memory and stream handles only; all arithmetic happens in 
 Every function takes contiguous bf16 CUDA tensors (int64 for ids) and launches on `stream`
 (a raw hipStream_t as int; default = the context's compute stream).
 """
+import collections
 import ctypes
 
 import torch
@@ -25,6 +26,10 @@ def _chk(t, dtype=torch.bfloat16):
         return
     if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
         raise ValueError(f"expected a contiguous {dtype} CUDA tensor, got {t.dtype} {t.device} contiguous={t.is_contiguous()}")
+
+
+# lia_lm_verify's outputs, all on the device: greedy int64 [B, T], accepted int32 [B], common int32 [1], next int64 [B]
+VerifyResult = collections.namedtuple("VerifyResult", "greedy accepted common next")
 
 
 class Context:
@@ -66,6 +71,10 @@ class Context:
     def fused_combines(self, kind):
         """fused split-K combines of LIA_POST_* kind (1 LayerNorm, 2 RMSNorm, 3 SiLU*up, 4 RoPE) launched through this context"""
         return self.lib.lia_ctx_get_counter(self.handle, N.LIA_CNT_FUSED_COMBINE + kind)
+
+    def block_attention_launches(self):
+        """block attention launches through this context (N.LIA_OPT_BLOCK_ATTENTION set: the verify pass of speculative decoding)"""
+        return self.lib.lia_ctx_get_counter(self.handle, N.LIA_CNT_BLOCK_ATTENTION)
 
     def chain_next_norm(self, g_ptr, b_ptr=None):
         """lia_ctx_chain_next_norm: the next layer call also computes the first norm (weights g, b) of the layer after it."""
@@ -226,6 +235,46 @@ class Context:
         N.check(self.lib.lia_llama_lm_score(self.handle, _ptr(hidden), H, M, H, _ptr(normw), _ptr(lm), lm.shape[0], eps,
                                             _ptr(targets), _ptr(lp), _ptr(gr), self._st(stream)), "lia_llama_lm_score")
         return lp, gr
+
+    def _verify_args(self, hidden, block_ids, active):
+        _chk(hidden)
+        _chk(block_ids, torch.int64)
+        if block_ids.dim() != 2:
+            raise ValueError(f"block_ids must be [B, T], got shape {tuple(block_ids.shape)}")
+        B, T = block_ids.shape
+        H = hidden.shape[-1]
+        if hidden.numel() != B * T * H:
+            raise ValueError(f"hidden has {hidden.numel() // H} rows, block_ids {B} x {T}")
+        if active is not None:
+            _chk(active, torch.int32)
+            if active.numel() != B:
+                raise ValueError(f"active has {active.numel()} entries, block_ids {B} rows")
+        dev = hidden.device
+        out = VerifyResult(torch.empty((B, T), dtype=torch.int64, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
+                           torch.empty((1,), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int64, device=dev))
+        return B, T, H, out
+
+    def lm_verify(self, hidden, lnw, lnb, emb, block_ids, eps=1e-5, suppress_token=-1, n_suppress=0, active=None, stream=None):
+        """lia_lm_verify: final LN + tied lm_head on every row of hidden [B, T, H] (lm_score's chunks), the greedy token of every
+        block position (suppress_token counts as -inf at positions < n_suppress) and what block_ids [B, T] = [pending | draft]
+        (int64, device) accepts of it; active (int32 [B], device, or None): rows with 0 never limit `common`.  -> VerifyResult."""
+        for t in (lnw, lnb, emb):
+            _chk(t)
+        B, T, H, out = self._verify_args(hidden, block_ids, active)
+        N.check(self.lib.lia_lm_verify(self.handle, _ptr(hidden), H, B, T, H, _ptr(lnw), _ptr(lnb), _ptr(emb), emb.shape[0], eps,
+                                       int(suppress_token), int(n_suppress), _ptr(block_ids), _ptr(active), _ptr(out.greedy),
+                                       _ptr(out.accepted), _ptr(out.common), _ptr(out.next), self._st(stream)), "lia_lm_verify")
+        return out
+
+    def llama_lm_verify(self, hidden, normw, lm, block_ids, eps=1e-5, suppress_token=-1, n_suppress=0, active=None, stream=None):
+        """lia_llama_lm_verify: lm_verify with the final RMSNorm and the untied lm_head of a Llama"""
+        for t in (normw, lm):
+            _chk(t)
+        B, T, H, out = self._verify_args(hidden, block_ids, active)
+        N.check(self.lib.lia_llama_lm_verify(self.handle, _ptr(hidden), H, B, T, H, _ptr(normw), _ptr(lm), lm.shape[0], eps,
+                                             int(suppress_token), int(n_suppress), _ptr(block_ids), _ptr(active), _ptr(out.greedy),
+                                             _ptr(out.accepted), _ptr(out.common), _ptr(out.next), self._st(stream)), "lia_llama_lm_verify")
+        return out
 
     def score_chunk_rows(self, M, H, vocab):
         """rows per chunk lm_score would use for M rows in this context's workspace (0: not even min(M, 256) rows fit)"""

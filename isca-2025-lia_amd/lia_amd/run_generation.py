@@ -122,6 +122,11 @@ def build_parser():
     p.add_argument("--top-k", default=50, type=int, help="with --do-sample; 0: off")
     p.add_argument("--top-p", default=1.0, type=float, help="with --do-sample; 1: off")
     p.add_argument("--sample-seed", default=0, type=int, help="with --do-sample: the seed of the generation's uniforms")
+    p.add_argument("--draft-model", default=None, type=str,
+                   help="speculative greedy decoding: an OPT / Llama shape name or checkpoint directory of the same vocabulary, kept all "
+                        "resident (policies 3 / 3) beside the target; it proposes --draft-tokens tokens per round and one pass of the "
+                        "target's weights verifies them (same ids as plain greedy; not with --do-sample or --cpu-layers -1)")
+    p.add_argument("--draft-tokens", default=4, type=int, help="with --draft-model: draft tokens per round")
     add_init_args(p)
     return p
 
@@ -331,6 +336,35 @@ def load_model(args):
     fmt, raw = placement_formats(args.prefill_policy, args.decoding_policy, fmt, n_gpu, shape.layers, args.pin_weight, args.enable_cxl, raw)
     return LiaOPTModel.random_init(shape, seed=args.seed, init=args.init, n_gpu_layers=n_gpu,
                                    pin_weight=args.pin_weight, enable_cxl=args.enable_cxl, wire=fmt, raw_layers=raw)
+
+
+def load_draft(args):
+    """--draft-model: the draft model, every layer resident, with a scheduler of its own -> speculative.ModelDrafter"""
+    import copy
+    from .speculative import ModelDrafter
+    d = copy.copy(args)
+    d.model_id, d.gpu_percentage, d.prefill_policy, d.decoding_policy = args.draft_model, 100, 3, 3
+    d.pin_weight, d.enable_cxl, d.cpu_layers, d.stream_format = True, False, 0, args.stream_format
+    model = load_model(d)
+    attach_scheduler(model, d.stream_format or default_stream_format())
+    return ModelDrafter(model)
+
+
+def summarize_speculation(spec_log, total_list, batch_size, out=print):
+    """accepted draft tokens per round over the timed iterations, beside the latencies: -> the record of --result-json"""
+    commons = [c for c, _ in spec_log]
+    rec = {"rounds": len(commons), "accepted_per_round": round(float(np.mean(commons)), 3) if commons else None,
+           "accepted_histogram": {int(v): int(n) for v, n in zip(*np.unique(commons, return_counts=True))} if commons else {}}
+    out("Speculative rounds: %d, accepted draft tokens per round: %s (histogram %s)" % (rec["rounds"], rec["accepted_per_round"], rec["accepted_histogram"]))
+    if total_list and commons:
+        passes = sum(len(x) - 1 for x in total_list)
+        secs = sum(sum(x[1:]) for x in total_list)
+        tokens = sum(c + 1 for c in commons)
+        rec.update(target_passes=passes, s_per_pass=secs / max(passes, 1),
+                   decode_tokens_per_s=batch_size * tokens / max(secs, 1e-9))
+        out("Average latency per target pass (draft included): %.3f sec; decode throughput by accepted tokens: %.2f tokens/s (an upper "
+            "bound: the last round of an iteration may be cut)" % (rec["s_per_pass"], rec["decode_tokens_per_s"]))
+    return rec
 
 
 def summarize(total_time, num_iter, num_warmup, total_list, batch_size, out=print):
@@ -602,6 +636,10 @@ def _main(args, rec=None):
         generate_kwargs["cpu_layers"] = args.cpu_layers
         if args.cpu_layers < 0 and args.cpu_layers_start is not None:
             generate_kwargs["cpu_layers_start"] = args.cpu_layers_start
+    spec_log = None
+    if args.draft_model:
+        spec_log = []
+        generate_kwargs.update(draft=load_draft(args), draft_tokens=args.draft_tokens, spec_log=spec_log)
     tokenizer = load_tokenizer(args.model_id)
     if args.prompt_file is not None:
         input_ids, generate_kwargs["attention_mask"] = prompt_file_inputs(args, model.shape.vocab, tokenizer,
@@ -612,6 +650,8 @@ def _main(args, rec=None):
         if args.prompt_file is not None:
             raise SystemExit("[ERROR] --followup with --prompt-file is not supported: one conversation, every row the same (--prompt)")
         return run_conversation(model, input_ids, followup_ids(args, model.shape.vocab, tokenizer), generate_kwargs, args, tokenizer)
+    if args.profile and spec_log is not None:
+        raise SystemExit("[ERROR] --profile with --draft-model is not supported: the profile brackets a prefill and single-token decode steps")
     if args.profile:
         profile_once(model, input_ids, generate_kwargs)
     total_time, total_list = 0.0, []
@@ -620,7 +660,9 @@ def _main(args, rec=None):
         if rec is not None and i == args.num_warmup and hasattr(sched, "stream_stats"):
             sched.stream_stats(reset=True)                     # the weight stream's bytes / copy-engine time over the timed iterations
         tic = time.time()
-        if rec is not None and i == 0 and args.num_warmup >= 1 and hasattr(sched, "coop_report"):
+        # (not with a drafter: the brackets describe a prefill and single-token decode steps, and the first verify pass may move
+        # to a larger workspace -- a new library context -- between them)
+        if rec is not None and spec_log is None and i == 0 and args.num_warmup >= 1 and hasattr(sched, "coop_report"):
             profile_once(model, input_ids, generate_kwargs, warm=False)       # the first warm-up iteration, bracketed
             output = profile_once.last[0]
             if not args.token_latency:
@@ -643,6 +685,8 @@ def _main(args, rec=None):
         if rec is not None:
             from . import hostinfo as _hi
             rec["_mem_samples"].append(_hi.cgroup_memory()["current"])
+        if spec_log is not None and i < args.num_warmup:
+            del spec_log[:]                                        # the acceptance figures are those of the timed iterations
         if i >= args.num_warmup:
             total_time += toc - tic
             if args.token_latency:
@@ -656,6 +700,9 @@ def _main(args, rec=None):
                                 "fraction_of_63_gbs_link_over_wall": round(b / max(total_time, 1e-9) / 63e9, 3),
                                 "wire_format": ("pack10" if any(getattr(st, "packed", 0) for st in model.layers) else "raw"),
                                 "wire_format_note": "the format of the host copies that streamed (a policy-1 / NUMA-tier / unpinned placement ships raw: scheduler.placement_formats)"}
+    if spec_log is not None:
+        # (with a drafter a latency entry is a target pass of several tokens: "Average 2... latency" above is per pass)
+        res["speculative"] = summarize_speculation(spec_log, total_list, args.batch_size)
     if "decode_tokens_per_s" in res:
         print("Decode throughput: %.2f tokens/s, prefill %.1f ms" % (res["decode_tokens_per_s"], res["prefill_ms"]))
     coop = getattr(model._lia_scheduler, "coop_report", lambda: None)()

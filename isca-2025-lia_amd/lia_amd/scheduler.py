@@ -93,6 +93,19 @@ def wire_format_code(fmt):
     return codes[fmt]
 
 
+def check_verify_block(block_ids, kv_state):
+    """every refusal of a scheduler's verify(), by name"""
+    if block_ids.dim() != 2:
+        raise ValueError(f"verify: block_ids must be [batch, T], got shape {tuple(block_ids.shape)}")
+    T = block_ids.shape[1]
+    if kv_state.len < 1:
+        raise ValueError("verify: an empty cache (a draft block is verified behind the prompt's prefill)")
+    if T < 2:
+        raise ValueError(f"verify: a block of at least two tokens, the pending one and a draft (T={T})")
+    if kv_state.len + T > kv_state.smax:
+        raise ValueError(f"verify: the cache holds {kv_state.smax} positions, the context {kv_state.len} + the block {T} need {kv_state.len + T}")
+
+
 class OffloadScheduler:
     """forward(input_ids, kv_state, **lia flags) -> (logits [B,vocab], next_ids [B]) on the device."""
 
@@ -108,6 +121,9 @@ class OffloadScheduler:
         self.resident = ResidentRun(model)
         self.host = HostLayers(model)      # policy 1 and the cooperative split's host-computed layers
         self._key_starts = None     # (host int32 [B], device copy, context it was uploaded to) of a left-padded generation
+        # a verify pass's attention: "measured" = the block kernel where it was measured faster than the append kernels
+        # (speculative.block_attention_pays), True = wherever the launch takes the shape (A/B runs, tests), False = never
+        self.block_attention = "measured"
         self.host_threads = None    # OpenMP team of the host attention / host layers; default = hostinfo.default_host_threads
         # policy-0 prefill: keep the fresh K/V of the streamed layers in HBM until the prefill's last layer has run and deliver
         # them to the host caches then (lia_kv_deliver), instead of beside the prefill's weight stream.  LIA_DEFER_KV=0: deliver at once.
@@ -289,6 +305,44 @@ class OffloadScheduler:
             kv_state.len = len0               # (an appended block is scored, not kept)
         return lp.view(B, T), greedy.view(B, T)
 
+    def verify(self, block_ids, kv_state, suppress_token=-1, n_suppress=0, active=None, prefill_policy=1, decoding_policy=1,
+               no_overlap=False, pin_weight=False, gpu_percentage=0, num_minibatch=1, enable_cxl=False, append_policy=None,
+               **_decode_only):
+        """Speculative verification: one pass of the weights over block_ids [B, T] = [pending | d_1 .. d_{T-1}]
+        appended at kv_state.len on a NON-EMPTY cache.  forward()'s phases with the last layer on every position, lm_verify in
+        place of lm_head and LIA_OPT_BLOCK_ATTENTION set around the layers; the K/V rows are delivered as in forward().  Returns
+        ops.VerifyResult (device tensors) and the number `common` of draft tokens every active row accepts; the new cache length
+        is pos0 + common + 1 -- the rows behind it are dead and are rewritten by the next round (nothing is outstanding into them:
+        _deliver has synchronised both streams and awaited the policy-0 stores).  suppress_token counts as -inf at block positions
+        < n_suppress; active (int32 / bool [B] or None): rows with 0 never limit common.  A fixed cpu_layers is passed through as
+        in score()."""
+        from . import speculative
+        check_verify_block(block_ids, kv_state)
+        B, T = block_ids.shape
+        pos0 = kv_state.len
+        s = self._validate(block_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch, append_policy)
+        s.every_pos = s.verify = True
+        cpu_layers = max(0, int(_decode_only.get("cpu_layers") or 0))
+        self._place(s, kv_state, pin_weight, enable_cxl, None, cpu_layers, None)
+        m, sh, ctx = self.model, self.model.shape, self.ctx
+        ids_dev = block_ids.to(device="cuda", dtype=torch.int64).contiguous()
+        act_dev = None if active is None else torch.as_tensor(active).to(device="cuda", dtype=torch.int32).contiguous()
+        ctx.set_option(N.LIA_OPT_BLOCK_ATTENTION, int(speculative.block_attention_for(self, sh, B, T, pos0)))
+        try:
+            ctx.embed_into(ids_dev, m.embed_tokens, m.embed_positions, s.x, s.pos0, starts=self._key_starts_for(s.B)[1])
+            if s.on_host:
+                self._await_kv(kv_state)
+                hidden = self._host_layers(s.x, kv_state, s.n_gpu, s.B, s.T, s.pos0)
+            else:
+                hidden = self._run_layers(s, kv_state)
+        finally:
+            ctx.set_option(N.LIA_OPT_BLOCK_ATTENTION, 0)
+        res = ctx.lm_verify(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, sh.ln_eps, suppress_token, n_suppress, act_dev)
+        self._deliver(s, kv_state)
+        common = int(res.common.item())
+        kv_state.len = pos0 + common + 1
+        return res, common
+
     # -- left-padded batches (generation.generate(..., attention_mask=)) -----------------------------------------------------
     def set_key_starts(self, starts):
         """starts: int32 [B] (row b's first real cache position) for every forward until the next call, or None: the unpadded
@@ -359,6 +413,7 @@ class OffloadScheduler:
                                pos0=kv_state.len, coop=None, cpu_set=frozenset(), host_act=frozenset(), host_now=frozenset(),
                                t_fwd0=None, busy0=0.0, hold=None, x=None, y=None,
                                every_pos=False,                          # a scoring pass (score): no last-position-only last layer, no K/V delivery
+                               verify=False,                             # a verify pass of speculative decoding (verify): every_pos, K/V delivered
                                on_host=(policy == 1 and n_gpu < L))      # policy 1: the streamed layers run on the host cores (_host_layers)
 
     def _place(self, s, kv_state, pin_weight, enable_cxl, max_new_tokens, cpu_layers, cpu_layers_start):
@@ -408,7 +463,8 @@ class OffloadScheduler:
             rows = max(rows, s.mini * kv_state.smax)
         if is_prefill and s.policy == 0 and s.pos0 > 0 and n_gpu < L:
             # a policy-0 block appended to a non-empty cache parks the cached prefix and its own rows in the slab: mini (pos0 + T) rows
-            rows = max(rows, s.mini * (s.pos0 + T))
+            # (a verify pass sizes the slab for the whole cache once: pos0 grows every round, and a larger workspace is a new context)
+            rows = max(rows, s.mini * (kv_state.smax if s.verify else s.pos0 + T))
         s.x, s.y = self._ensure(rows, B, T, n_gpu, score_rows=B * T if s.every_pos else 0)
         if is_prefill and s.policy == 0 and n_gpu < L and self.defer_kv and s.pos0 == 0:
             self._await_all_deliveries()          # (host-blocking: afterwards nothing on the D2H stream reads the holding caches)

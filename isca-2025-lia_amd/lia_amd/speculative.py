@@ -1,0 +1,254 @@
+"""Speculative greedy decoding: a drafter proposes k tokens per row, the target model verifies the block
+[pending | proposal] in ONE pass of its weights (scheduler.verify) and keeps what its own greedy search would have produced.
+
+The cache length stays one integer per batch: a round accepts `common` draft tokens on every row, the minimum over the active rows'
+own counts, plus the target's token behind them.  That is exact -- the output is the greedy output -- and pays where one pass of the
+weights is the cost of a token and the batch is small; at a large batch the minimum collapses towards 0.
+
+    out = generate(model, ids, max_new_tokens=N, draft=ModelDrafter(small_model), draft_tokens=4, spec_log=log, **lia_flags)
+
+A drafter is any object with  propose(ids [B, n] int64 CPU, k, suppress) -> int64 [B, k]:  its guess of the k tokens behind ids.
+suppress = (token, n): the target will not produce `token` (EOS below min_new_tokens) as the first n of them; a drafter that ignores
+it only loses acceptance.  An optional attribute `vocab` is checked against the target's.
+"""
+import time
+
+import numpy as np
+import torch
+
+REFUSALS = {
+    "do_sample": "draft together with do_sample=True is not supported: verification keeps the GREEDY token of every position",
+    "return_logits": "draft together with return_logits=True is not supported: a verify pass never materialises the logits",
+    "dp": "draft together with a data-parallel group is not supported: the ranks would accept different counts",
+    "cpu_layers": "draft together with cpu_layers=-1 (the online cooperative split) is not supported: the controller samples "
+                  "single-token decode steps; name a fixed cpu_layers",
+}
+
+
+def block_attention_pays(head_dim, heads, kv_heads, B, T, pos0):
+    """Where the block attention launch beat the append launch by more than the ~20 % run-to-run spread of such short launches
+    (results/attn_block_bench.txt, one MI355X) -- and nowhere else: a shape that was not measured keeps the append launch.
+    Measured: d = 128 with G = heads / kv_heads = 1 (OPT-30B's 56 heads, B 1 / 4 / 64, pos0 288 / 2048, T 2 / 3 / 5 / 8) and G = 4
+    (Llama-3-8B's 32 / 8, B 1 / 128, pos0 1024, T 2 / 4).  In work = (B x kv_heads workgroups) x keys:
+        G 1: T 2 everywhere (1.4 - 2.1 x); T 3 from ~1e5 (1.3 - 1.8 x; 1.16 - 1.18 x below); T 4, 5 from ~4e6 (1.5 x at B 64, pos0 2048;
+             0.8 - 1.2 x below; T 4 by its neighbours); T >= 6 nowhere (T 8: 0.4 - 0.8 x)
+        G 4: T 2 and 4 (and 3 between them) from 512 workgroups (2.4 x / 1.3 x at B 128; 0.5 - 0.8 x at B 1)"""
+    if head_dim != 128 or heads % kv_heads:
+        return False
+    G, wgs = heads // kv_heads, B * kv_heads
+    work = wgs * (pos0 + T)
+    if G == 1:
+        return T == 2 or (T == 3 and work >= 100000) or (T in (4, 5) and work >= 4000000)
+    if G == 4:
+        return 2 <= T <= 4 and wgs >= 512
+    return False
+
+
+def block_attention_for(sched, shape, B, T, pos0):
+    """LIA_OPT_BLOCK_ATTENTION of one verify pass: the scheduler's block_attention -- True / False, or "measured": the table above"""
+    mode = getattr(sched, "block_attention", "measured")
+    if mode == "measured":
+        return block_attention_pays(shape.head_dim, shape.heads, getattr(shape, "kv_heads", shape.heads), B, T, pos0)
+    return bool(mode)
+
+
+def check_settings(model, sched, draft, draft_tokens, do_sample, return_logits, lia):
+    """every refusal of generate(draft=), by name (ValueError)"""
+    if do_sample:
+        raise ValueError(REFUSALS["do_sample"])
+    if return_logits:
+        raise ValueError(REFUSALS["return_logits"])
+    if getattr(sched, "dp", None) is not None:
+        raise ValueError(REFUSALS["dp"])
+    if lia.get("cpu_layers", 0) < 0:
+        raise ValueError(REFUSALS["cpu_layers"])
+    if isinstance(draft_tokens, bool) or not isinstance(draft_tokens, int) or draft_tokens < 1:
+        raise ValueError(f"draft_tokens must be an int >= 1, got {draft_tokens!r}")
+    if not callable(getattr(draft, "propose", None)):
+        raise ValueError(f"draft must have propose(ids, k, suppress), got {type(draft).__name__}")
+    vocab = getattr(draft, "vocab", None)
+    if vocab is not None and vocab != model.shape.vocab:
+        raise ValueError(f"the draft model has a vocabulary of {vocab} tokens, the target {model.shape.vocab}: their ids do not mean the same")
+
+
+class ReplayDrafter:
+    """Proposes a recorded continuation: ids [B, N] holds the prompt and what the target is known to generate behind it (its own
+    earlier output, an oracle's).  corrupt (optional): per round r a list with, per row, the number a of leading proposal tokens
+    left right -- token a of that row's proposal is made wrong (its lowest bit flipped), the tokens behind it are right again; an
+    entry >= k, None, or a round past the end of the list leaves the row alone.  For tests and measurements: the acceptance of
+    every round is scripted."""
+
+    def __init__(self, ids, corrupt=None):
+        self.ids = torch.as_tensor(ids, dtype=torch.int64).cpu()
+        self.corrupt = list(corrupt) if corrupt is not None else []
+        self.rounds = 0
+
+    def script(self, r, B, k):
+        """per row, the scripted number of right leading tokens of round r (k: all of them)"""
+        row = self.corrupt[r] if r < len(self.corrupt) and self.corrupt[r] is not None else [None] * B
+        return [k if a is None else min(int(a), k) for a in row]
+
+    def propose(self, ids, k, suppress=(-1, 0)):
+        B, n = ids.shape
+        out = torch.zeros((B, k), dtype=torch.int64)
+        have = max(0, min(k, self.ids.shape[1] - n))
+        out[:, :have] = self.ids[:, n:n + have]
+        for b, a in enumerate(self.script(self.rounds, B, k)):
+            if a < k:
+                out[b, a] ^= 1
+        self.rounds += 1
+        return out
+
+
+class ModelDrafter:
+    """A second, all-resident model (policy 3 / 3, gpu_percentage 100) with its own scheduler, context and cache.  Every round it
+    feeds the tokens its cache lacks -- one, or two after a fully accepted round -- through the decode / append paths and runs
+    k - 1 more decode steps whose argmax stays on the device.  Its cache length is rolled back to the common prefix of what it was
+    fed and the ids it is given; it prefills again when that prefix is empty, the batch changed or the cache is too small (a new
+    conversation, a new turn of past=)."""
+
+    FLAGS = dict(prefill_policy=3, decoding_policy=3, gpu_percentage=100, pin_weight=True)
+
+    def __init__(self, model, reserve=64):
+        from .generation import _scheduler_of
+        self.model, self.sched, self.reserve = model, _scheduler_of(model), reserve
+        self.vocab = model.shape.vocab
+        self.kv = None
+        self.fed = None          # int64 [B, kv.len]: the tokens whose K/V the cache holds
+        self.prefills = self.rounds = 0
+
+    def _new_cache(self, B, n, k):
+        smax = min(n + k + self.reserve, self.model.shape.max_pos)
+        if getattr(self.model, "family", "opt") == "llama":
+            from .llama import LlamaKVState
+            return LlamaKVState(self.model, B, smax)
+        return self.sched.new_kv_state(B, n, smax - n, **self.FLAGS)
+
+    def propose(self, ids, k, suppress=(-1, 0)):
+        ids = torch.as_tensor(ids, dtype=torch.int64).cpu()
+        B, n = ids.shape
+        tok, n_sup = suppress
+        if n + k > self.model.shape.max_pos:
+            raise ValueError(f"the draft model has max positions {self.model.shape.max_pos}, the round reaches {n + k}")
+        keep = 0
+        if self.kv is not None and self.fed is not None and self.fed.shape[0] == B and self.kv.smax >= n + k:
+            m = min(self.fed.shape[1], n - 1)
+            same = (self.fed[:, :m] == ids[:, :m]).all(dim=0).long()
+            keep = int(same.cumprod(0).sum())
+        if keep == 0:
+            self.kv = self._new_cache(B, n, k)
+            self.prefills += 1
+        self.kv.len = keep
+        cur = ids[:, keep:]
+        dev = []
+        for i in range(k):
+            sup = tok if i < n_sup else -1
+            _, nxt = self.sched.forward(cur, self.kv, max_new_tokens=k, suppress_token=sup, **self.FLAGS)
+            dev.append(nxt)
+            cur = nxt.view(B, 1)
+        out = torch.stack(dev, dim=1).cpu()
+        self.fed = torch.cat([ids, out[:, :k - 1]], dim=1)
+        self.rounds += 1
+        return out
+
+
+def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, eos_token_id, pad_token_id, token_latency, lia,
+                       draft, draft_tokens, spec_log=None, step_hook=None, max_steps=None, past=None, return_state=False,
+                       reserve_tokens=0, starts=None):
+    """_greedy_search with a drafter: the ordinary prefill, then rounds of propose -> verify -> append.  The EOS / pad / unfinished
+    bookkeeping is applied token by token as the greedy loop applies it; a finished row is inactive (it never limits `common`, its
+    block is pad tokens, as the greedy loop feeds them); a round ends behind the token at which a row finishes, so the cache holds
+    exactly what the greedy loop would have fed.  latency_list has one entry per target pass."""
+    from .generation import GenerationState, turn_positions
+    k = draft_tokens
+    ids = torch.as_tensor(input_ids, dtype=torch.int64).cpu()
+    if ids.dim() != 2:
+        raise ValueError("input_ids must be [batch, seq]")
+    first = ids
+    if past is not None:
+        first = torch.cat([past.pending[:, None], ids], dim=1)
+        need = turn_positions(past.kv.len, ids.shape[1], max_new_tokens) + k
+        if need > past.kv.smax:
+            raise ValueError(f"the turn needs {need} cache positions with draft_tokens={k} (a verify block overhangs by {k}), the cache "
+                             f"holds {past.kv.smax} (give the first turn a larger reserve_tokens)")
+        if need + 1 > model.shape.max_pos:
+            raise ValueError(f"the conversation would reach {need + 1} positions with draft_tokens={k}, the model has max positions {model.shape.max_pos}")
+        ids = torch.cat([past.ids, ids], dim=1)
+    B, T = ids.shape
+    reserve = reserve_tokens if past is None else 0
+    if past is None and T + max_new_tokens + reserve + k > model.shape.max_pos:
+        raise ValueError(f"prompt {T} + max_new_tokens {max_new_tokens}" + (f" + reserve_tokens {reserve}" if reserve else "")
+                         + f" + draft_tokens {k} exceeds max positions {model.shape.max_pos}")
+    if past is not None:
+        kv = past.kv
+    elif getattr(model, "family", "opt") == "llama":
+        from .llama import LlamaKVState
+        kv = LlamaKVState(model, B, T + max_new_tokens + reserve + k)
+    else:
+        kv = sched.new_kv_state(B, T, max_new_tokens + reserve + k, **lia)
+    unfinished = torch.ones(B, dtype=torch.int64)
+    latency_list = []
+    ids_buf = torch.empty((B, T + max_new_tokens), dtype=torch.int64)
+    ids_buf[:, :T] = ids
+    limit = max_new_tokens if max_steps is None else min(max_new_tokens, max_steps)
+    state = {"step": 0, "unfinished": unfinished}
+
+    def append(tokens):
+        """one generated token per row, greedy_search.py:398-421; True when the generation is over"""
+        unf = state["unfinished"]
+        if eos_token_id is not None:
+            tokens = tokens * unf + pad_token_id * (1 - unf)
+        ids_buf[:, T + state["step"]] = tokens
+        newly = False
+        if eos_token_id is not None:
+            nxt_unf = unf * (tokens != eos_token_id).long()
+            newly = bool((nxt_unf != unf).any())
+            state["unfinished"] = nxt_unf
+        state["step"] += 1
+        over = (eos_token_id is not None and int(state["unfinished"].max()) == 0) or state["step"] >= limit
+        return over, newly
+
+    # the prefill (or the turn's block): an ordinary forward
+    if step_hook is not None:
+        step_hook(0)
+    tic = time.time()
+    suppress = eos_token_id if (eos_token_id is not None and 0 < min_new_tokens) else -1
+    _, nxt = sched.forward(first, kv, max_new_tokens=max_new_tokens, suppress_token=suppress, **lia)
+    over, _ = append(nxt.cpu())
+    latency_list.append(time.time() - tic)
+    rnd = 0
+    while not over:
+        rnd += 1
+        if step_hook is not None:
+            step_hook(rnd)
+        tic = time.time()
+        g = state["step"]
+        pos0 = kv.len
+        n_sup = int(np.clip(min_new_tokens - g, 0, k + 1)) if eos_token_id is not None else 0
+        sup_tok = eos_token_id if n_sup else -1
+        active = state["unfinished"]
+        prop = torch.as_tensor(draft.propose(ids_buf[:, :T + g], k, (sup_tok, min(n_sup, k))), dtype=torch.int64).cpu()
+        if tuple(prop.shape) != (B, k):
+            raise ValueError(f"draft.propose returned shape {tuple(prop.shape)}, expected {(B, k)}")
+        if eos_token_id is not None:
+            prop = prop * active[:, None] + pad_token_id * (1 - active[:, None])      # a finished row is fed pad tokens
+        block = torch.cat([ids_buf[:, T + g - 1:T + g], prop], dim=1)
+        res, common = sched.verify(block, kv, suppress_token=sup_tok, n_suppress=n_sup, active=active.to(torch.int32), **lia)
+        greedy = res.greedy.cpu()
+        if spec_log is not None:
+            spec_log.append((common, res.accepted.cpu().tolist()))
+        n_app = 0
+        for i in range(common + 1):
+            over, newly = append(greedy[:, i])
+            n_app += 1
+            if over or newly:
+                break
+        kv.len = pos0 + n_app          # the block's rows behind it are dead: the next round rewrites them
+        latency_list.append(time.time() - tic)
+    step = state["step"]
+    out = ids_buf[:, :T + step].clone() if step < max_new_tokens else ids_buf
+    res = (out, latency_list) if token_latency else (out,)
+    if return_state:
+        flags = past.flags if past is not None else {key: v for key, v in lia.items() if key != "append_policy"}
+        res = res + (GenerationState(kv, out.clone(), starts, flags),)
+    return res if len(res) > 1 else res[0]

@@ -1,0 +1,120 @@
+"""Speculative greedy decoding against plain greedy decoding in the same run: what a verify pass of k + 1 tokens costs beside a decode
+step, what a draft round of an opt-125m-shaped ModelDrafter costs, and the end-to-end tokens/s at a scripted acceptance.
+
+    python tools/spec_ab.py --config opt30b-online-1-1 | opt30b-online-0-1 | opt30b-headline [--batch 1] [--prompt 256] [--new 32]
+                            [--ks 1,2,4,7] [--draft opt-125m | none] [--append-policy 2]
+
+Per k: a ReplayDrafter replays the run's own plain continuation with every row of every round scripted to accept 0, k // 2 and k
+tokens, so tokens/s = B (common + 1) / verify pass is measured, not modelled.  A decode step and a verify pass round differently, and
+a near-tie of a random-weight model then flips a token: the row leaves its recording and the replayed drafts are wrong from there on.
+So the prompts are CHOSEN, as the tests choose theirs: --pool candidate rows are generated plain with their logits, and the B rows
+whose smallest top-2 gap over all steps is largest are the run's batch (the gap is printed in bf16 quanta of the row's largest
+logit).  Every line still reports whether its acceptance stayed on the script and how many rows differ from the plain run's ids:
+only lines that stayed on it are figures of that acceptance.  The draft
+round (k decode-shaped steps of the small model, all resident, its own context) is timed apart: a ReplayDrafter costs nothing, so
+tokens/s with a real drafter of that acceptance is B (common + 1) / (verify + draft round).  Host clock around the passes (each ends
+in a device synchronise); medians."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "isca-2025-lia_amd"))
+
+CONFIGS = {     # the lia_online-shaped lines (batch 1, in 256 / out 32) at their gpu %, and the headline flags
+    "opt30b-online-1-1": dict(model="opt-30b", flags=dict(prefill_policy=1, decoding_policy=1, gpu_percentage=64, pin_weight=True)),
+    "opt30b-online-0-1": dict(model="opt-30b", flags=dict(prefill_policy=0, decoding_policy=1, gpu_percentage=58, pin_weight=True)),
+    "opt30b-headline": dict(model="opt-30b", flags=dict(prefill_policy=0, decoding_policy=2, gpu_percentage=10, pin_weight=True)),
+    "opt1.3b-resident": dict(model="opt-1.3b", flags=dict(prefill_policy=3, decoding_policy=3, gpu_percentage=100, pin_weight=True)),
+}
+
+
+def build(name, flags):
+    from lia_amd.model import LiaOPTModel, resolve_shape
+    from lia_amd.scheduler import OffloadScheduler, placement_formats
+    shape = resolve_shape(name)
+    n_gpu = int(shape.layers * flags["gpu_percentage"] / 100)
+    fmt, raw = placement_formats(flags["prefill_policy"], flags["decoding_policy"], 10, n_gpu, shape.layers, True, False, ())
+    model = LiaOPTModel.random_init(shape, seed=0, n_gpu_layers=n_gpu, pin_weight=True, wire=fmt, raw_layers=raw)
+    model._lia_scheduler = OffloadScheduler(model, wire="pack10")
+    return shape, model
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", required=True, choices=sorted(CONFIGS))
+    ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--prompt", type=int, default=256)
+    ap.add_argument("--new", type=int, default=32)
+    ap.add_argument("--ks", type=str, default="1,2,4,7")
+    ap.add_argument("--draft", type=str, default="opt-125m")
+    ap.add_argument("--append-policy", type=int, default=None)
+    ap.add_argument("--pool", type=int, default=16, help="candidate prompts the batch is chosen from (0: take the first --batch)")
+    a = ap.parse_args()
+    import torch
+    from lia_amd.generation import generate
+    from lia_amd.speculative import ModelDrafter, ReplayDrafter
+    c = CONFIGS[a.config]
+    flags, B, ks = c["flags"], a.batch, [int(v) for v in a.ks.split(",")]
+    shape, model = build(c["model"], flags)
+    g = torch.Generator().manual_seed(0)
+    kw = dict(eos_token_id=None, token_latency=True, **flags)
+    print(f"{a.config}: {c['model']} B {B}, in {a.prompt} / out {a.new}, {flags}, append_policy {a.append_policy}", flush=True)
+    prompt = torch.randint(4, shape.vocab, (max(B, a.pool), a.prompt), generator=g)
+    if a.pool > B:
+        _, _, steps = generate(model, prompt, max_new_tokens=a.new + max(ks) + 1, return_logits=True, **kw)
+        gaps = []
+        for lg in steps:
+            f = lg.float()
+            top2 = f.topk(2, dim=-1).values
+            q = torch.exp2(torch.floor(torch.log2(f.abs().amax(dim=-1).clamp_min(1e-30))) - 7)
+            gaps.append(((top2[:, 0] - top2[:, 1]) / q).cpu())
+        worst = torch.stack(gaps).amin(dim=0)
+        pick = worst.argsort(descending=True)[:B]
+        print(f"  rows {pick.tolist()} of {a.pool} candidates: smallest top-2 gap over {len(steps)} steps {[round(float(worst[i]), 1) for i in pick]} "
+              f"bf16 quanta (pool median {float(worst.median()):.1f})", flush=True)
+        prompt = prompt[pick]
+        del steps
+    prompt = prompt[:B].contiguous()
+    generate(model, prompt, max_new_tokens=a.new + max(ks) + 1, max_steps=2, **kw)             # warm-up: placement, allocations
+    rec, lat = generate(model, prompt, max_new_tokens=a.new + max(ks) + 1, **kw)                # the recording, and the plain figures
+    plain = rec[:, :a.prompt + a.new]
+    step = statistics.median(lat[1:])
+    print(f"  plain greedy: prefill {1e3 * lat[0]:9.1f} ms, decode step {1e3 * step:8.2f} ms (median of {len(lat) - 1}), {B / step:8.2f} tokens/s", flush=True)
+    for k in ks:
+        for acc in sorted({0, k // 2, k}):
+            d, log = ReplayDrafter(rec, [[acc] * B] * (a.new + 1)), []
+            t0 = time.time()
+            out, slat = generate(model, prompt, max_new_tokens=a.new, draft=d, draft_tokens=k, spec_log=log, append_policy=a.append_policy, **kw)
+            wall = time.time() - t0
+            vp = statistics.median(slat[1:])
+            differ = int((out != plain).any(dim=1).sum())
+            scripted = all(cm == acc for cm, _ in log[:-1]) and differ == 0
+            print(f"  k {k} accept {acc}: verify pass {1e3 * vp:8.2f} ms ({vp / step:5.2f} x a decode step), {len(slat) - 1:3d} passes, "
+                  f"{B * (a.new - 1) / sum(slat[1:]):8.2f} tokens/s ({step * (a.new - 1) / sum(slat[1:]):5.2f} x plain), wall {wall:6.2f} s, "
+                  f"block attention launches {model._lia_scheduler.ctx.block_attention_launches()}, rows differing from plain {differ}"
+                  f"{'' if scripted else '   (OFF THE SCRIPT, acceptance per round: ' + str([cm for cm, _ in log]) + ')'}", flush=True)
+    if a.draft != "none":
+        _, dmodel = build(a.draft, ModelDrafter.FLAGS)
+        d = ModelDrafter(dmodel)
+        for k in ks:
+            ids = rec[:, :a.prompt + 1]
+            out = d.propose(ids, k)                                   # its prefill (or its rollback to the prompt)
+            p0, times = d.prefills, []
+            for r in range(5):       # rounds behind a fully accepted one (its own proposal + one token): two tokens fed, then k - 1 steps
+                ids = torch.cat([ids, out, rec[:, :1]], dim=1)
+                t0 = time.time()
+                out = d.propose(ids, k)
+                times.append(time.time() - t0)
+            assert d.prefills == p0, "the drafter prefilled again: its rollback did not find the common prefix"
+            print(f"  {a.draft} draft round, k {k}: {1e3 * statistics.median(times[1:]):8.2f} ms (median of 4, B {B}, context {ids.shape[1]})", flush=True)
+        dmodel._lia_scheduler.close()
+        dmodel.close()
+    model._lia_scheduler.close()
+    model.close()
+
+
+if __name__ == "__main__":
+    main()
