@@ -198,6 +198,27 @@ int lia_embed_padded(const int64_t* ids, const lia_bf16* tok, const lia_bf16* po
 int lia_attention_padded(const lia_bf16* q, long ldq, const lia_bf16* kcache, const lia_bf16* vcache, lia_bf16* out, long ldo,
                          int B, int T, int S, int heads, int head_dim, int cache_batch, int b0, const int32_t* starts_device,
                          void* stream);
+/* ---- ragged cache (build-defined; DESIGN.md 3.11 "row mode"): per-row acceptance of speculative decoding lets the rows' cache
+ * lengths drift apart.  Serves OPT layers whose cache lives in HBM (policy 3), blocks of T >= 2 tokens.
+ * lia_ctx_set_row_lens: the table of lens[b] >= 1 per cache batch row = the positions row b has cached (host pointer, n_rows
+ * entries; NULL or 0 clears it), kept like the key starts: a host copy for validation, a device copy replaced only after the
+ * compute stream has drained.  WHILE A TABLE IS SET every lia_layer_forward is the ragged form: it serves rows b0 .. b0 + B - 1 of the
+ * table, block token t of row b sits at cache position lens[b] + t and attends keys starts[b] .. lens[b] + t (starts: the key-start
+ * table, or zeros); pos0 must be >= every served lens[b] (pass max(lens)) and only sizes buffers.  The q | k | v GEMM writes K and V
+ * into the workspace, a scatter kernel places row (b, t) in cache row (lens[b] + t) * batch + b0 + b, and the attention is the
+ * ragged block launch -- row b bit for bit the block attention of a one-row call at pos0 = lens[b]; it counts in
+ * LIA_CNT_BLOCK_ATTENTION whatever LIA_OPT_BLOCK_ATTENTION says.  LIA_ERR_INVALID, by name: a policy other than 3 or a host cache,
+ * T == 1, lia_layer_forward_last, rows beyond the table, lens[b] outside 1 .. pos0, lens[b] + T > smax, starts[b] > lens[b], a
+ * shape lia_attn_block_takes rejects.  lia_decode_layers (T == 1) is refused the same way.
+ * lia_attn_block_takes: 1 when the block attention launches take T queries per row whose last one sees S keys (S = pos0 + T;
+ * ragged: max(lens) + T) -- the launches' own rule: head_dim 32 / 64 / 128, heads % kv_heads == 0, T >= 2, S - T >= 1,
+ * (heads / kv_heads) * T <= 16, scores and partial outputs within 160 KB of LDS.
+ * lia_embed_ragged: lia_embed_padded's kernel with position lens[b] + t - starts[b] + 2 for block token t of row b.  lens, starts:
+ * DEVICE pointers, B entries (row b <-> b0 + b); starts may be NULL (all zeros). */
+int lia_ctx_set_row_lens(lia_ctx* ctx, const int32_t* lens_host, int n_rows);
+int lia_attn_block_takes(int heads, int kv_heads, int head_dim, int T, int S);
+int lia_embed_ragged(const int64_t* ids, const lia_bf16* tok, const lia_bf16* pos, lia_bf16* y, int B, int T, int H,
+                     const int32_t* lens_device, const int32_t* starts_device, void* stream);
 /* final LN on the last position + tied lm_head + greedy argmax: modeling_opt.py:1563, models.py:424-431,
  * greedy_search.py:367,395.  logits [B,vocab], next_ids [B] (device).  suppress_token >= 0: that token's score
  * counts as -inf (EOS while min_new_tokens is unmet, run_generation.py:173,179-182); -1: none. */
@@ -260,6 +281,12 @@ int lia_lm_verify(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, 
 int lia_llama_lm_verify(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* normw,
                         const lia_bf16* lm, int vocab, float eps, int suppress_token, int n_suppress, const int64_t* block_ids,
                         const int32_t* active, int64_t* greedy, int32_t* accepted, int32_t* common, int64_t* next, void* stream);
+/* lia_lm_verify with a bound per row (build-defined, row mode): suppress_token counts as -inf at block positions t < n_suppress_rows[b]
+ * (int32 [B], device, each in [0, T]; NULL is refused by name).  Everything else, common and next included, as lia_lm_verify. */
+int lia_lm_verify_rows(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* lnw, const lia_bf16* lnb,
+                       const lia_bf16* emb, int vocab, float eps, int suppress_token, const int32_t* n_suppress_rows,
+                       const int64_t* block_ids, const int32_t* active, int64_t* greedy, int32_t* accepted, int32_t* common,
+                       int64_t* next, void* stream);
 
 /* ---- Llama-family layer (BASELINE.json config 4; build-defined: the reference's LlamaDecoderLayer_forward,
  * decoder.py:121-169, has no policy plumbing -- SURVEY.md quirk 3).  Arithmetic = HF transformers' eager bf16 Llama.

@@ -1189,17 +1189,29 @@ extern "C" int lia_attn_decode_padded_launch(const bf16_t* q, long ldq, const bf
 // and its rounding points, and only gains the limit -- so row t is bit for bit lia_attn_decode_kernel over S = pos0 + t + 1 keys with
 // that query row (U, the rows in flight, batches the loads and is not part of any order).  Slots >= G * T (Q is the next
 // instantiated size) have lim = 0: no key, no output.
+// PADDED = 2, the ragged form (per-row acceptance of speculative decoding): row b holds lens[b] cached positions instead of pos0, and
+// starts may be NULL (all zeros).  Both tables are read through readfirstlane -- a row's base length and start are wave-uniform --
+// and everything below derives from S exactly as before, so row b is bit for bit the PADDED = 0 / 1 kernel of a B = 1 launch at
+// pos0 = lens[b].  pos0 is then max(lens): it sized the LDS, and a table entry beyond it is clamped to it (never past the buffers).
 // ---------------------------------------------------------------------------------------------
 template <int D, int Q, int PADDED>
 __global__ __launch_bounds__(256) void lia_attn_block_kernel(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ kc,
                                                               const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, long ldo, int T,
                                                               int pos0, int G, int kv_heads, int Bc, int b0, float scaling,
-                                                              int post_scale, const int* __restrict__ starts) {
+                                                              int post_scale, const int* __restrict__ starts,
+                                                              const int* __restrict__ lens) {
   constexpr int LPK = D / 8;          // lanes per key
   constexpr int KPP = 256 / LPK;      // keys per pass of the workgroup
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int kstart = PADDED ? __builtin_amdgcn_readfirstlane(starts[blockIdx.y]) : 0;
-  const int S = pos0 + T - kstart;          // the keys of the last query of the block
+  int kstart, len;
+  if constexpr (PADDED == 2) {
+    kstart = starts ? __builtin_amdgcn_readfirstlane(starts[blockIdx.y]) : 0;
+    len = min(__builtin_amdgcn_readfirstlane(lens[blockIdx.y]), pos0);
+  } else {
+    kstart = PADDED ? __builtin_amdgcn_readfirstlane(starts[blockIdx.y]) : 0;
+    len = pos0;
+  }
+  const int S = len + T - kstart;           // the keys of the last query of the block
   const int Smin = S - T + 1;               // ... of the first: below it no slot needs a limit
   const int Spad = (S + 3) & ~3;
   float* sc = (float*)smem;                                   // [Q][Spad] scores -> probabilities
@@ -1370,26 +1382,44 @@ static int block_q_of(int n_slots) {
   return 0;
 }
 
+// The one rule of what the block launches take (lia_attn_block_launch, lia_attn_block_ragged_launch, lia_attn_block_takes): T queries
+// per row whose last one sees S keys at most (S = pos0 + T; ragged: pos0 = max(lens)).  -> the instantiated slot count and the LDS
+// bytes, or 0: d other than 32 / 64 / 128, heads % kv_heads, T < 2 or S - T < 1, more than LIA_BLOCK_MAX_Q slots, or scores + partials
+// beyond 160 KB of LDS.
+static int block_shape(int heads, int kv_heads, int d, int T, long S, size_t* lds_out) {
+  if (T < 2 || S - T < 1 || kv_heads <= 0 || heads <= 0 || heads % kv_heads) return 0;
+  if (d != 32 && d != 64 && d != 128) return 0;
+  if ((long)(heads / kv_heads) * T > LIA_BLOCK_MAX_Q) return 0;
+  const int Qv = block_q_of((heads / kv_heads) * T);
+  if (!Qv) return 0;
+  const size_t Spad = (size_t)((S + 3) & ~3L);     // (a padded row holds fewer keys: the unpadded size bounds it)
+  const size_t lds = ((size_t)Qv * Spad + (size_t)4 * Qv * d + (size_t)Qv * 8) * sizeof(float);
+  if (lds > 160 * 1024) return 0;
+  if (lds_out) *lds_out = lds;
+  return Qv;
+}
+
+extern "C" int lia_attn_block_takes(int heads, int kv_heads, int head_dim, int T, int S) { return block_shape(heads, kv_heads, head_dim, T, S, nullptr) ? 1 : 0; }
+
 template <int D>
 static int launch_block(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T, int pos0,
-                        int heads, int kv_heads, int Bc, int b0, float scaling, int post_scale, const int* starts, hipStream_t st) {
+                        int heads, int kv_heads, int Bc, int b0, float scaling, int post_scale, const int* starts, const int* lens,
+                        hipStream_t st) {
   const int G = heads / kv_heads;
-  const int Qv = block_q_of(G * T);
+  size_t lds = 0;
+  const int Qv = block_shape(heads, kv_heads, D, T, (long)pos0 + T, &lds);
   if (!Qv) return -1;
   dim3 grid(kv_heads, B);
-  const int Spad = (pos0 + T + 3) & ~3;     // (a padded row holds fewer keys: the unpadded size bounds it)
-  size_t lds = ((size_t)Qv * Spad + (size_t)4 * Qv * D + (size_t)Qv * 8) * sizeof(float);
-  if (lds > 160 * 1024) return -1;
-#define LIA_BLK(QV)                                                                                                            \
-  if (starts) {                                                                                                                \
+#define LIA_BLK_MODE(QV, MODE, STARTS, LENS)                                                                                   \
+  {                                                                                                                            \
     static bool attr = false;                                                                                                  \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)lia_attn_block_kernel<D, QV, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-    hipLaunchKernelGGL((lia_attn_block_kernel<D, QV, 1>), grid, dim3(256), lds, st, q, ldq, kc, vc, out, ldo, T, pos0, G, kv_heads, Bc, b0, scaling, post_scale, starts); \
-  } else {                                                                                                                     \
-    static bool attr = false;                                                                                                  \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)lia_attn_block_kernel<D, QV, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-    hipLaunchKernelGGL((lia_attn_block_kernel<D, QV, 0>), grid, dim3(256), lds, st, q, ldq, kc, vc, out, ldo, T, pos0, G, kv_heads, Bc, b0, scaling, post_scale, nullptr); \
+    if (!attr) { (void)hipFuncSetAttribute((const void*)lia_attn_block_kernel<D, QV, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
+    hipLaunchKernelGGL((lia_attn_block_kernel<D, QV, MODE>), grid, dim3(256), lds, st, q, ldq, kc, vc, out, ldo, T, pos0, G, kv_heads, Bc, b0, scaling, post_scale, STARTS, LENS); \
   }
+#define LIA_BLK(QV)                                                                                                            \
+  if (lens) LIA_BLK_MODE(QV, 2, starts, lens)                                                                                  \
+  else if (starts) LIA_BLK_MODE(QV, 1, starts, nullptr)                                                                        \
+  else LIA_BLK_MODE(QV, 0, nullptr, nullptr)
   switch (Qv) {
     case 2: LIA_BLK(2) break;
     case 3: LIA_BLK(3) break;
@@ -1403,7 +1433,17 @@ static int launch_block(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_
     default: return -1;
   }
 #undef LIA_BLK
+#undef LIA_BLK_MODE
   return 0;
+}
+
+template <typename... A>
+static int launch_block_d(int d, A... a) {
+  switch (d) {
+    case 128: return launch_block<128>(a...);
+    case 64: return launch_block<64>(a...);
+    default: return launch_block<32>(a...);
+  }
 }
 
 // lia_attn_append_launch's arguments and meaning, for blocks of a few queries: row t of the result is bit for bit the decode launch
@@ -1412,16 +1452,21 @@ static int launch_block(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_
 extern "C" int lia_attn_block_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T,
                                      int pos0, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts,
                                      hipStream_t st) {
-  if (T < 2 || pos0 < 1 || kv_heads <= 0 || heads <= 0 || heads % kv_heads) return -1;
-  if (d != 32 && d != 64 && d != 128) return -1;
-  if ((long)(heads / kv_heads) * T > LIA_BLOCK_MAX_Q) return -1;
+  if (!block_shape(heads, kv_heads, d, T, (long)pos0 + T, nullptr)) return -1;
   if (B <= 0) return 0;
-  const float scaling = 1.0f / sqrtf((float)d);
-  switch (d) {
-    case 128: return launch_block<128>(q, ldq, kc, vc, out, ldo, B, T, pos0, heads, kv_heads, Bc, b0, scaling, post_scale, starts, st);
-    case 64: return launch_block<64>(q, ldq, kc, vc, out, ldo, B, T, pos0, heads, kv_heads, Bc, b0, scaling, post_scale, starts, st);
-    default: return launch_block<32>(q, ldq, kc, vc, out, ldo, B, T, pos0, heads, kv_heads, Bc, b0, scaling, post_scale, starts, st);
-  }
+  return launch_block_d(d, q, ldq, kc, vc, out, ldo, B, T, pos0, heads, kv_heads, Bc, b0, 1.0f / sqrtf((float)d), post_scale, starts, (const int*)nullptr, st);
+}
+
+// The ragged form: served row b holds lens[b] cached positions of its own (device, B entries, 1 <= lens[b] <= max_len; starts: device,
+// B entries with starts[b] <= lens[b], or NULL = all zeros).  Row b is bit for bit lia_attn_block_launch with B = 1 on that row at
+// pos0 = lens[b].  max_len = max(lens) sizes the LDS; the caller guarantees lens[b] + T <= the cache's positions.  The same refusals
+// (at pos0 = max_len), plus a NULL lens: -1, nothing launched.
+extern "C" int lia_attn_block_ragged_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B,
+                                            int T, int max_len, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
+                                            const int* starts, const int* lens, hipStream_t st) {
+  if (!lens || !block_shape(heads, kv_heads, d, T, (long)max_len + T, nullptr)) return -1;
+  if (B <= 0) return 0;
+  return launch_block_d(d, q, ldq, kc, vc, out, ldo, B, T, max_len, heads, kv_heads, Bc, b0, 1.0f / sqrtf((float)d), post_scale, starts, lens, st);
 }
 
 // The attention launch of a call with T queries per row behind pos0 cached positions: see lia_internal.h for the rule.

@@ -81,6 +81,8 @@ extern "C" void lia_ctx_destroy(lia_ctx* c) {
   if (c->hidden_tmp) (void)hipFree(c->hidden_tmp);
   if (c->key_starts_dev) (void)hipFree(c->key_starts_dev);
   delete c->key_starts;
+  if (c->row_lens_dev) (void)hipFree(c->row_lens_dev);
+  delete c->row_lens;
   if (c->host_stage) (void)hipHostFree(c->host_stage);
   if (c->deliver_t0) { (void)hipEventDestroy(c->deliver_t0); (void)hipEventDestroy(c->deliver_t1); }
   if (c->deliver_events) {
@@ -140,6 +142,29 @@ extern "C" int lia_ctx_set_key_starts(lia_ctx* c, const int32_t* starts, int n_r
   HIP_TRY(hipMemcpyAsync(c->key_starts_dev, c->key_starts->data(), (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice, c->compute));
   HIP_TRY(hipStreamSynchronize(c->compute));
   c->key_starts_n = n_rows;
+  return LIA_OK;
+}
+
+// the ragged cache's per-row lengths: lia_ctx_set_key_starts' discipline -- a host copy the layer calls validate against, a device
+// copy that is replaced only after the compute stream has drained
+extern "C" int lia_ctx_set_row_lens(lia_ctx* c, const int32_t* lens, int n_rows) {
+  if (!c || n_rows < 0) return LIA_ERR_INVALID;
+  if (!lens || n_rows == 0) { c->row_lens_n = 0; return LIA_OK; }
+  for (int b = 0; b < n_rows; ++b)
+    if (lens[b] < 1) { lia_set_error("lia_ctx_set_row_lens: lens[%d] = %d < 1 (a ragged block is appended behind a prefill)", b, lens[b]); return LIA_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->compute));
+  if (c->row_lens_cap < n_rows) {
+    if (c->row_lens_dev) (void)hipFree(c->row_lens_dev);
+    c->row_lens_dev = nullptr; c->row_lens_cap = 0; c->row_lens_n = 0;
+    HIP_TRY(hipMalloc((void**)&c->row_lens_dev, (size_t)n_rows * sizeof(int)));
+    c->row_lens_cap = n_rows;
+  }
+  if (!c->row_lens) c->row_lens = new std::vector<int>();
+  c->row_lens->assign(lens, lens + n_rows);
+  HIP_TRY(hipMemcpyAsync(c->row_lens_dev, c->row_lens->data(), (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice, c->compute));
+  HIP_TRY(hipStreamSynchronize(c->compute));
+  c->row_lens_n = n_rows;
   return LIA_OK;
 }
 

@@ -192,12 +192,16 @@ extern "C" void lia_embed_launch(const int64_t* ids, const bf16_t* tok, const bf
 // left-padded rows: row b's tokens start at cache position starts[b]; the token at position p = past_len + t takes the learned
 // position p - starts[b] + 2, a pad position (p < starts[b]) position 1 -- HF's (cumsum(mask) * mask) - 1 + 2
 // (lia/modeling_opt.py:368-378).  The same bf16 add as lia_embed_kernel.
+template <int RAGGED>
 __global__ __launch_bounds__(256) void lia_embed_padded_kernel(const int64_t* __restrict__ ids, const bf16_t* __restrict__ tok,
                                                                 const bf16_t* __restrict__ pos, bf16_t* __restrict__ y, int T,
-                                                                int past_len, int H, const int* __restrict__ starts) {
+                                                                int past_len, int H, const int* __restrict__ starts,
+                                                                const int* __restrict__ lens) {
   const long row = blockIdx.x;
   const int t = (int)(row % T);
-  const int p = past_len + t - starts[row / T];
+  int p;
+  if constexpr (RAGGED) p = lens[row / T] + t - (starts ? starts[row / T] : 0);   // row b's own base length; starts NULL: all zeros
+  else p = past_len + t - starts[row / T];
   const bf16_t* te = tok + ids[row] * (long)H;
   const bf16_t* pe = pos + (long)(p >= 0 ? p + 2 : 1) * H;
   bf16_t* yo = y + row * (long)H;
@@ -216,7 +220,35 @@ __global__ __launch_bounds__(256) void lia_embed_padded_kernel(const int64_t* __
 extern "C" void lia_embed_padded_launch(const int64_t* ids, const bf16_t* tok, const bf16_t* pos, bf16_t* y, int B, int T,
                                         int past_len, int H, const int* starts, hipStream_t st) {
   if (B * T <= 0) return;
-  hipLaunchKernelGGL(lia_embed_padded_kernel, dim3(B * T), dim3(256), 0, st, ids, tok, pos, y, T, past_len, H, starts);
+  hipLaunchKernelGGL(lia_embed_padded_kernel<0>, dim3(B * T), dim3(256), 0, st, ids, tok, pos, y, T, past_len, H, starts, (const int*)nullptr);
+}
+
+// ragged block (per-row acceptance of speculative decoding): block token t of row b sits at cache position lens[b] + t and takes the
+// learned position lens[b] + t - starts[b] + 2.  lens: device, B entries; starts: device, B entries, or NULL (all zeros)
+extern "C" void lia_embed_ragged_launch(const int64_t* ids, const bf16_t* tok, const bf16_t* pos, bf16_t* y, int B, int T, int H,
+                                        const int* lens, const int* starts, hipStream_t st) {
+  if (B * T <= 0) return;
+  hipLaunchKernelGGL(lia_embed_padded_kernel<1>, dim3(B * T), dim3(256), 0, st, ids, tok, pos, y, T, 0, H, starts, lens);
+}
+
+// K / V rows of a ragged block, src [B * T, H] (row b * T + t), into the seq-major cache [smax][Bc][H]: row (b, t) lands in cache row
+// (lens[b] + t) * Bc + b0 + b -- where the GEMM's cache-mode epilogue puts it when every row shares one pos0.  blockIdx.y: 0 = K, 1 = V.
+__global__ __launch_bounds__(256) void lia_kv_scatter_ragged_kernel(const bf16_t* __restrict__ ksrc, const bf16_t* __restrict__ vsrc,
+                                                                     bf16_t* __restrict__ kc, bf16_t* __restrict__ vc, int T, int H,
+                                                                     int Bc, int b0, const int* __restrict__ lens) {
+  const long row = blockIdx.x;
+  const int b = (int)(row / T), t = (int)(row - (long)b * T);
+  const long dst = ((long)(lens[b] + t) * Bc + b0 + b) * H;
+  const uint4* src = (const uint4*)((blockIdx.y ? vsrc : ksrc) + row * (long)H);
+  uint4* out = (uint4*)((blockIdx.y ? vc : kc) + dst);
+  for (int i = threadIdx.x; i < (H >> 3); i += 256) out[i] = src[i];
+}
+
+// lens: device, B entries; the caller guarantees lens[b] + T <= the cache's positions and b0 + B <= Bc; H % 8 == 0
+extern "C" void lia_kv_scatter_ragged_launch(const bf16_t* ksrc, const bf16_t* vsrc, bf16_t* kc, bf16_t* vc, int B, int T, int H, int Bc,
+                                             int b0, const int* lens, hipStream_t st) {
+  if (B * T <= 0) return;
+  hipLaunchKernelGGL(lia_kv_scatter_ragged_kernel, dim3(B * T, 2), dim3(256), 0, st, ksrc, vsrc, kc, vc, T, H, Bc, b0, lens);
 }
 
 // Greedy argmax over bf16 logits [B, vocab], first maximal index on ties (greedy_search.py:367,395).

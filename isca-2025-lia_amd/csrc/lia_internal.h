@@ -31,6 +31,10 @@ extern "C" void lia_embed_launch(const int64_t* ids, const bf16_t* tok, const bf
                                  hipStream_t st);
 extern "C" void lia_embed_padded_launch(const int64_t* ids, const bf16_t* tok, const bf16_t* pos, bf16_t* y, int B, int T, int past_len,
                                         int H, const int* starts, hipStream_t st);
+extern "C" void lia_embed_ragged_launch(const int64_t* ids, const bf16_t* tok, const bf16_t* pos, bf16_t* y, int B, int T, int H,
+                                        const int* lens, const int* starts, hipStream_t st);
+extern "C" void lia_kv_scatter_ragged_launch(const bf16_t* ksrc, const bf16_t* vsrc, bf16_t* kc, bf16_t* vc, int B, int T, int H, int Bc,
+                                             int b0, const int* lens, hipStream_t st);
 extern "C" void lia_argmax_launch(const bf16_t* logits, int64_t* out, int B, int vocab, int suppress, hipStream_t st);
 extern "C" void lia_blit_launch(void* dst, const void* src, size_t bytes, hipStream_t st);
 // lia_sample.hip, lia_score.hip
@@ -40,6 +44,8 @@ extern "C" void lia_token_logprobs_launch(const bf16_t* logits, long ld, int M, 
                                           int64_t* greedy, hipStream_t st);
 extern "C" void lia_verify_argmax_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress, int T, int r0,
                                          int64_t* greedy, hipStream_t st);
+extern "C" void lia_verify_argmax_rows_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress,
+                                              const int* n_suppress_rows, int T, int r0, int64_t* greedy, hipStream_t st);
 extern "C" void lia_verify_accept_launch(const int64_t* block_ids, const int64_t* greedy, const int* active, int B, int T, int* accepted,
                                          int* common, int64_t* next, hipStream_t st);
 // lia_llama.hip
@@ -70,6 +76,10 @@ extern "C" int lia_attn_decode_padded_launch(const bf16_t* q, long ldq, const bf
 extern "C" int lia_attn_block_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T,
                                      int pos0, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts,
                                      hipStream_t st);
+// the ragged form (per-row acceptance): row b at its own base length lens[b] <= max_len (device, B entries); starts or NULL; -1 as above
+extern "C" int lia_attn_block_ragged_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B,
+                                            int T, int max_len, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
+                                            const int* starts, const int* lens, hipStream_t st);
 
 // ---- helpers shared by the API files: C++ linkage, kept out of the dynamic symbol table
 #define LIA_HIDDEN __attribute__((visibility("hidden")))
@@ -155,6 +165,12 @@ struct lia_ctx {
   int* key_starts_dev;
   int key_starts_cap;
   int key_starts_n;           // 0: no table -- every layer call takes the unpadded route
+  // ragged cache (lia_ctx_set_row_lens): per cache batch row, the positions it has cached; kept like the key starts.  While a table
+  // is set, every lia_layer_forward is the ragged form (policy 3, T >= 2)
+  std::vector<int>* row_lens;
+  int* row_lens_dev;
+  int row_lens_cap;
+  int row_lens_n;             // 0: no table
 };
 
 // the workspace is about to be reused: a norm the previous layer call chained into it is gone, and so is a pending hint

@@ -136,6 +136,42 @@ static int layer_forward_impl(lia_ctx* ctx, const lia_layer_desc* d, int policy,
           return LIA_ERR_INVALID;
         }
   }
+  // ragged cache (lia_ctx_set_row_lens): rows b0 .. b0 + B - 1 of the table are the rows' own base lengths; pos0 = max(lens) only
+  // sizes buffers.  Policy 3 with T >= 2 only: K / V go to the plain workspace buffers and a scatter kernel places them, the
+  // attention is the ragged block launch -- always, there is no append fallback behind per-row lengths
+  const bool ragged = ctx->row_lens_n > 0;
+  const int* lens_dev = nullptr;
+  if (ragged) {
+    if (policy != 3 || !kv->on_device) {
+      lia_set_error("lia_layer_forward: row lengths are set (ragged cache), which serves policy 3 with the cache in HBM only; got policy %d with a %s cache",
+                    policy, kv->on_device ? "device" : "host");
+      return LIA_ERR_INVALID;
+    }
+    if (T < 2) { lia_set_error("lia_layer_forward: row lengths are set (ragged cache): a block of T >= 2 tokens only, got T=%d", T); return LIA_ERR_INVALID; }
+    if (tail) { lia_set_error("lia_layer_forward_last: row lengths are set (ragged cache): the tail form is not served"); return LIA_ERR_INVALID; }
+    if (b0 + B > ctx->row_lens_n) {
+      lia_set_error("lia_layer_forward: rows %d..%d beyond the %d rows of the row-length table", b0, b0 + B - 1, ctx->row_lens_n);
+      return LIA_ERR_INVALID;
+    }
+    const int* lens_host = ctx->row_lens->data() + b0;
+    for (int b = 0; b < B; ++b) {
+      if (lens_host[b] < 1 || lens_host[b] > pos0 || lens_host[b] + T > kv->smax) {
+        lia_set_error("lia_layer_forward: row %d holds %d positions: outside 1 .. pos0 = %d (the largest row length), or its block of %d overruns the cache's %d",
+                      b0 + b, lens_host[b], pos0, T, kv->smax);
+        return LIA_ERR_INVALID;
+      }
+      if (kst_host && kst_host[b] > lens_host[b]) {
+        lia_set_error("lia_layer_forward: row %d starts at %d, behind its %d cached positions", b0 + b, kst_host[b], lens_host[b]);
+        return LIA_ERR_INVALID;
+      }
+    }
+    if (!lia_attn_block_takes(d->heads, d->heads, d->hidden / d->heads, T, pos0 + T)) {
+      lia_set_error("lia_layer_forward: row lengths are set (ragged cache), and the ragged block attention does not take %d heads x T=%d at %d keys "
+                    "(at most 16 query slots per KV head, scores within 160 KB of LDS)", d->heads, T, pos0 + T);
+      return LIA_ERR_INVALID;
+    }
+    lens_dev = ctx->row_lens_dev + b0;
+  }
   const int H = d->hidden, F = d->ffn, hd = H / d->heads;
   const long M = (long)B * T;
   // policy 0 on a non-empty cache (a decode step, an appended block) parks the cached prefix and the call's rows, [pos0+T][B][H]
@@ -179,7 +215,9 @@ static int layer_forward_impl(lia_ctx* ctx, const lia_layer_desc* d, int policy,
   int dst_batch, dst_b0, dst_pos0;
   bool cache_mode = true;
   int slab = -1;
-  if (policy == 3) {
+  if (ragged) {   // plain [M,H] buffers; lia_kv_scatter_ragged_launch places the rows behind the projection
+    kdst = kb; vdst = vb; dst_batch = B; dst_b0 = 0; dst_pos0 = 0; cache_mode = false;
+  } else if (policy == 3) {
     kdst = kv->k; vdst = kv->v; dst_batch = kv->batch; dst_b0 = b0; dst_pos0 = pos0;
   } else if (policy == 0) {
     // device slab [S][B][h][d] shared by K then V; two slabs alternate so the previous delivery may still drain
@@ -212,7 +250,14 @@ static int layer_forward_impl(lia_ctx* ctx, const lia_layer_desc* d, int policy,
     }
   }
 
-  if (policy == 2) {
+  if (ragged) {
+    lia_kv_scatter_ragged_launch(kb, vb, kv->k, kv->v, B, T, H, kv->batch, b0, lens_dev, st);
+    if (lia_attn_block_ragged_launch(qb, H, kv->k, kv->v, ao, H, B, T, pos0, d->heads, d->heads, hd, kv->batch, b0, 0, kst_dev, lens_dev, st)) {
+      lia_set_error("ragged attention: unsupported head_dim %d / S %zu", hd, S);
+      return LIA_ERR_INVALID;
+    }
+    ++ctx->attn_opts.block_launches;
+  } else if (policy == 2) {
     // q, k, v -> host; host attention over the host cache; result back (attentions.py:421-440)
     const size_t one = (size_t)M * H * 2;
     rc = ensure_host_stage(ctx, 4 * one);

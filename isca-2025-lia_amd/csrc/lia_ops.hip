@@ -132,6 +132,15 @@ extern "C" int lia_embed_padded(const int64_t* ids, const lia_bf16* tok, const l
   return LIA_OK;
 }
 
+extern "C" int lia_embed_ragged(const int64_t* ids, const lia_bf16* tok, const lia_bf16* pos, lia_bf16* y, int B, int T, int H,
+                                const int32_t* lens, const int32_t* starts, void* stream) {
+  if (!ids || !tok || !pos || !y || !lens) { lia_set_error("lia_embed_ragged: NULL tensor"); return LIA_ERR_MISSING; }
+  if (B <= 0 || T <= 0 || H % 8) { lia_set_error("lia_embed_ragged: B=%d T=%d H=%d", B, T, H); return LIA_ERR_INVALID; }
+  lia_embed_ragged_launch(ids, tok, pos, y, B, T, H, lens, starts, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
 extern "C" int lia_llama_embed(const int64_t* ids, const lia_bf16* tok, lia_bf16* y, int B, int T, int H, void* stream) {
   if (!ids || !tok || !y) return LIA_ERR_MISSING;
   if (B <= 0 || T <= 0 || H % 8) return LIA_ERR_INVALID;
@@ -317,14 +326,14 @@ extern "C" int lia_llama_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh
 static int lm_verify_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int B, int T, int H, const bf16_t* norm_w,
                           const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, int suppress_token, int n_suppress,
                           const int64_t* block_ids, const int32_t* active, int64_t* greedy, int32_t* accepted, int32_t* common,
-                          int64_t* next, hipStream_t st) {
+                          int64_t* next, hipStream_t st, const int32_t* n_suppress_rows = nullptr) {
   if (B <= 0) { lia_set_error("%s: B=%d must be >= 1", who, B); return LIA_ERR_INVALID; }
   if (T < 2) { lia_set_error("%s: T=%d must be >= 2 (the pending token and at least one draft token)", who, T); return LIA_ERR_INVALID; }
   if ((long)B * T > 0x7fffffffL) { lia_set_error("%s: B=%d x T=%d rows", who, B, T); return LIA_ERR_INVALID; }
   if (n_suppress < 0 || n_suppress > T) { lia_set_error("%s: n_suppress=%d must be in [0, T=%d]", who, n_suppress, T); return LIA_ERR_INVALID; }
   if (suppress_token < -1 || (vocab > 0 && suppress_token >= vocab)) { lia_set_error("%s: suppress_token=%d must be -1 or in [0, vocab)", who, suppress_token); return LIA_ERR_INVALID; }
   const int rc = lm_rows_chunked(who, ctx, hidden, ldh, B * T, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
-    lia_verify_argmax_launch(logits, vocab, n, vocab, suppress_token, n_suppress, T, r0, greedy, st);
+    lia_verify_argmax_rows_launch(logits, vocab, n, vocab, suppress_token, n_suppress, n_suppress_rows, T, r0, greedy, st);
   });
   if (rc) return rc;
   lia_verify_accept_launch(block_ids, greedy, active, B, T, accepted, common, next, st);
@@ -348,6 +357,20 @@ extern "C" int lia_lm_verify(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int
   if (!lnb) { lia_set_error("lia_lm_verify: NULL norm bias"); return LIA_ERR_INVALID; }
   return lm_verify_impl("lia_lm_verify", ctx, hidden, ldh, B, T, H, lnw, lnb, emb, vocab, eps, suppress_token, n_suppress, block_ids,
                         active, greedy, accepted, common, next, (hipStream_t)stream);
+}
+
+// lia_lm_verify with a bound per row: n_suppress_rows (device, int32 [B], each in [0, T] -- the caller's to guarantee; a larger entry
+// suppresses at every block position, as T does) in place of the scalar
+extern "C" int lia_lm_verify_rows(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* lnw, const lia_bf16* lnb,
+                                  const lia_bf16* emb, int vocab, float eps, int suppress_token, const int32_t* n_suppress_rows,
+                                  const int64_t* block_ids, const int32_t* active, int64_t* greedy, int32_t* accepted, int32_t* common,
+                                  int64_t* next, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  LIA_VERIFY_NULL("lia_lm_verify_rows", hidden, lnw, emb, block_ids, greedy, accepted, common, next);
+  if (!lnb) { lia_set_error("lia_lm_verify_rows: NULL norm bias"); return LIA_ERR_INVALID; }
+  if (!n_suppress_rows) { lia_set_error("lia_lm_verify_rows: NULL n_suppress_rows"); return LIA_ERR_INVALID; }
+  return lm_verify_impl("lia_lm_verify_rows", ctx, hidden, ldh, B, T, H, lnw, lnb, emb, vocab, eps, suppress_token, 0, block_ids, active,
+                        greedy, accepted, common, next, (hipStream_t)stream, n_suppress_rows);
 }
 
 extern "C" int lia_llama_lm_verify(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* normw,

@@ -94,15 +94,18 @@ extern "C" void lia_token_logprobs_launch(const bf16_t* logits, long ld, int M, 
 // speculative verification (lia_lm_verify): the argmax of a chunk of block rows, then what the block's rows accept
 // ------------------------------------------------------------------------------------------------
 // lia_argmax_kernel's scan and tie rule over row r0 + blockIdx.x of the block; `suppress` counts as -inf where the row's block
-// position (r0 + blockIdx.x) % T is below n_suppress
+// position (r0 + blockIdx.x) % T is below n_suppress -- or, with n_suppress_rows (int32 per block row b = (r0 + blockIdx.x) / T, or
+// NULL), below n_suppress_rows[b]
 __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_verify_argmax_kernel(const bf16_t* __restrict__ logits, long ld, int vocab, int vec,
                                                                             int suppress, int n_suppress, int T, int r0,
-                                                                            int64_t* __restrict__ greedy) {
+                                                                            int64_t* __restrict__ greedy,
+                                                                            const int* __restrict__ n_suppress_rows) {
   __shared__ float sv[LIA_ROW_WAVES];
   __shared__ int si[LIA_ROW_WAVES];
   const int tid = threadIdx.x, lane = tid & 63;
   const bf16_t* row = logits + (long)blockIdx.x * ld;
-  const int sup = (r0 + (int)blockIdx.x) % T < n_suppress ? suppress : -1;
+  const int brow = (r0 + (int)blockIdx.x) / T;
+  const int sup = (r0 + (int)blockIdx.x) % T < (n_suppress_rows ? n_suppress_rows[brow] : n_suppress) ? suppress : -1;
   float best = -INFINITY;
   int bi = 0x7fffffff;
   for (int i = tid * 8; i < vocab; i += LIA_ROW_THREADS * 8) {
@@ -154,11 +157,17 @@ __global__ __launch_bounds__(256) void lia_verify_accept_kernel(const int64_t* _
   for (int b = tid; b < B; b += 256) next[b] = greedy[(long)b * T + lo];
 }
 
-extern "C" void lia_verify_argmax_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress, int T, int r0,
-                                         int64_t* greedy, hipStream_t st) {
+extern "C" void lia_verify_argmax_rows_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress,
+                                              const int* n_suppress_rows, int T, int r0, int64_t* greedy, hipStream_t st) {
   if (n <= 0) return;
   const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
-  hipLaunchKernelGGL(lia_verify_argmax_kernel, dim3(n), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, suppress, n_suppress, T, r0, greedy);
+  hipLaunchKernelGGL(lia_verify_argmax_kernel, dim3(n), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, suppress, n_suppress, T, r0, greedy,
+                     n_suppress_rows);
+}
+
+extern "C" void lia_verify_argmax_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress, int T, int r0,
+                                         int64_t* greedy, hipStream_t st) {
+  lia_verify_argmax_rows_launch(logits, ld, n, vocab, suppress, n_suppress, nullptr, T, r0, greedy, st);
 }
 
 extern "C" void lia_verify_accept_launch(const int64_t* block_ids, const int64_t* greedy, const int* active, int B, int T, int* accepted,

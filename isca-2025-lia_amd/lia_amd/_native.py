@@ -112,6 +112,11 @@ SIGNATURES = {
     "lia_host_layers_forward": (c_int, [ctypes.POINTER(LayerDesc), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "lia_ctx_set_key_starts": (c_int, [c_void_p, c_void_p, c_int]),
+    "lia_ctx_set_row_lens": (c_int, [c_void_p, c_void_p, c_int]),
+    "lia_attn_block_takes": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "lia_embed_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "lia_lm_verify_rows": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lia_embed_padded": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "lia_attention_padded": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_void_p, c_void_p]),

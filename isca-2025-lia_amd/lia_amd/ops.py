@@ -151,6 +151,27 @@ class Context:
         else:
             N.check(self.lib.lia_embed_padded(*args, _ptr(starts), self._st(stream)), "lia_embed")
 
+    def embed_ragged_into(self, ids, tok, pos, y, lens, starts=None, stream=None):
+        """lia_embed_ragged: embed_into for a block on a ragged cache -- lens (int32 [B], device): row b's cached positions, block
+        token t of row b takes the learned position lens[b] + t - starts[b] + 2 (starts: int32 [B], device, or None = zeros)."""
+        _chk(tok)
+        _chk(pos)
+        _chk(lens, torch.int32)
+        _chk(starts, torch.int32)
+        B, T = ids.shape
+        if lens.numel() != B or (starts is not None and starts.numel() != B):
+            raise ValueError(f"lens / starts must have {B} entries, one per row of ids")
+        N.check(self.lib.lia_embed_ragged(_ptr(ids), _ptr(tok), _ptr(pos), _ptr(y), B, T, tok.shape[1], _ptr(lens), _ptr(starts),
+                                          self._st(stream)), "lia_embed_ragged")
+
+    def set_row_lens(self, lens):
+        """lia_ctx_set_row_lens: lens (int32 numpy [rows of the cache batch], or None to clear) -- while set, every layer call is the
+        ragged form (policy 3, T >= 2) on rows b0 .. b0 + B - 1 of the table"""
+        if lens is None:
+            N.check(self.lib.lia_ctx_set_row_lens(self.handle, None, 0), "lia_ctx_set_row_lens")
+        else:
+            N.check(self.lib.lia_ctx_set_row_lens(self.handle, ctypes.c_void_p(lens.ctypes.data), lens.shape[0]), "lia_ctx_set_row_lens")
+
     LM_HEAD_ROWS = 256       # rows per lia_lm_head call (its argmax scratch is sized for that many)
 
     def lm_head(self, hidden, lnw, lnb, emb, eps=1e-5, suppress_token=-1, stream=None):
@@ -266,6 +287,20 @@ class Context:
                                        _ptr(out.accepted), _ptr(out.common), _ptr(out.next), self._st(stream)), "lia_lm_verify")
         return out
 
+    def lm_verify_rows(self, hidden, lnw, lnb, emb, block_ids, n_suppress_rows, eps=1e-5, suppress_token=-1, active=None, stream=None):
+        """lia_lm_verify_rows: lm_verify with one bound per row -- suppress_token counts as -inf at block positions
+        t < n_suppress_rows[b] (int32 [B], device, each in [0, T])."""
+        for t in (lnw, lnb, emb):
+            _chk(t)
+        _chk(n_suppress_rows, torch.int32)
+        B, T, H, out = self._verify_args(hidden, block_ids, active)
+        if n_suppress_rows.numel() != B:
+            raise ValueError(f"n_suppress_rows has {n_suppress_rows.numel()} entries, block_ids {B} rows")
+        N.check(self.lib.lia_lm_verify_rows(self.handle, _ptr(hidden), H, B, T, H, _ptr(lnw), _ptr(lnb), _ptr(emb), emb.shape[0], eps,
+                                            int(suppress_token), _ptr(n_suppress_rows), _ptr(block_ids), _ptr(active), _ptr(out.greedy),
+                                            _ptr(out.accepted), _ptr(out.common), _ptr(out.next), self._st(stream)), "lia_lm_verify_rows")
+        return out
+
     def llama_lm_verify(self, hidden, normw, lm, block_ids, eps=1e-5, suppress_token=-1, n_suppress=0, active=None, stream=None):
         """lia_llama_lm_verify: lm_verify with the final RMSNorm and the untied lm_head of a Llama"""
         for t in (normw, lm):
@@ -292,6 +327,12 @@ class Context:
         y_last: [B,1,H] device."""
         N.check(self.lib.lia_layer_forward_last(self.handle, ctypes.byref(desc), policy, ctypes.byref(weight_ptrs), _ptr(x), _ptr(y_last),
                                                 ctypes.byref(kv), B, T, pos0, b0, self._st(stream)), "lia_layer_forward_last")
+
+
+def block_attention_takes(heads, kv_heads, head_dim, T, S):
+    """lia_attn_block_takes: whether the block attention launches (the ragged one included) take T queries per row whose last one
+    sees S keys -- the launches' own rule, asked of the library"""
+    return bool(N.lib().lia_attn_block_takes(int(heads), int(kv_heads), int(head_dim), int(T), int(S)))
 
 
 def make_desc(hidden, heads, ffn, eps=1e-5):

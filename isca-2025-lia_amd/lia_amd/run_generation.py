@@ -127,6 +127,9 @@ def build_parser():
                         "resident (policies 3 / 3) beside the target; it proposes --draft-tokens tokens per round and one pass of the "
                         "target's weights verifies them (same ids as plain greedy; not with --do-sample or --cpu-layers -1)")
     p.add_argument("--draft-tokens", default=4, type=int, help="with --draft-model: draft tokens per round")
+    p.add_argument("--acceptance", default="common", choices=["common", "row"],
+                   help="with --draft-model: common = every row keeps the minimum over the rows per round; row = every row keeps what it "
+                        "accepted itself on a ragged KV cache (OPT with --prefill-policy 3 --decoding-policy 3)")
     add_init_args(p)
     return p
 
@@ -350,11 +353,18 @@ def load_draft(args):
     return ModelDrafter(model)
 
 
-def summarize_speculation(spec_log, total_list, batch_size, out=print):
-    """accepted draft tokens per round over the timed iterations, beside the latencies: -> the record of --result-json"""
+def summarize_speculation(spec_log, total_list, batch_size, out=print, acceptance="common"):
+    """accepted draft tokens per round over the timed iterations, beside the latencies: -> the record of --result-json.
+    acceptance="row": a row keeps its own count, so the tokens of a round are the mean over the rows (accepted_per_row_round; a full
+    row reports draft_tokens, so this too is an upper bound) instead of the minimum."""
     commons = [c for c, _ in spec_log]
     rec = {"rounds": len(commons), "accepted_per_round": round(float(np.mean(commons)), 3) if commons else None,
            "accepted_histogram": {int(v): int(n) for v, n in zip(*np.unique(commons, return_counts=True))} if commons else {}}
+    if acceptance == "row" and commons:
+        rec.update(acceptance="row", accepted_per_row_round=round(float(np.mean([np.mean(a) for _, a in spec_log])), 3),
+                   accepted_rows=[list(map(int, a)) for _, a in spec_log])
+        out("Per-row acceptance: accepted draft tokens per row and round: %s" % rec["accepted_per_row_round"])
+        commons = [float(np.mean(a)) for _, a in spec_log]
     out("Speculative rounds: %d, accepted draft tokens per round: %s (histogram %s)" % (rec["rounds"], rec["accepted_per_round"], rec["accepted_histogram"]))
     if total_list and commons:
         passes = sum(len(x) - 1 for x in total_list)
@@ -640,6 +650,8 @@ def _main(args, rec=None):
     if args.draft_model:
         spec_log = []
         generate_kwargs.update(draft=load_draft(args), draft_tokens=args.draft_tokens, spec_log=spec_log)
+        if args.acceptance != "common":
+            generate_kwargs.update(acceptance=args.acceptance)
     tokenizer = load_tokenizer(args.model_id)
     if args.prompt_file is not None:
         input_ids, generate_kwargs["attention_mask"] = prompt_file_inputs(args, model.shape.vocab, tokenizer,
@@ -702,7 +714,7 @@ def _main(args, rec=None):
                                 "wire_format_note": "the format of the host copies that streamed (a policy-1 / NUMA-tier / unpinned placement ships raw: scheduler.placement_formats)"}
     if spec_log is not None:
         # (with a drafter a latency entry is a target pass of several tokens: "Average 2... latency" above is per pass)
-        res["speculative"] = summarize_speculation(spec_log, total_list, args.batch_size)
+        res["speculative"] = summarize_speculation(spec_log, total_list, args.batch_size, acceptance=args.acceptance)
     if "decode_tokens_per_s" in res:
         print("Decode throughput: %.2f tokens/s, prefill %.1f ms" % (res["decode_tokens_per_s"], res["prefill_ms"]))
     coop = getattr(model._lia_scheduler, "coop_report", lambda: None)()

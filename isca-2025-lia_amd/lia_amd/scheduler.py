@@ -106,6 +106,26 @@ def check_verify_block(block_ids, kv_state):
         raise ValueError(f"verify: the cache holds {kv_state.smax} positions, the context {kv_state.len} + the block {T} need {kv_state.len + T}")
 
 
+def check_verify_rows(block_ids, kv_state, row_lens, flags, n_gpu, L):
+    """every refusal of OffloadScheduler.verify_rows(), by name"""
+    from . import speculative
+    if block_ids.dim() != 2:
+        raise ValueError(f"verify_rows: block_ids must be [batch, T], got shape {tuple(block_ids.shape)}")
+    B, T = block_ids.shape
+    why = speculative.row_flags_refusal(flags)
+    if why is None and not (getattr(kv_state, "all_on_device", False) and all(kv_state.kv[i].on_device for i in range(L))):
+        why = speculative.ROW_REFUSALS["flags"] + "; this cache has layers on the host"
+    if why:
+        raise ValueError("verify_rows: " + why)
+    if T < 2:
+        raise ValueError(f"verify_rows: a block of at least two tokens, the pending one and a draft (T={T})")
+    if row_lens.shape != (B,) or (row_lens < 1).any():
+        raise ValueError(f"verify_rows: row_lens must hold one cache length >= 1 per row ({B}), got {row_lens.tolist()}")
+    if int(row_lens.max()) + T > kv_state.smax:
+        raise ValueError(f"verify_rows: the cache holds {kv_state.smax} positions, the longest row {int(row_lens.max())} + the block {T} "
+                         f"need {int(row_lens.max()) + T}")
+
+
 class OffloadScheduler:
     """forward(input_ids, kv_state, **lia flags) -> (logits [B,vocab], next_ids [B]) on the device."""
 
@@ -342,6 +362,47 @@ class OffloadScheduler:
         common = int(res.common.item())
         kv_state.len = pos0 + common + 1
         return res, common
+
+    def verify_rows(self, block_ids, kv_state, row_lens, suppress_token=-1, n_suppress_rows=None, active=None, prefill_policy=1,
+                    decoding_policy=1, no_overlap=False, pin_weight=False, gpu_percentage=0, num_minibatch=1, enable_cxl=False,
+                    **_decode_only):
+        """verify() on a ragged cache (DESIGN.md 3.11, row mode): row b of block_ids [B, T] is appended at ITS cache length
+        row_lens[b] (int32 [B]; the caller owns it).  Policies 3 / 3 only -- every layer's cache in HBM.  verify()'s phases with the
+        library's row-length table (lia_ctx_set_row_lens) set around the embedding and the layer calls and cleared in a finally:
+        while it is set every layer call is the ragged form (per-row positions, K/V scatter, ragged block attention), with
+        max(row_lens) as the scalar position that sizes buffers.  num_minibatch > 1 serves slices of the table as it does of the key
+        starts.  suppress_token counts as -inf at block positions < n_suppress_rows[b] (int32 [B] or None: zeros).  Returns
+        ops.VerifyResult (device tensors); kv_state.len is NOT advanced."""
+        row_lens = np.ascontiguousarray(np.asarray(row_lens, dtype=np.int32))
+        flags = dict(prefill_policy=prefill_policy, decoding_policy=decoding_policy, cpu_layers=int(_decode_only.get("cpu_layers") or 0))
+        sh = self.model.shape
+        check_verify_rows(block_ids, kv_state, row_lens, flags, int(sh.layers * gpu_percentage / 100), sh.layers)
+        B, T = block_ids.shape
+        len0 = kv_state.len
+        kv_state.len = int(row_lens.max())                 # the scalar position of the ragged calls: it sizes buffers only
+        try:
+            s = self._validate(block_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch)
+            s.every_pos = s.verify = True
+            self._place(s, kv_state, pin_weight, enable_cxl, None, 0, None)
+            m, ctx = self.model, self.ctx
+            ids_dev = block_ids.to(device="cuda", dtype=torch.int64).contiguous()
+            act_dev = None if active is None else torch.as_tensor(active).to(device="cuda", dtype=torch.int32).contiguous()
+            nsup = np.zeros(B, np.int32) if n_suppress_rows is None else np.ascontiguousarray(np.asarray(n_suppress_rows, dtype=np.int32))
+            if nsup.shape != (B,) or (nsup < 0).any() or (nsup > T).any():
+                raise ValueError(f"verify_rows: n_suppress_rows must hold one count in [0, T={T}] per row, got {nsup.tolist()}")
+            nsup_dev = torch.from_numpy(nsup).to("cuda")
+            lens_dev = torch.from_numpy(row_lens).to("cuda")
+            ctx.set_row_lens(row_lens)
+            try:
+                ctx.embed_ragged_into(ids_dev, m.embed_tokens, m.embed_positions, s.x, lens_dev, starts=self._key_starts_for(B)[1])
+                hidden = self._run_layers(s, kv_state)
+            finally:
+                ctx.set_row_lens(None)
+            res = ctx.lm_verify_rows(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, nsup_dev, sh.ln_eps, suppress_token, act_dev)
+            self._deliver(s, kv_state)
+        finally:
+            kv_state.len = len0
+        return res
 
     # -- left-padded batches (generation.generate(..., attention_mask=)) -----------------------------------------------------
     def set_key_starts(self, starts):

@@ -10,6 +10,11 @@ weights is the cost of a token and the batch is small; at a large batch the mini
 A drafter is any object with  propose(ids [B, n] int64 CPU, k, suppress) -> int64 [B, k]:  its guess of the k tokens behind ids.
 suppress = (token, n): the target will not produce `token` (EOS below min_new_tokens) as the first n of them; a drafter that ignores
 it only loses acceptance.  An optional attribute `vocab` is checked against the target's.
+
+Row mode, generate(..., acceptance="row") (speculative_search_rows): OPT targets whose KV cache lives in HBM on every layer
+(policies 3 / 3) keep one cache length PER ROW -- row b appends accepted[b] + 1 tokens per round, whatever the other rows accept, and
+the number of target passes is set by the slowest row's own acceptance.  The drafter then needs
+propose_rows(rows: list of 1-D int64 CPU tensors, k, suppress_rows) -> int64 [B, k]  with suppress_rows = (token, [n per row]).
 """
 import time
 
@@ -23,6 +28,64 @@ REFUSALS = {
     "cpu_layers": "draft together with cpu_layers=-1 (the online cooperative split) is not supported: the controller samples "
                   "single-token decode steps; name a fixed cpu_layers",
 }
+
+
+ACCEPTANCE = ("common", "row")
+ROW_REFUSALS = {
+    "llama": "acceptance='row' is not supported for Llama-family models: their RoPE positions are one per batch, not per row yet",
+    "state": "acceptance='row' together with return_state=True or past= is not supported: a GenerationState has one cache length, "
+             "row mode keeps one per row",
+    "flags": "acceptance='row' needs the KV cache in HBM on every layer: prefill_policy=3 and decoding_policy=3 (any gpu_percentage)",
+    "cpu_layers": "acceptance='row' together with cpu_layers is not supported: a host-computed layer keeps its cache on the host",
+    "propose_rows": "acceptance='row' needs a drafter with propose_rows(rows, k, suppress_rows)",
+    "llama_draft": "acceptance='row' with a Llama draft model is not supported: ModelDrafter.propose_rows re-prefills left padded, "
+                   "which the Llama path does not have",
+}
+
+
+def check_acceptance(acceptance):
+    if acceptance not in ACCEPTANCE:
+        raise ValueError(f"acceptance must be 'common' or 'row', got {acceptance!r}")
+
+
+def row_flags_refusal(lia):
+    """the refusal (a ROW_REFUSALS text) of a flag set row mode does not serve, or None"""
+    if lia.get("prefill_policy", 1) != 3 or lia.get("decoding_policy", 1) != 3:
+        return ROW_REFUSALS["flags"] + f"; got {lia.get('prefill_policy', 1)} / {lia.get('decoding_policy', 1)}"
+    if lia.get("cpu_layers", 0) != 0:
+        return ROW_REFUSALS["cpu_layers"]
+    return None
+
+
+def largest_row_block(shape, T, max_new_tokens, k):
+    """the largest draft_tokens <= k whose verify block (k + 1 queries, a cache of T + max_new_tokens + k positions) the ragged block
+    attention takes (ops.block_attention_takes: the launch's own rule), or 0"""
+    from . import ops
+    kvh = getattr(shape, "kv_heads", shape.heads)
+    for kk in range(k, 0, -1):
+        if ops.block_attention_takes(shape.heads, kvh, shape.head_dim, kk + 1, T + max_new_tokens + kk):
+            return kk
+    return 0
+
+
+def check_row_mode(model, draft, k, lia, T, max_new_tokens, past=None, return_state=False):
+    """every refusal of generate(draft=, acceptance="row"), by name (ValueError), before any forward"""
+    if getattr(model, "family", "opt") == "llama":
+        raise ValueError(ROW_REFUSALS["llama"])
+    if past is not None or return_state:
+        raise ValueError(ROW_REFUSALS["state"])
+    why = row_flags_refusal(lia)
+    if why:
+        raise ValueError(why)
+    if not callable(getattr(draft, "propose_rows", None)):
+        raise ValueError(ROW_REFUSALS["propose_rows"] + f", got {type(draft).__name__}")
+    if isinstance(draft, ModelDrafter) and getattr(draft.model, "family", "opt") == "llama":
+        raise ValueError(ROW_REFUSALS["llama_draft"])
+    fit = largest_row_block(model.shape, T, max_new_tokens, k)
+    if fit != k:
+        raise ValueError(f"acceptance='row': the ragged block attention does not take a verify block of draft_tokens={k} + 1 queries on "
+                         f"a cache of {T + max_new_tokens + k} positions ({model.shape.heads} heads of {model.shape.head_dim}); "
+                         + (f"the largest draft_tokens that fits is {fit}" if fit else "no draft_tokens fits"))
 
 
 def block_attention_pays(head_dim, heads, kv_heads, B, T, pos0):
@@ -100,6 +163,22 @@ class ReplayDrafter:
         return out
 
 
+    def propose_rows(self, rows, k, suppress_rows=(-1, None)):
+        """propose() for rows of their own lengths (row mode): row b continues the recording behind its len(rows[b]) tokens; the
+        script is the same, one entry per round"""
+        B = len(rows)
+        out = torch.zeros((B, k), dtype=torch.int64)
+        for b, row in enumerate(rows):
+            n = int(row.shape[0])
+            have = max(0, min(k, self.ids.shape[1] - n))
+            out[b, :have] = self.ids[b, n:n + have]
+        for b, a in enumerate(self.script(self.rounds, B, k)):
+            if a < k:
+                out[b, a] ^= 1
+        self.rounds += 1
+        return out
+
+
 class ModelDrafter:
     """A second, all-resident model (policy 3 / 3, gpu_percentage 100) with its own scheduler, context and cache.  Every round it
     feeds the tokens its cache lacks -- one, or two after a fully accepted round -- through the decode / append paths and runs
@@ -150,6 +229,114 @@ class ModelDrafter:
         self.fed = torch.cat([ids, out[:, :k - 1]], dim=1)
         self.rounds += 1
         return out
+
+
+    def propose_rows(self, rows, k, suppress_rows=(-1, None), pad_token_id=1):
+        """Row mode's baseline: every round is a fresh generation of its own -- the rows right-aligned (left padded to the longest),
+        prefilled through the attention_mask machinery (the scheduler's key starts), then k - 1 decode steps.  No cache is kept
+        between rounds.  suppress_rows = (token, [n per row]): `token` is suppressed at the steps below the SMALLEST n, so the
+        drafter never suppresses where the target would not (a drafter that suppresses too little only loses acceptance)."""
+        if getattr(self.model, "family", "opt") == "llama":
+            raise ValueError(ROW_REFUSALS["llama_draft"])
+        B = len(rows)
+        lens = [int(r.shape[0]) for r in rows]
+        n = max(lens)
+        if n + k > self.model.shape.max_pos:
+            raise ValueError(f"the draft model has max positions {self.model.shape.max_pos}, the round reaches {n + k}")
+        ids = torch.full((B, n), pad_token_id, dtype=torch.int64)
+        for b, r in enumerate(rows):
+            ids[b, n - lens[b]:] = torch.as_tensor(r, dtype=torch.int64)
+        starts = np.asarray([n - v for v in lens], dtype=np.int32)
+        tok, n_rows = suppress_rows
+        n_sup = min(n_rows) if n_rows is not None and len(n_rows) else 0
+        kv = self.sched.new_kv_state(B, n, k, **self.FLAGS)
+        self.kv = self.fed = None                      # (a later propose() of common mode starts from a fresh cache)
+        self.sched.set_key_starts(starts if starts.any() else None)
+        try:
+            cur, dev = ids, []
+            for i in range(k):
+                sup = tok if i < n_sup else -1
+                _, nxt = self.sched.forward(cur, kv, max_new_tokens=k, suppress_token=sup, **self.FLAGS)
+                dev.append(nxt)
+                cur = nxt.view(B, 1)
+            out = torch.stack(dev, dim=1).cpu()
+        finally:
+            self.sched.set_key_starts(None)
+        self.prefills += 1
+        self.rounds += 1
+        return out
+
+
+def speculative_search_rows(model, sched, input_ids, max_new_tokens, min_new_tokens, eos_token_id, pad_token_id, token_latency, lia,
+                            draft, draft_tokens, spec_log=None, step_hook=None, max_steps=None, starts=None):
+    """speculative_search with one cache length per row (acceptance="row").  Row b has generated g[b] tokens, caches T + g[b] - 1
+    positions (its last token is pending), and appends greedy[b, :accepted[b] + 1] per round, cut behind its EOS token and at
+    max_new_tokens.  A finished or full row is inactive: its block is pad tokens, its length stands still, it never holds another
+    row back.  The output is _greedy_search's: finished rows padded with pad_token_id up to the length the greedy loop would have
+    reached (the longest row's).  latency_list has one entry per target pass; spec_log receives (min over the active rows,
+    accepted per row) per round."""
+    k = draft_tokens
+    ids = torch.as_tensor(input_ids, dtype=torch.int64).cpu()
+    if ids.dim() != 2:
+        raise ValueError("input_ids must be [batch, seq]")
+    B, T = ids.shape
+    check_row_mode(model, draft, k, lia, T, max_new_tokens)
+    if T + max_new_tokens + k > model.shape.max_pos:
+        raise ValueError(f"prompt {T} + max_new_tokens {max_new_tokens} + draft_tokens {k} exceeds max positions {model.shape.max_pos}")
+    kv = sched.new_kv_state(B, T, max_new_tokens + k, **lia)
+    limit = max_new_tokens if max_steps is None else min(max_new_tokens, max_steps)
+    ids_buf = torch.full((B, T + max_new_tokens), pad_token_id, dtype=torch.int64)
+    ids_buf[:, :T] = ids
+    g = np.zeros(B, dtype=np.int64)                    # tokens generated per row
+    unfinished = np.ones(B, dtype=bool)
+    latency_list = []
+
+    def append(b, token):
+        ids_buf[b, T + g[b]] = token
+        g[b] += 1
+        if eos_token_id is not None and token == eos_token_id:
+            unfinished[b] = False
+
+    if step_hook is not None:
+        step_hook(0)
+    tic = time.time()
+    suppress = eos_token_id if (eos_token_id is not None and 0 < min_new_tokens) else -1
+    _, nxt = sched.forward(ids, kv, max_new_tokens=max_new_tokens, suppress_token=suppress, **lia)
+    for b, token in enumerate(nxt.cpu().tolist()):
+        append(b, token)
+    latency_list.append(time.time() - tic)
+    rnd = 0
+    while True:
+        active = unfinished & (g < limit)
+        if not active.any():
+            break
+        rnd += 1
+        if step_hook is not None:
+            step_hook(rnd)
+        tic = time.time()
+        row_lens = (T + g - 1).astype(np.int32)
+        n_sup = np.clip(min_new_tokens - g, 0, k + 1).astype(np.int32) if eos_token_id is not None else np.zeros(B, np.int32)
+        sup_tok = eos_token_id if n_sup.any() else -1
+        rows = [ids_buf[b, :T + g[b]] for b in range(B)]
+        prop = torch.as_tensor(draft.propose_rows(rows, k, (sup_tok, np.minimum(n_sup, k).tolist())), dtype=torch.int64).cpu()
+        if tuple(prop.shape) != (B, k):
+            raise ValueError(f"draft.propose_rows returned shape {tuple(prop.shape)}, expected {(B, k)}")
+        block = torch.cat([torch.stack([r[-1] for r in rows])[:, None], prop], dim=1)
+        block[torch.from_numpy(~active)] = pad_token_id                      # an inactive row is fed pad tokens
+        res = sched.verify_rows(block, kv, row_lens, suppress_token=sup_tok, n_suppress_rows=n_sup,
+                                active=torch.from_numpy(active.astype(np.int32)), **lia)
+        greedy, acc = res.greedy.cpu(), res.accepted.cpu().tolist()
+        if spec_log is not None:
+            spec_log.append((min(a for a, on in zip(acc, active) if on), acc))
+        for b in np.flatnonzero(active):
+            for i in range(acc[b] + 1):
+                append(b, int(greedy[b, i]))
+                if not unfinished[b] or g[b] >= limit:
+                    break
+        latency_list.append(time.time() - tic)
+    step = int(g.max())                                # where the greedy loop stops: every row finished, or the limit
+    out = ids_buf[:, :T + step].clone() if step < max_new_tokens else ids_buf
+    return (out, latency_list) if token_latency else out
 
 
 def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, eos_token_id, pad_token_id, token_latency, lia,

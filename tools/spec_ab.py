@@ -13,7 +13,16 @@ logit).  Every line still reports whether its acceptance stayed on the script an
 only lines that stayed on it are figures of that acceptance.  The draft
 round (k decode-shaped steps of the small model, all resident, its own context) is timed apart: a ReplayDrafter costs nothing, so
 tokens/s with a real drafter of that acceptance is B (common + 1) / (verify + draft round).  Host clock around the passes (each ends
-in a device synchronise); medians."""
+in a device synchronise); medians.
+
+    python tools/spec_ab.py --config opt30b-kv-hbm --batch 64 --pool 0 --acceptance common,row [--reps 2] [--ks 1,4,7]
+
+--acceptance common,row (KV cache in HBM on every layer, policies 3 / 3): per-row acceptance on a ragged cache beside the one-length
+loop, in the same process, the two modes' generations taken in turn --reps times.  The ReplayDrafter draws every row's count
+independently per round (uniform on 0 .. k, seeded), the same script for both modes.  Per k and mode: the verify pass (median, and
+the min .. max of the generations' medians: the run-to-run spread), the passes, tokens/s; then the accepted counts per round, each
+line marked on or off the script (off: some active row's count inside the run differs from its scripted one -- such a line is not
+a figure of an acceptance rate).  The ModelDrafter's row-mode round (a fresh left-padded prefill + k - 1 steps) is timed at the end."""
 import argparse
 import os
 import statistics
@@ -27,6 +36,7 @@ CONFIGS = {     # the lia_online-shaped lines (batch 1, in 256 / out 32) at thei
     "opt30b-online-1-1": dict(model="opt-30b", flags=dict(prefill_policy=1, decoding_policy=1, gpu_percentage=64, pin_weight=True)),
     "opt30b-online-0-1": dict(model="opt-30b", flags=dict(prefill_policy=0, decoding_policy=1, gpu_percentage=58, pin_weight=True)),
     "opt30b-headline": dict(model="opt-30b", flags=dict(prefill_policy=0, decoding_policy=2, gpu_percentage=10, pin_weight=True)),
+    "opt30b-kv-hbm": dict(model="opt-30b", flags=dict(prefill_policy=3, decoding_policy=3, gpu_percentage=10, pin_weight=True)),
     "opt1.3b-resident": dict(model="opt-1.3b", flags=dict(prefill_policy=3, decoding_policy=3, gpu_percentage=100, pin_weight=True)),
 }
 
@@ -42,6 +52,41 @@ def build(name, flags):
     return shape, model
 
 
+def rows_ab(a, model, prompt, rec, plain, step, ks, modes, kw, generate, ReplayDrafter):
+    """common and row mode under one script of independent per-row counts, their generations taken in turn"""
+    import numpy as np
+    B = prompt.shape[0]
+    for k in ks:
+        rs = np.random.RandomState(k)
+        scr = rs.randint(0, k + 1, size=(a.new + 1, B)).tolist()
+        runs = {m: [] for m in modes}
+        for rep in range(a.reps):
+            for m in modes:
+                d, log = ReplayDrafter(rec, scr), []
+                t0 = time.time()
+                out, slat = generate(model, prompt, max_new_tokens=a.new, draft=d, draft_tokens=k, spec_log=log, acceptance=m, **kw)
+                runs[m].append((slat, log, out, time.time() - t0))
+        for m in modes:
+            meds = [statistics.median(sl[1:]) for sl, _, _, _ in runs[m]]
+            every = [v for sl, _, _, _ in runs[m] for v in sl[1:]]
+            slat, log, out, wall = runs[m][-1]
+            differ = int((out != plain).any(dim=1).sum())
+            print(f"  k {k} {m:6s}: verify pass {1e3 * statistics.median(every):8.2f} ms (generations' medians {1e3 * min(meds):.2f} .. {1e3 * max(meds):.2f}; "
+                  f"{statistics.median(every) / step:5.2f} x a decode step), {len(slat) - 1:3d} passes, {B * (a.new - 1) / sum(slat[1:]):8.2f} tokens/s "
+                  f"({step * (a.new - 1) / sum(slat[1:]):5.2f} x plain), wall {wall:6.2f} s, block attention launches "
+                  f"{model._lia_scheduler.ctx.block_attention_launches()}, rows differing from plain {differ}", flush=True)
+            g = [1] * B
+            for r, (lo, acc) in enumerate(log):
+                if m == "common":
+                    lim = a.new - g[0]
+                    on = [min(x, lim) for x in acc] == [min(x, lim) for x in scr[r]]
+                    g = [v + lo + 1 for v in g]
+                else:
+                    on = all(v >= a.new or min(x, a.new - v) == min(w, a.new - v) for v, x, w in zip(g, acc, scr[r]))
+                    g = [v if v >= a.new else min(a.new, v + x + 1) for v, x in zip(g, acc)]
+                print(f"      round {r:2d} [{'on ' if on else 'OFF'} script] kept {lo if m == 'common' else 'per row'}, accepted per row {acc}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True, choices=sorted(CONFIGS))
@@ -51,6 +96,8 @@ def main():
     ap.add_argument("--ks", type=str, default="1,2,4,7")
     ap.add_argument("--draft", type=str, default="opt-125m")
     ap.add_argument("--append-policy", type=int, default=None)
+    ap.add_argument("--acceptance", type=str, default="common", help="common | row | common,row (row: policies 3 / 3 only)")
+    ap.add_argument("--reps", type=int, default=2, help="with --acceptance common,row: generations per k and mode, taken in turn")
     ap.add_argument("--pool", type=int, default=16, help="candidate prompts the batch is chosen from (0: take the first --batch)")
     a = ap.parse_args()
     import torch
@@ -83,6 +130,26 @@ def main():
     plain = rec[:, :a.prompt + a.new]
     step = statistics.median(lat[1:])
     print(f"  plain greedy: prefill {1e3 * lat[0]:9.1f} ms, decode step {1e3 * step:8.2f} ms (median of {len(lat) - 1}), {B / step:8.2f} tokens/s", flush=True)
+    modes = a.acceptance.split(",")
+    if modes != ["common"]:
+        rows_ab(a, model, prompt, rec, plain, step, ks, modes, kw, generate, ReplayDrafter)
+        if a.draft != "none":
+            _, dmodel = build(a.draft, ModelDrafter.FLAGS)
+            d = ModelDrafter(dmodel)
+            for k in ks:
+                rows = [rec[b, :a.prompt + 1 + (3 * b) % (a.new - 1)] for b in range(B)]        # lengths spread over the run
+                times = []
+                for r in range(4):
+                    t0 = time.time()
+                    d.propose_rows(rows, k, (-1, None))
+                    times.append(time.time() - t0)
+                print(f"  {a.draft} row-mode draft round (left-padded prefill of {max(len(r) for r in rows)} + {k - 1} steps), k {k}: "
+                      f"{1e3 * statistics.median(times[1:]):8.2f} ms (median of 3, B {B})", flush=True)
+            dmodel._lia_scheduler.close()
+            dmodel.close()
+        model._lia_scheduler.close()
+        model.close()
+        return
     for k in ks:
         for acc in sorted({0, k // 2, k}):
             d, log = ReplayDrafter(rec, [[acc] * B] * (a.new + 1)), []
