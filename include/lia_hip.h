@@ -483,6 +483,29 @@ int lia_stream_decode_stats(lia_streamer* s, long* launches, double* ms, double*
  * right before the first timed step.  (busy_ms of lia_stream_stats includes the staging memcpy for PAGEABLE sources.) */
 int lia_stream_poll_decode_stats(lia_streamer* s, long* launches, double* ms, double* bytes_in, double* bytes_out, int reset);
 void* lia_stream_copy_stream(lia_streamer* s);
+/* Decode mode (build-defined): a decode step is link-bound and its consumer needs a slot for a fraction of a layer's link time, so
+ * keep_slots slots serve it and the others idle.  While the mode is on, slots keep_slots .. n_slots - 1 and their staging areas leave
+ * the ring and hold layers in their WIRE format -- `capacity` entries, each with room for entry_bytes -- that the decode kernel
+ * rebuilds in a kept slot every step without crossing the link again; the staging areas of the kept slots become landing buffers
+ * that belong to no slot, so the link runs ahead by landing buffers while the slots cycle through the cached layers.  Nothing is
+ * allocated or freed by a mode change, and every hand-over of memory is ordered by events on the copy and decode streams.
+ *   capacity: entries that fit; 0 when n_slots <= keep_slots or no packed layer was ever staged (raw wire).
+ *   enable: LIA_ERR_INVALID when the capacity is 0 or the mode is on.  Prefetches in flight into slots >= keep_slots are
+ *       abandoned by it (their copies and decodes finish first); those into kept slots stay valid.
+ *   land: H2D copy of an encoded layer into landing buffer `landing` (< keep_slots), behind the decode that last read it.
+ *   decode_landed: landing buffer -> slot (< keep_slots) behind the copy and the slot's last release; the slot is then waited
+ *       for and released with lia_stream_wait / lia_stream_release as ever.
+ *   decode_cached: entry -> slot; the first call for an entry copies host_ptr into it first (counted by lia_stream_stats like
+ *       any copy), later calls (same host_ptr and bytes) copy nothing.  Only layers that their validator passed belong here.
+ *   disable: every entry is dropped, slots and staging areas return to the ring behind the mode's last decode.  The legacy packed
+ *       entry points are refused while the mode is on; lia_stream_prefetch (a raw layer) works on the kept slots. */
+int lia_stream_cache_capacity(lia_streamer* s, int keep_slots, size_t entry_bytes);
+int lia_stream_cache_enable(lia_streamer* s, int keep_slots, size_t entry_bytes);
+int lia_stream_cache_disable(lia_streamer* s);
+int lia_stream_land(lia_streamer* s, int landing, const void* host_ptr, size_t packed_bytes, int pinned);
+int lia_stream_decode_landed(lia_streamer* s, int landing, int slot, size_t n_values, int format);
+int lia_stream_decode_cached(lia_streamer* s, int entry, int slot, const void* host_ptr, size_t packed_bytes, size_t n_values, int format,
+                             int pinned);
 
 /* ---- host memory tiers ------------------------------------------------------------------------------
  * The four exports of the reference's libnuma shim, lia/cxl/numa_alloc.c:7,25,66,108 (same names, same

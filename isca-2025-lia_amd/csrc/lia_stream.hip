@@ -40,7 +40,31 @@ struct lia_streamer {
   hipEvent_t bounce_done[2];
   int bounce_next;
   double bytes, busy_ms;
+  // wire cache (lia_stream_cache_*, decode mode): while keep_slots != 0 the slots and staging areas from keep_slots on are a pool of
+  // n_entries wire-format layers, entry_stride bytes apart (the first entries_in_slots of them in the slots' bytes, the rest in the
+  // staging areas'), and the staging areas below keep_slots are landing buffers that no longer belong to a slot
+  int keep_slots, n_entries, entries_in_slots;
+  size_t entry_stride;
+  std::vector<char> entry_filled;
+  std::vector<const void*> entry_src;
+  std::vector<size_t> entry_bytes;
+  std::vector<hipEvent_t> drained;     // per landing buffer, on the decode stream: the decode that last read it has finished
+  std::vector<char> has_drained;
+  std::vector<size_t> landing_bytes;
+  hipEvent_t cache_idle;               // on the decode stream when the mode ends: no decode reads an entry or a landing buffer any more
+  // copy timing of the mode: its copies belong to no slot, so their event pairs come from a ring
+  std::vector<hipEvent_t> r0, r1;
+  std::vector<char> ring_pending;
+  std::vector<size_t> ring_bytes;
+  int ring_next;
 };
+
+constexpr int LIA_CACHE_MAX_ENTRIES = 64;
+constexpr int LIA_CACHE_TIMING_RING = 16;
+// The decode kernels read a little past the bytes shipped: 16 bytes of stream padding for a consistent encoding, at most
+// (1024 codes) / 2 + 8 bytes behind the level-3 stream whatever the planes hold once the validator passed the tables
+// (lia_pack10_validate), 2 bytes behind pack10a's words.  Every entry keeps this much room behind its layer.
+constexpr size_t LIA_CACHE_READ_SLACK = 4096;
 
 static void streamer_collect_decode(lia_streamer* s, int slot, bool wait) {
   if (s->decode_pending.empty() || !s->decode_pending[slot]) return;
@@ -66,6 +90,20 @@ static void streamer_collect(lia_streamer* s, int slot) {
   s->timing_pending[slot] = 0;
 }
 
+// the same for record r of the decode mode's timing ring; wait = false: only if the copy has finished
+static void streamer_collect_ring(lia_streamer* s, int r, bool wait) {
+  if (!s->ring_pending[r]) return;
+  if (!wait && hipEventQuery(s->r1[r]) != hipSuccess) return;
+  if (hipEventSynchronize(s->r1[r]) == hipSuccess) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->r0[r], s->r1[r]) == hipSuccess) {
+      s->busy_ms += ms;
+      s->bytes += (double)s->ring_bytes[r];
+    }
+  }
+  s->ring_pending[r] = 0;
+}
+
 extern "C" int lia_stream_create(lia_ctx* ctx, int n_slots, size_t slot_bytes, lia_streamer** out) {
   if (!ctx || !out || n_slots < 1 || n_slots > 16 || slot_bytes == 0) { lia_set_error("lia_stream_create: n_slots=%d slot_bytes=%zu", n_slots, slot_bytes); return LIA_ERR_INVALID; }
   *out = nullptr;
@@ -74,6 +112,7 @@ extern "C" int lia_stream_create(lia_ctx* ctx, int n_slots, size_t slot_bytes, l
   s->bounce[0] = s->bounce[1] = nullptr; s->bounce_done[0] = s->bounce_done[1] = nullptr; s->bounce_next = 0;
   s->bytes = 0; s->busy_ms = 0; s->slots = nullptr; s->staging = nullptr; s->staging_bytes = 0;
   s->dec_ms = s->dec_in = s->dec_out = 0; s->dec_launches = 0;
+  s->keep_slots = s->n_entries = s->entries_in_slots = 0; s->entry_stride = 0; s->cache_idle = nullptr; s->ring_next = 0;
   HIP_TRY(hipMalloc((void**)&s->slots, s->slot_bytes * n_slots));
   if (ctx->serialized) s->copy = ctx->compute;
   else HIP_TRY(hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking));
@@ -107,6 +146,10 @@ extern "C" void lia_stream_destroy(lia_streamer* s) {
     for (hipEvent_t e : s->landed) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->d0) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->d1) (void)hipEventDestroy(e);
+    for (hipEvent_t e : s->drained) (void)hipEventDestroy(e);
+    for (hipEvent_t e : s->r0) (void)hipEventDestroy(e);
+    for (hipEvent_t e : s->r1) (void)hipEventDestroy(e);
+    if (s->cache_idle) (void)hipEventDestroy(s->cache_idle);
     if (s->decode != s->ctx->compute) (void)hipStreamDestroy(s->decode);
     (void)hipFree(s->staging);
   }
@@ -126,6 +169,7 @@ extern "C" void* lia_stream_copy_stream(lia_streamer* s) { return s ? (void*)s->
 // declared ready.
 extern "C" int lia_stream_begin(lia_streamer* s, int slot) {
   if (!s || slot < 0 || slot >= s->n_slots) { lia_set_error("lia_stream_begin: slot=%d", slot); return LIA_ERR_INVALID; }
+  if (s->keep_slots && slot >= s->keep_slots) { lia_set_error("lia_stream_begin: slot %d holds cached layers (decode mode keeps %d slots)", slot, s->keep_slots); return LIA_ERR_INVALID; }
   streamer_collect(s, slot);
   if (s->has_release[slot]) HIP_TRY(hipStreamWaitEvent(s->copy, s->released[slot], 0));
   // A prefetch the caller dropped (never waited for, never released) may still have its decode kernel running on the side
@@ -199,6 +243,18 @@ static int ensure_staging(lia_streamer* s) {
     HIP_TRY(hipEventCreate(&s->d0[i]));
     HIP_TRY(hipEventCreate(&s->d1[i]));
   }
+  // everything the decode mode needs, so that turning it on or off allocates nothing
+  s->drained.resize(s->n_slots);
+  s->has_drained.assign(s->n_slots, 0); s->landing_bytes.assign(s->n_slots, 0);
+  for (int i = 0; i < s->n_slots; ++i) HIP_TRY(hipEventCreateWithFlags(&s->drained[i], hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&s->cache_idle, hipEventDisableTiming));
+  s->r0.resize(LIA_CACHE_TIMING_RING); s->r1.resize(LIA_CACHE_TIMING_RING);
+  s->ring_pending.assign(LIA_CACHE_TIMING_RING, 0); s->ring_bytes.assign(LIA_CACHE_TIMING_RING, 0);
+  for (int i = 0; i < LIA_CACHE_TIMING_RING; ++i) {
+    HIP_TRY(hipEventCreate(&s->r0[i]));
+    HIP_TRY(hipEventCreate(&s->r1[i]));
+  }
+  s->entry_filled.assign(LIA_CACHE_MAX_ENTRIES, 0); s->entry_src.assign(LIA_CACHE_MAX_ENTRIES, nullptr); s->entry_bytes.assign(LIA_CACHE_MAX_ENTRIES, 0);
   return LIA_OK;
 }
 
@@ -209,14 +265,34 @@ extern "C" void* lia_stream_staging_ptr(lia_streamer* s, int slot) {
 
 extern "C" int lia_stream_copy_chunk_packed(lia_streamer* s, int slot, size_t offset, const void* host_ptr, size_t bytes, int pinned) {
   if (!s || slot < 0 || slot >= s->n_slots || !host_ptr) return LIA_ERR_INVALID;
+  if (s->keep_slots) { lia_set_error("lia_stream_copy_chunk_packed: the staging areas are landing buffers in decode mode (lia_stream_land)"); return LIA_ERR_INVALID; }
   int rc = ensure_staging(s);
   if (rc) return rc;
   if (offset + bytes > s->staging_bytes) { lia_set_error("lia_stream_copy_chunk_packed: %zu + %zu > staging %zu", offset, bytes, s->staging_bytes); return LIA_ERR_INVALID; }
   return copy_chunk_to(s, s->staging, s->staging_bytes, slot, offset, host_ptr, bytes, pinned);
 }
 
+// The decode kernel of one layer on the decode stream, src -> slot, inside the slot's timing bracket.  The bracket re-uses the
+// slot's event pair: collect the previous launch first -- WITHOUT waiting (this runs inside the token loop).  The slot's previous
+// decode finished long ago (its consumer released the slot); should it not have -- a dropped prefetch whose decode is still in
+// flight -- this launch simply goes untimed.
+static int launch_decode(lia_streamer* s, const char* src, int slot, size_t n_values, int format, double bytes_in) {
+  streamer_collect_decode(s, slot, false);
+  (void)hipGetLastError();                                             // hipErrorNotReady from the query is an answer, not an error
+  const bool timed = !s->decode_pending[slot];
+  wire_decode_launch(format, src, (bf16_t*)(s->slots + (size_t)slot * s->slot_bytes), n_values, s->decode, timed ? s->d0[slot] : nullptr,
+                     timed ? s->d1[slot] : nullptr);
+  HIP_TRY(hipGetLastError());
+  if (timed) {
+    s->decode_in[slot] = bytes_in;
+    s->decode_out[slot] = 2.0 * (double)n_values;
+    s->decode_pending[slot] = 1;
+  }
+  return LIA_OK;
+}
+
 extern "C" int lia_stream_decode_packed(lia_streamer* s, int slot, size_t n_values, int format) {
-  if (!s || slot < 0 || slot >= s->n_slots || !s->staging || n_values * 2 > s->slot_bytes || !wire_format_known(format) || (n_values % 1024)) {
+  if (!s || slot < 0 || slot >= s->n_slots || !s->staging || s->keep_slots || n_values * 2 > s->slot_bytes || !wire_format_known(format) || (n_values % 1024)) {
     lia_set_error("lia_stream_decode_packed: slot=%d n_values=%zu format=%d", slot, n_values, format);
     return LIA_ERR_INVALID;
   }
@@ -226,20 +302,7 @@ extern "C" int lia_stream_decode_packed(lia_streamer* s, int slot, size_t n_valu
   HIP_TRY(hipEventRecord(s->t1[slot], s->copy));                       // copy-engine busy time ends here
   HIP_TRY(hipEventRecord(s->landed[slot], s->copy));
   HIP_TRY(hipStreamWaitEvent(s->decode, s->landed[slot], 0));
-  // the timing bracket re-uses the slot's event pair: collect the previous launch first -- WITHOUT waiting (this runs inside the
-  // token loop).  The slot's previous decode finished long ago (its consumer released the slot); should it not have -- a dropped
-  // prefetch whose decode is still in flight -- this launch simply goes untimed.
-  streamer_collect_decode(s, slot, false);
-  (void)hipGetLastError();                                             // hipErrorNotReady from the query is an answer, not an error
-  const bool timed = !s->decode_pending[slot];
-  wire_decode_launch(format, s->staging + (size_t)slot * s->staging_bytes, (bf16_t*)(s->slots + (size_t)slot * s->slot_bytes), n_values, s->decode,
-                     timed ? s->d0[slot] : nullptr, timed ? s->d1[slot] : nullptr);
-  HIP_TRY(hipGetLastError());
-  if (timed) {
-    s->decode_in[slot] = (double)s->pending_bytes[slot];
-    s->decode_out[slot] = 2.0 * (double)n_values;
-    s->decode_pending[slot] = 1;
-  }
+  if (int rc = launch_decode(s, s->staging + (size_t)slot * s->staging_bytes, slot, n_values, format, (double)s->pending_bytes[slot])) return rc;
   s->decoded_on_side[slot] = 1;
   return LIA_OK;
 }
@@ -305,9 +368,156 @@ extern "C" int lia_stream_release(lia_streamer* s, int slot, void* compute_strea
   return LIA_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// decode mode: wire-format layers cached in the slots a decode step has no use for
+// ------------------------------------------------------------------------------------------------
+// A decode step is link-bound: its consumer holds a slot for 2-3 ms per layer, the link needs 14.5 ms per layer, so two slots and
+// two landing buffers keep the link busy and the rest of the streamer's memory idles.  In decode mode that rest holds layers in
+// their WIRE format; the decode kernel rebuilds such a layer in a slot every step and the layer never crosses the link again.
+//   landing buffer b (< keep_slots): the staging area of slot b, cut loose from the slot.  lia_stream_land copies into it behind
+//       drained[b], the decode that last read it; lia_stream_decode_landed decodes it into ANY kept slot behind landed[b] and the
+//       slot's release, and records drained[b].
+//   entry e: lia_stream_decode_cached fills it on first use (one H2D copy, counted like any copy) and decodes it into a kept slot.
+// All copies stay on the copy stream and all decodes on the decode stream; nothing here waits on the host.
+static size_t cache_staging_offset(const lia_streamer* s, int keep_slots) { return align_up((size_t)keep_slots * s->staging_bytes, 256); }
+static size_t cache_stride(size_t entry_bytes) { return align_up(entry_bytes + LIA_CACHE_READ_SLACK, 256); }
+static void cache_counts(const lia_streamer* s, int keep_slots, size_t entry_bytes, int* in_slots, int* in_staging) {
+  *in_slots = *in_staging = 0;
+  if (!s->staging || keep_slots < 1 || keep_slots >= s->n_slots || entry_bytes == 0) return;
+  const size_t stride = cache_stride(entry_bytes);
+  const size_t a = (size_t)(s->n_slots - keep_slots) * s->slot_bytes;
+  const size_t off = cache_staging_offset(s, keep_slots), total = (size_t)s->n_slots * s->staging_bytes;
+  const size_t b = total > off ? total - off : 0;
+  *in_slots = (int)std::min<size_t>(a / stride, LIA_CACHE_MAX_ENTRIES);
+  *in_staging = (int)std::min<size_t>(b / stride, (size_t)(LIA_CACHE_MAX_ENTRIES - *in_slots));
+}
+static char* cache_entry_ptr(lia_streamer* s, int e) {
+  if (e < s->entries_in_slots) return s->slots + (size_t)s->keep_slots * s->slot_bytes + (size_t)e * s->entry_stride;
+  return s->staging + cache_staging_offset(s, s->keep_slots) + (size_t)(e - s->entries_in_slots) * s->entry_stride;
+}
+
+extern "C" int lia_stream_cache_capacity(lia_streamer* s, int keep_slots, size_t entry_bytes) {
+  if (!s) return 0;
+  int a, b;
+  cache_counts(s, keep_slots, entry_bytes, &a, &b);
+  return a + b;
+}
+
+extern "C" int lia_stream_cache_enable(lia_streamer* s, int keep_slots, size_t entry_bytes) {
+  if (!s) return LIA_ERR_INVALID;
+  int a = 0, b = 0;
+  cache_counts(s, keep_slots, entry_bytes, &a, &b);
+  if (s->keep_slots || a + b == 0) {
+    lia_set_error("lia_stream_cache_enable: keep_slots=%d entry_bytes=%zu on %d slots (%s)", keep_slots, entry_bytes, s->n_slots,
+                  s->keep_slots ? "the mode is on" : "no room for an entry");
+    return LIA_ERR_INVALID;
+  }
+  // the pool's first writer is the copy stream: behind the last consumers of the slots that leave the ring and behind their
+  // prefetches' decodes (dropped ones included), which read the staging areas that leave with them
+  for (int i = 0; i < s->n_slots; ++i) {
+    if (i >= keep_slots && s->has_release[i]) HIP_TRY(hipStreamWaitEvent(s->copy, s->released[i], 0));
+    // (a kept slot: its staging area becomes a landing buffer, still read by the decode of the slot's last legacy prefetch)
+    if (s->was_marked[i]) HIP_TRY(hipStreamWaitEvent(s->copy, s->copied[i], 0));
+    s->has_drained[i] = 0; s->landing_bytes[i] = 0;
+  }
+  s->keep_slots = keep_slots; s->entries_in_slots = a; s->n_entries = a + b; s->entry_stride = cache_stride(entry_bytes);
+  std::fill(s->entry_filled.begin(), s->entry_filled.end(), 0);
+  return LIA_OK;
+}
+
+extern "C" int lia_stream_cache_disable(lia_streamer* s) {
+  if (!s) return LIA_ERR_INVALID;
+  if (!s->keep_slots) return LIA_OK;
+  // Slots and staging areas return to the ring.  Their next writers are copies on the copy stream and decodes on the decode
+  // stream: the latter run behind every decode of the mode by stream order, the former behind this event.
+  HIP_TRY(hipEventRecord(s->cache_idle, s->decode));
+  HIP_TRY(hipStreamWaitEvent(s->copy, s->cache_idle, 0));
+  s->keep_slots = s->n_entries = s->entries_in_slots = 0; s->entry_stride = 0;
+  std::fill(s->entry_filled.begin(), s->entry_filled.end(), 0);
+  return LIA_OK;
+}
+
+// one timed copy of the mode on the copy stream (the caller has enqueued what it must wait for)
+static int cache_copy(lia_streamer* s, char* dst, const void* host_ptr, size_t bytes, int pinned) {
+  const int r = s->ring_next;
+  s->ring_next = (r + 1) % LIA_CACHE_TIMING_RING;
+  streamer_collect_ring(s, r, true);       // sixteen copies back: finished long ago
+  HIP_TRY(hipEventRecord(s->r0[r], s->copy));
+  if (pinned) HIP_TRY(hipMemcpyAsync(dst, host_ptr, bytes, hipMemcpyHostToDevice, s->copy));
+  else if (int rc = staged_copy(s, dst, host_ptr, bytes)) return rc;
+  HIP_TRY(hipEventRecord(s->r1[r], s->copy));
+  s->ring_bytes[r] = bytes; s->ring_pending[r] = 1;
+  return LIA_OK;
+}
+
+extern "C" int lia_stream_land(lia_streamer* s, int landing, const void* host_ptr, size_t packed_bytes, int pinned) {
+  if (!s || !s->keep_slots || landing < 0 || landing >= s->keep_slots || !host_ptr || packed_bytes == 0 || packed_bytes > s->staging_bytes) {
+    lia_set_error("lia_stream_land: landing=%d bytes=%zu (decode mode %s, %d landing buffers of %zu)", landing, packed_bytes,
+                  s && s->keep_slots ? "on" : "off", s ? s->keep_slots : 0, s ? s->staging_bytes : 0);
+    return LIA_ERR_INVALID;
+  }
+  if (s->has_drained[landing]) HIP_TRY(hipStreamWaitEvent(s->copy, s->drained[landing], 0));
+  if (int rc = cache_copy(s, s->staging + (size_t)landing * s->staging_bytes, host_ptr, packed_bytes, pinned)) return rc;
+  HIP_TRY(hipEventRecord(s->landed[landing], s->copy));
+  s->landing_bytes[landing] = packed_bytes;
+  return LIA_OK;
+}
+
+// the decode stream takes over slot `slot`: behind its last consumer and behind whatever an abandoned prefetch still writes there
+static int cache_claim_slot(lia_streamer* s, int slot) {
+  if (s->has_release[slot]) HIP_TRY(hipStreamWaitEvent(s->decode, s->released[slot], 0));
+  if (s->was_marked[slot]) HIP_TRY(hipStreamWaitEvent(s->decode, s->copied[slot], 0));
+  return LIA_OK;
+}
+static int cache_slot_ready(lia_streamer* s, int slot) {
+  HIP_TRY(hipEventRecord(s->copied[slot], s->decode));                  // ready = decoded, as in lia_stream_mark_ready
+  s->was_marked[slot] = 1;
+  return LIA_OK;
+}
+
+extern "C" int lia_stream_decode_landed(lia_streamer* s, int landing, int slot, size_t n_values, int format) {
+  if (!s || !s->keep_slots || landing < 0 || landing >= s->keep_slots || slot < 0 || slot >= s->keep_slots || !s->landing_bytes[landing] ||
+      n_values * 2 > s->slot_bytes || !wire_format_known(format) || (n_values % 1024)) {
+    lia_set_error("lia_stream_decode_landed: landing=%d slot=%d n_values=%zu format=%d", landing, slot, n_values, format);
+    return LIA_ERR_INVALID;
+  }
+  HIP_TRY(hipStreamWaitEvent(s->decode, s->landed[landing], 0));
+  if (int rc = cache_claim_slot(s, slot)) return rc;
+  if (int rc = launch_decode(s, s->staging + (size_t)landing * s->staging_bytes, slot, n_values, format, (double)s->landing_bytes[landing])) return rc;
+  HIP_TRY(hipEventRecord(s->drained[landing], s->decode));
+  s->has_drained[landing] = 1; s->landing_bytes[landing] = 0;
+  return cache_slot_ready(s, slot);
+}
+
+extern "C" int lia_stream_decode_cached(lia_streamer* s, int entry, int slot, const void* host_ptr, size_t packed_bytes, size_t n_values,
+                                        int format, int pinned) {
+  if (!s || !s->keep_slots || entry < 0 || entry >= s->n_entries || slot < 0 || slot >= s->keep_slots || !host_ptr || packed_bytes == 0 ||
+      packed_bytes + LIA_CACHE_READ_SLACK > s->entry_stride || n_values * 2 > s->slot_bytes || !wire_format_known(format) || (n_values % 1024)) {
+    lia_set_error("lia_stream_decode_cached: entry=%d slot=%d bytes=%zu n_values=%zu format=%d (%d entries, stride %zu)", entry, slot,
+                  packed_bytes, n_values, format, s ? s->n_entries : 0, s ? s->entry_stride : 0);
+    return LIA_ERR_INVALID;
+  }
+  char* const at = cache_entry_ptr(s, entry);
+  if (!s->entry_filled[entry]) {
+    // the one crossing of this layer.  (The event of a slot outside the ring serves: its wait is enqueued right here.)
+    if (int rc = cache_copy(s, at, host_ptr, packed_bytes, pinned)) return rc;
+    HIP_TRY(hipEventRecord(s->landed[s->keep_slots], s->copy));
+    HIP_TRY(hipStreamWaitEvent(s->decode, s->landed[s->keep_slots], 0));
+    s->entry_filled[entry] = 1; s->entry_src[entry] = host_ptr; s->entry_bytes[entry] = packed_bytes;
+  } else if (s->entry_src[entry] != host_ptr || s->entry_bytes[entry] != packed_bytes) {
+    // an entry is never refilled while decodes may still read it: the caller turns the mode off and on again
+    lia_set_error("lia_stream_decode_cached: entry %d holds another layer", entry);
+    return LIA_ERR_INVALID;
+  }
+  if (int rc = cache_claim_slot(s, slot)) return rc;
+  if (int rc = launch_decode(s, at, slot, n_values, format, (double)packed_bytes)) return rc;
+  return cache_slot_ready(s, slot);
+}
+
 extern "C" int lia_stream_stats(lia_streamer* s, double* bytes, double* busy_ms, int reset) {
   if (!s) return LIA_ERR_INVALID;
   for (int i = 0; i < s->n_slots; ++i) streamer_collect(s, i);
+  for (size_t r = 0; r < s->ring_pending.size(); ++r) streamer_collect_ring(s, (int)r, true);
   if (bytes) *bytes = s->bytes;
   if (busy_ms) *busy_ms = s->busy_ms;
   if (reset) { s->bytes = 0; s->busy_ms = 0; }
@@ -341,6 +551,7 @@ extern "C" int lia_stream_poll_stats(lia_streamer* s, double* bytes, double* bus
   if (!s) return LIA_ERR_INVALID;
   for (int i = 0; i < s->n_slots; ++i)
     if (s->timing_pending[i] && hipEventQuery(s->t1[i]) == hipSuccess) streamer_collect(s, i);
+  for (size_t r = 0; r < s->ring_pending.size(); ++r) streamer_collect_ring(s, (int)r, false);
   (void)hipGetLastError();   // hipErrorNotReady from the query is an answer, not an error
   if (bytes) *bytes = s->bytes;
   if (busy_ms) *busy_ms = s->busy_ms;

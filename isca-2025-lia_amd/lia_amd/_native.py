@@ -158,6 +158,12 @@ SIGNATURES = {
     "lia_pack10a_validate": (c_int, [c_void_p, c_size_t, c_size_t]),
     "lia_pack_codec": (c_int, [c_void_p, c_size_t]),
     "lia_stream_copy_stream": (c_void_p, [c_void_p]),
+    "lia_stream_cache_capacity": (c_int, [c_void_p, c_int, c_size_t]),
+    "lia_stream_cache_enable": (c_int, [c_void_p, c_int, c_size_t]),
+    "lia_stream_cache_disable": (c_int, [c_void_p]),
+    "lia_stream_land": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int]),
+    "lia_stream_decode_landed": (c_int, [c_void_p, c_int, c_int, c_size_t, c_int]),
+    "lia_stream_decode_cached": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_size_t, c_int, c_int]),
     "numa_alloc_node": (c_void_p, [c_size_t, c_int]),
     "numa_alloc_interleave": (c_void_p, [c_size_t]),
     "numa_free_node": (None, [c_void_p, c_size_t]),

@@ -27,6 +27,10 @@ class Box:
     host_linear_gbs_per_thread: float = 7.0   # policy-1 linears at M = 64 beside the running weight stream (7.3 alone; r02's kernel: 4.4 / 4.9; 3.6 unpinned)
     host_attn_beside_stream: float = 0.8      # share of its rate the host attention keeps beside the stream (0.55 unpinned)
     wire_ratio: float = 0.675         # bytes shipped per weight byte: pack10 0.675, raw 1.0
+    # decode steps find the first streamed layers in HBM in their wire format (the scheduler's wire cache; wire_cache_layers below).
+    # Off in a bare Box, whose rates and predictions are the calibration measurements' (every layer crossing the link every step);
+    # planner.wire_cache_default() is what a run of the OPT scheduler will do -- run.py's --auto-plan and --plan set it
+    wire_cache: bool = False
     host_threads: int = 0
     host_mem_gb: float = 0.0
     calibrated: dict = None           # set by calibrate(): the measured numbers, for the log
@@ -169,6 +173,23 @@ def decode_gemm_ms(shape, B, box):
     return max(bw_ms, 1e3 * 2.0 * B * (lb / 2) / (0.65 * box.mfma_tflops * 1e12))
 
 
+def wire_cache_default():
+    """whether an OffloadScheduler of this process caches wire-format layers during decode (LIA_WIRE_CACHE, default on)"""
+    import os
+    return os.environ.get("LIA_WIRE_CACHE", "1") != "0"
+
+
+def wire_cache_layers(shape, box, n_str, n_slots=4, keep_slots=2):
+    """Streamed layers a decode step finds in HBM in their wire format (streaming.WeightPipeline's decode mode): what fits the
+    n_slots - keep_slots streamer slots such a step has no use for and their staging areas (lia_pack10_bound: 1.13 x the raw
+    layer each).  They cost the step their compute, not their copy."""
+    if not box.wire_cache or box.wire_ratio >= 1.0 or n_str <= 0 or n_slots <= keep_slots:
+        return 0
+    lb = layer_bytes(shape)
+    entry = lb * box.wire_ratio
+    return min(n_str, int((n_slots - keep_slots) * lb // entry) + int((n_slots - keep_slots) * 1.13 * lb // entry))
+
+
 def estimate(shape, B, T, new, gpu_percentage, decoding_policy, box=None, kv_in_hbm=None):
     """Predicted prefill ms / decode ms per step of one configuration (prefill policy 0 on streamed layers)."""
     box = box or Box()
@@ -185,12 +206,14 @@ def estimate(shape, B, T, new, gpu_percentage, decoding_policy, box=None, kv_in_
     attn_gpu_ms = 1e3 * (2 * (T + new // 2) * B * H * 2) / (box.attn_gbs * 1e9)
     attn_host_ms = 1e3 * (2 * (T + new // 2) * B * H * 2) / (min(box.host_threads * box.host_gbs_per_thread, box.host_gbs_cap) * 1e9)
     resident_ms = gemm_ms + attn_gpu_ms
-    if decoding_policy == 2:
-        streamed_ms = max(copy_ms, gemm_ms + attn_host_ms + 0.3)
-    else:
-        streamed_ms = max(copy_ms, gemm_ms + attn_gpu_ms)
+    compute_ms = gemm_ms + attn_host_ms + 0.3 if decoding_policy == 2 else gemm_ms + attn_gpu_ms
+    streamed_ms = max(copy_ms, compute_ms)
     lm_ms = 1e3 * shape.vocab * H * 2 / (box.hbm_gbs * 1e9)
-    decode_ms = n_gpu * resident_ms + n_str * streamed_ms + lm_ms + 0.5
+    # a cached layer: its compute, and its wire-format decode kernel's HBM traffic beside the layer in front of it (encoded bytes
+    # read, bf16 written: 0.54 ms measured for an OPT-30B layer) -- never cheaper than a resident layer
+    n_cached = wire_cache_layers(shape, box, n_str)
+    cached_ms = compute_ms + 1e3 * lb * (1.0 + box.wire_ratio) / (box.hbm_gbs * 1e9)
+    decode_ms = n_gpu * resident_ms + n_cached * cached_ms + (n_str - n_cached) * streamed_ms + lm_ms + 0.5
     # prefill
     flops_layer = 2.0 * B * T * (4 * H * H + 2 * H * F) + 6.0 * B * T * T * H
     pre_layer_ms = 1e3 * flops_layer / (box.mfma_tflops * 1e12)

@@ -129,9 +129,12 @@ def check_verify_rows(block_ids, kv_state, row_lens, flags, n_gpu, L):
 class OffloadScheduler:
     """forward(input_ids, kv_state, **lia flags) -> (logits [B,vocab], next_ids [B]) on the device."""
 
-    def __init__(self, model, device=0, n_slots=None, dp_group=None, wire=None):
+    def __init__(self, model, device=0, n_slots=None, dp_group=None, wire=None, wire_cache=None):
         self.model, self.device, self.dp = model, device, dp_group
         self.n_slots = n_slots or 4
+        # decode steps and small blocks keep the first streamed layers in HBM in their wire format, in the streamer slots such
+        # forwards have no use for (WeightPipeline.set_decode_mode); LIA_WIRE_CACHE=0: every layer crosses the link every step
+        self.wire_cache = (os.environ.get("LIA_WIRE_CACHE", "1") != "0") if wire_cache is None else bool(wire_cache)
         # wire format of the streamed layers: "pack10" (the lossless encoding of lia_pack10.hip) or "raw" bf16
         fmt = default_stream_format() if wire is None else wire
         self.wire = wire_format_code(fmt)
@@ -537,6 +540,8 @@ class OffloadScheduler:
         m, sh, ctx, pipe = self.model, self.model.shape, self.ctx, self.pipe
         B, T, L, n_gpu, is_prefill, policy, mini, overlap, pos0, hold = s.B, s.T, s.L, s.n_gpu, s.is_prefill, s.policy, s.mini, s.overlap, s.pos0, s.hold
         host_act, host_now, x, y = s.host_act, s.host_now, s.x, s.y
+        if n_gpu < L:
+            self._set_wire_cache(s)
         if n_gpu < L and overlap:
             pipe.prefetch(n_gpu)                                   # no-op if the previous step already wrapped to it
         # the prefill's last layer: only hidden[:, -1, :] feeds lm_head (models.py:424-431), its K/V of every position feed decode
@@ -599,6 +604,30 @@ class OffloadScheduler:
             if not overlap:
                 ctx.synchronize()
         return x if xlast is None else xlast
+
+    SKINNY_ROWS = 256       # B x T up to which a forward's GEMMs run in the skinny, weight-bandwidth-bound regime (lia_gemm.hip)
+
+    def _set_wire_cache(self, s):
+        """Decode mode of the streamer, decided per forward: on for decode steps and for blocks in the skinny GEMM regime (verify
+        passes, short appends), which are link-bound like a decode step; off before a prefill, a scoring pass or any block in the
+        tiled regime, which get every slot back.  Not with data parallelism, and not under the cooperative split (cpu_layers != 0),
+        whose host set moves between steps."""
+        pipe = self.pipe
+        if not self.wire_cache or self.dp is not None or s.coop is not None or s.cpu_set:
+            if pipe.keep:
+                pipe.set_decode_mode(None)
+            return
+        # a decode step, or a block behind a non-empty cache that is kept: an append or a verify pass, not a scoring pass
+        step = not s.is_prefill or (s.pos0 > 0 and (s.verify or not s.every_pos))
+        if step and s.B * s.T <= self.SKINNY_ROWS:
+            pipe.set_decode_mode(range(s.n_gpu, s.L))
+        else:
+            pipe.set_decode_mode(None)
+
+    def wire_cache_info(self):
+        """{"enabled", "on", "capacity" (layers), "layers" (bound to an entry, in order), "bytes" (wire bytes held in HBM)}"""
+        info = self.pipe.cache_info() if self.pipe else {"on": False, "capacity": 0, "layers": [], "bytes": 0}
+        return dict(info, enabled=self.wire_cache)
 
     def _deliver(self, s, kv_state):
         """behind lm_head: the deferred K/V deliveries of a policy-0 prefill (tickets, awaited per layer by the first decode

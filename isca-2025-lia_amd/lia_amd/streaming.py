@@ -13,7 +13,14 @@ from .model import LayerStore
 
 
 class WeightPipeline:
-    """Slot bookkeeping over lia_stream_*: prefetch(layer) -> acquire(layer) -> release(layer)."""
+    """Slot bookkeeping over lia_stream_*: prefetch(layer) -> acquire(layer) -> release(layer).
+
+    Decode mode (set_decode_mode, lia_stream_cache_*): KEEP_SLOTS slots stay in the ring, the memory of the others holds the first
+    streamed layers of a step in their wire format, and a packed layer that is not cached passes two stages with a resource each:
+    `landed` (its copy is queued into a landing buffer) and `inflight` (its decode is queued into a slot).  The link runs ahead by
+    landing buffers while the slots cycle through the cached layers."""
+
+    KEEP_SLOTS = 2
 
     def __init__(self, ctx, model, n_slots, dp_group=None):
         self.ctx, self.model, self.lib = ctx, model, N.lib()
@@ -24,6 +31,12 @@ class WeightPipeline:
         self.free_slots = list(range(n_slots))
         self.inflight = []          # [(layer_idx, slot)] in issue order, not yet acquired
         self.held = {}              # layer_idx -> slot (acquired, not yet released)
+        self.keep = 0               # decode mode: the slots left in the ring (0 = the mode is off)
+        self.cache = {}             # layer_idx -> cache entry, bound while the mode is on
+        self.cache_filled = set()   # bound layers whose entry holds their bytes
+        self.free_landing = []
+        self.landed = []            # [(layer_idx, landing buffer)] in issue order: copy queued, decode not yet
+        self._plan = None           # (order, bound layers, entry size) of the last cache_plan that found room
         self.slot_ptrs = [self.lib.lia_stream_slot_ptr(h, s) for s in range(n_slots)]
         self.ptr_arrays = [ops.weight_ptr_array(p, model.offsets) for p in self.slot_ptrs]
         if dp_group is not None:
@@ -55,10 +68,121 @@ class WeightPipeline:
     def can_prefetch(self):
         return bool(self.free_slots)
 
+    # -- decode mode ---------------------------------------------------------------------------------
+    def _cacheable(self, layer_idx):
+        st = self.model.layers[layer_idx]
+        return bool(st.packed) and st.tier not in ("device", None)
+
+    def cache_plan(self, order):
+        """the layers of `order` (streamed layers in the order a step computes them) that get a cache entry, and the entry size:
+        the first C packed ones, C the most for which the library has room when an entry is sized for the largest of them"""
+        if self.dp is not None or self.n_slots <= self.KEEP_SLOTS:
+            return [], 0
+        key = tuple(order)
+        if self._plan is not None and self._plan[0] == key:      # (dropped with the cache: drain, before the layers re-tier)
+            return self._plan[1:]
+        cand = [i for i in order if self._cacheable(i)]
+        for c in range(min(len(cand), 64), 0, -1):
+            size = max(int(self.model.layers[i].stream_bytes) for i in cand[:c])
+            if self.lib.lia_stream_cache_capacity(self.handle, self.KEEP_SLOTS, size) >= c:
+                self._plan = (key, cand[:c], size)
+                return cand[:c], size
+        return [], 0
+
+    def set_decode_mode(self, order):
+        """order: the streamed layers a decode step computes on the GPU, in order -> turn the mode on with the first of them bound
+        to cache entries (no-op if it is on with these layers); None or nothing to cache: turn it off.  The caller switches between
+        forwards, when no layer is held.  Returns whether the mode is on."""
+        if order is None:
+            self._plan = None
+        bound, size = self.cache_plan(order) if order is not None else ([], 0)
+        if self.keep and bound == sorted(self.cache, key=self.cache.get):
+            return True
+        if self.keep:
+            N.check(self.lib.lia_stream_cache_disable(self.handle), "lia_stream_cache_disable")
+            # decodes already queued into a kept slot stay good; a landed copy has no slot to be decoded into any more
+            self.keep, self.cache, self.cache_filled, self.landed, self.free_landing = 0, {}, set(), [], []
+            busy = {slot for _, slot in self.inflight} | set(self.held.values())
+            self.free_slots = [s_ for s_ in self.free_slots if s_ not in busy] + \
+                              [s_ for s_ in range(self.n_slots) if s_ not in busy and s_ not in self.free_slots]
+        if not bound:
+            return False
+        if any(slot >= self.KEEP_SLOTS for slot in self.held.values()):
+            raise RuntimeError("decode mode: a held layer sits in a slot that leaves the ring")
+        # Prefetches queued into the slots that leave the ring are abandoned (lia_stream_cache_enable lets them finish first), and
+        # so are those of the layers that get an entry: a slot holds the decoded layer, the entry wants its wire bytes, and every
+        # entry is to be filled by the first step.  (Up to n_slots - 1 layers the prefill's tail had copied cross the link again:
+        # once per generation.)
+        self.inflight = [(li, slot) for li, slot in self.inflight if slot < self.KEEP_SLOTS and li not in bound]
+        N.check(self.lib.lia_stream_cache_enable(self.handle, self.KEEP_SLOTS, size), "lia_stream_cache_enable")
+        self.keep = self.KEEP_SLOTS
+        busy = {slot for _, slot in self.inflight} | set(self.held.values())
+        self.free_slots = [s_ for s_ in self.free_slots if s_ < self.keep and s_ not in busy]
+        self.free_slots += [s_ for s_ in range(self.keep) if s_ not in busy and s_ not in self.free_slots]
+        self.free_landing = list(range(self.keep))
+        self.cache = {li: e for e, li in enumerate(bound)}
+        return True
+
+    def cache_info(self):
+        return {"on": bool(self.keep), "capacity": len(self.cache), "layers": sorted(self.cache, key=self.cache.get),
+                "bytes": sum(int(self.model.layers[i].stream_bytes) for i in self.cache_filled)}
+
+    def _land(self, layer_idx):
+        st = self.model.layers[layer_idx]
+        b = self.free_landing.pop(0)
+        N.check(self.lib.lia_stream_land(self.handle, b, ctypes.c_void_p(st.host_ptr()), st.stream_bytes, int(st.is_dma_able())), "lia_stream_land")
+        self.landed.append((layer_idx, b))
+
+    def _issue(self, layer_idx):
+        """decode mode: queue whatever brings the layer into a free slot"""
+        st = self.model.layers[layer_idx]
+        slot = self.free_slots.pop(0)
+        fmt = int(getattr(st, "codec", 0) or st.packed)
+        if layer_idx in self.cache:
+            N.check(self.lib.lia_stream_decode_cached(self.handle, self.cache[layer_idx], slot, ctypes.c_void_p(st.host_ptr()), st.stream_bytes,
+                                                      st.nbytes // 2, fmt, int(st.is_dma_able())), "lia_stream_decode_cached")
+            self.cache_filled.add(layer_idx)
+        elif st.packed:
+            pos = next((j for j, (li, _) in enumerate(self.landed) if li == layer_idx), None)
+            if pos is None:
+                if not self.free_landing:                      # (out of order: give up the copy queued last)
+                    self.free_landing.append(self.landed.pop()[1])
+                self._land(layer_idx)
+                pos = len(self.landed) - 1
+            _, b = self.landed.pop(pos)
+            N.check(self.lib.lia_stream_decode_landed(self.handle, b, slot, st.nbytes // 2, fmt), "lia_stream_decode_landed")
+            self.free_landing.append(b)                        # (the next copy into it is ordered behind this decode by the library)
+        else:
+            N.check(self.lib.lia_stream_prefetch(self.handle, slot, ctypes.c_void_p(st.host_ptr()), st.nbytes, int(st.is_dma_able())),
+                    "lia_stream_prefetch")
+        self.inflight.append((layer_idx, slot))
+
+    def _pump(self, idx, next_layer):
+        """decode mode's prefetch_ahead: slots go to the layers behind idx strictly in the order they are needed; behind the first
+        layer that finds none, packed layers without a cache entry still start their copies while a landing buffer is free."""
+        in_order = True
+        for _, nxt in zip(range(len(self.cache) + 2 * self.keep + 2), next_layer):
+            if nxt == idx or not (self.free_slots or self.free_landing):
+                break
+            if nxt in self.held or any(li == nxt for li, _ in self.inflight):
+                continue
+            if in_order and self.free_slots:
+                self._issue(nxt)
+                continue
+            in_order = False
+            if nxt in self.cache or not self.model.layers[nxt].packed or any(li == nxt for li, _ in self.landed):
+                continue                                       # needs nothing but a slot
+            if not self.free_landing:
+                break
+            self._land(nxt)
+
     def prefetch(self, layer_idx):
         if any(li == layer_idx for li, _ in self.inflight) or layer_idx in self.held:
             return
         if not self.can_prefetch():
+            return
+        if self.keep:
+            self._issue(layer_idx)
             return
         st = self.model.layers[layer_idx]
         slot = self.free_slots.pop(0)
@@ -171,6 +295,9 @@ class WeightPipeline:
         stream_order below), n_slots - 1 of them at most, until a slot is missing or the order comes back to idx.  The weight
         copies of the next streamed layer(s) overlap this layer's compute (:1305-1312, :1508-1515); behind the last layer the
         order wraps to the first streamed layer of the NEXT forward, so the copy engine keeps running across token steps."""
+        if self.keep:
+            self._pump(idx, next_layer)
+            return
         for _, nxt in zip(range(self.n_slots - 1), next_layer):
             if nxt == idx or not self.can_prefetch():
                 break
@@ -178,7 +305,15 @@ class WeightPipeline:
 
     def forget(self, layer_idx):
         """Give up a queued copy of layer_idx (it will not be used: the layer's decode step moved to the host cores).  The slot is
-        free again at once; lia_stream_begin orders its next copy behind the abandoned one."""
+        free again at once; lia_stream_begin orders its next copy behind the abandoned one.  A layer that is bound to a cache entry
+        takes the whole cache with it: the next forward binds the layers that are then streamed."""
+        if layer_idx in self.cache:
+            self.set_decode_mode(None)
+        for j, (li, b) in enumerate(self.landed):
+            if li == layer_idx:
+                self.landed.pop(j)
+                self.free_landing.append(b)
+                return True
         for j, (li, slot) in enumerate(self.inflight):
             if li == layer_idx:
                 self.inflight.pop(j)
@@ -201,7 +336,9 @@ class WeightPipeline:
         return b.value, ms.value
 
     def drain(self):
-        """Forget every queued copy and wait for the copy engine: called before the model re-tiers its layers."""
+        """Forget every queued copy and every cached layer and wait for the copy engine: called before the model re-tiers its
+        layers (the host copies the cache entries were filled from are about to be freed)."""
+        self.set_decode_mode(None)
         for _, slot in self.inflight:
             self.free_slots.append(slot)
         self.inflight = []
@@ -216,6 +353,7 @@ class WeightPipeline:
         if self.handle:
             self.lib.lia_stream_destroy(self.handle)
             self.handle = None
+        self.keep, self.cache, self.cache_filled, self.landed, self.free_landing = 0, {}, set(), [], []
 
 
 def stream_order(idx, first, L, skip=frozenset(), skip_now=True):
