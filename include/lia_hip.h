@@ -287,6 +287,41 @@ int lia_lm_verify_rows(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, in
                        const lia_bf16* emb, int vocab, float eps, int suppress_token, const int32_t* n_suppress_rows,
                        const int64_t* block_ids, const int32_t* active, int64_t* greedy, int32_t* accepted, int32_t* common,
                        int64_t* next, void* stream);
+/* ---- sampled verification ("Sampled verification"): lia_lm_verify with lia_sample's draw in place of the argmax.
+ * Plain sampled decoding emits  lia_sample(logits(prefix), U[step, row])  per step; a verify pass evaluates that same function behind
+ * every position of the block.  Per chunk (lia_lm_score's CHUNK RULE and workspace), for block row b at position t:
+ *   suppress_token counts as -inf where t < n_suppress_rows[b] (int32 [B], device) -- or, with a NULL n_suppress_rows, t < n_suppress
+ *   s = (step_rows ? step_rows[b] : step0) + t        u = s < n_steps ? uniforms[s * ldu + b] : 0   (nothing is read past the table:
+ *       such a position can never be kept)
+ *   sampled[b, t] = lia_sample's id for these logits, settings and u -- the same device function, the same bits; no argmax runs
+ *   p_draft[b, t] (fp32 [B, T], device, or NULL) = the probability that this draw confirms the draft token block_ids[b, t + 1]: its
+ *       kept weight exp(s - max s) over the kept mass; 0 where that token is not kept (or no token id), and 0 at t = T - 1
+ * then accepted / common / next exactly as lia_lm_verify computes them, on `sampled`.
+ * logits_out (bf16 [B * T, vocab], device, or NULL): each chunk's logits are copied out on `stream` before the next chunk overwrites
+ * them -- for tests and measurements; NULL in production.
+ * lia_block_sampler: the settings and the generation's table U (device fp32 [n_steps, ldu], U[step, row]); step_rows: int32 [B],
+ * device, or NULL (every row at step0).
+ * LIA_ERR_INVALID, by name: every lia_lm_verify refusal; lia_sample's for temperature, top_k, top_p and vocab > 2^21; ldu < B,
+ * n_steps < 1, step0 < 0, a NULL sampler, uniforms or sampled.  LIA_ERR_MEMORY as lia_lm_score. */
+typedef struct {
+  float temperature;
+  int top_k;
+  float top_p;
+  const float* uniforms;
+  long ldu;
+  int n_steps;
+  int step0;
+  const int32_t* step_rows;
+} lia_block_sampler;
+int lia_lm_verify_sample(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* lnw, const lia_bf16* lnb,
+                         const lia_bf16* emb, int vocab, float eps, int suppress_token, int n_suppress, const int32_t* n_suppress_rows,
+                         const lia_block_sampler* sampler, const int64_t* block_ids, const int32_t* active, int64_t* sampled,
+                         int32_t* accepted, int32_t* common, int64_t* next, float* p_draft, lia_bf16* logits_out, void* stream);
+int lia_llama_lm_verify_sample(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* normw,
+                               const lia_bf16* lm, int vocab, float eps, int suppress_token, int n_suppress,
+                               const int32_t* n_suppress_rows, const lia_block_sampler* sampler, const int64_t* block_ids,
+                               const int32_t* active, int64_t* sampled, int32_t* accepted, int32_t* common, int64_t* next,
+                               float* p_draft, lia_bf16* logits_out, void* stream);
 
 /* ---- Llama-family layer (BASELINE.json config 4; build-defined: the reference's LlamaDecoderLayer_forward,
  * decoder.py:121-169, has no policy plumbing -- SURVEY.md quirk 3).  Arithmetic = HF transformers' eager bf16 Llama.

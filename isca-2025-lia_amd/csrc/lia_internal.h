@@ -40,6 +40,10 @@ extern "C" void lia_blit_launch(void* dst, const void* src, size_t bytes, hipStr
 // lia_sample.hip, lia_score.hip
 extern "C" void lia_sample_launch(const bf16_t* logits, long ld, int B, int vocab, float tau, int top_k, float top_p, int suppress,
                                   const float* uniforms, int64_t* out, float* stats, hipStream_t st);
+extern "C" void lia_verify_sample_launch(const bf16_t* logits, long ld, int n, int vocab, float tau, int top_k, float top_p, int suppress,
+                                         int n_suppress, const int* n_suppress_rows, int T, int r0, const float* uniforms, long ldu,
+                                         int n_steps, int step0, const int* step_rows, const int64_t* block_ids, int64_t* sampled,
+                                         float* p_draft, hipStream_t st);
 extern "C" void lia_token_logprobs_launch(const bf16_t* logits, long ld, int M, int vocab, const int64_t* targets, float* logprobs,
                                           int64_t* greedy, hipStream_t st);
 extern "C" void lia_verify_argmax_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress, int T, int r0,

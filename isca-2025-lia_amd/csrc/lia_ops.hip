@@ -208,6 +208,14 @@ extern "C" int lia_llama_lm_head(lia_ctx* ctx, const lia_bf16* hidden, int B, in
 
 // temperature -> top-k -> top-p -> one draw per row (lia_sample.hip).  Any B; the row is read a fixed number of times.
 #define LIA_SAMPLE_MAX_VOCAB (256 * 8192)   // lia_sample.hip keeps one running sum per 8192-token tile in LDS
+// the settings' refusals, worded once for lia_sample and the sampled verify heads
+static bool sample_settings_invalid(const char* who, float temperature, int top_k, float top_p) {
+  if (!(temperature > 0.f) || !std::isfinite(temperature)) { lia_set_error("%s: temperature=%g must be finite and > 0", who, (double)temperature); return true; }
+  if (top_k < 0) { lia_set_error("%s: top_k=%d must be >= 0 (0: off)", who, top_k); return true; }
+  if (!(top_p > 0.f && top_p <= 1.f)) { lia_set_error("%s: top_p=%g must be in (0, 1] (1: off)", who, (double)top_p); return true; }
+  return false;
+}
+
 extern "C" int lia_sample(lia_ctx* ctx, const lia_bf16* logits, long ld, int B, int vocab, float temperature, int top_k, float top_p,
                           int suppress_token, const float* uniforms, int64_t* next_ids, float* stats, void* stream) {
   if (!ctx) return LIA_ERR_INVALID;
@@ -218,9 +226,7 @@ extern "C" int lia_sample(lia_ctx* ctx, const lia_bf16* logits, long ld, int B, 
   if (B <= 0) { lia_set_error("lia_sample: B=%d must be >= 1", B); return LIA_ERR_INVALID; }
   if (vocab <= 0 || vocab > LIA_SAMPLE_MAX_VOCAB) { lia_set_error("lia_sample: vocab=%d must be in [1, %d]", vocab, LIA_SAMPLE_MAX_VOCAB); return LIA_ERR_INVALID; }
   if (ld < vocab) { lia_set_error("lia_sample: ld=%ld < vocab=%d", ld, vocab); return LIA_ERR_INVALID; }
-  if (!(temperature > 0.f) || !std::isfinite(temperature)) { lia_set_error("lia_sample: temperature=%g must be finite and > 0", (double)temperature); return LIA_ERR_INVALID; }
-  if (top_k < 0) { lia_set_error("lia_sample: top_k=%d must be >= 0 (0: off)", top_k); return LIA_ERR_INVALID; }
-  if (!(top_p > 0.f && top_p <= 1.f)) { lia_set_error("lia_sample: top_p=%g must be in (0, 1] (1: off)", (double)top_p); return LIA_ERR_INVALID; }
+  if (sample_settings_invalid("lia_sample", temperature, top_k, top_p)) return LIA_ERR_INVALID;
   if (suppress_token < -1 || suppress_token >= vocab) { lia_set_error("lia_sample: suppress_token=%d must be -1 or in [0, vocab)", suppress_token); return LIA_ERR_INVALID; }
   lia_sample_launch(logits, ld, B, vocab, temperature, top_k, top_p, suppress_token, uniforms, next_ids, stats, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
@@ -381,4 +387,73 @@ extern "C" int lia_llama_lm_verify(lia_ctx* ctx, const lia_bf16* hidden, long ld
   LIA_VERIFY_NULL("lia_llama_lm_verify", hidden, normw, lm, block_ids, greedy, accepted, common, next);
   return lm_verify_impl("lia_llama_lm_verify", ctx, hidden, ldh, B, T, H, normw, nullptr, lm, vocab, eps, suppress_token, n_suppress,
                         block_ids, active, greedy, accepted, common, next, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// sampled verification: lm_verify_impl's chunks with lia_sample's draw behind every block position in place of the argmax
+// (lia_verify_sample_kernel, lia_sample.hip), then the same acceptance kernel on the sampled ids
+// ------------------------------------------------------------------------------------------------
+// norm_b == nullptr: RMSNorm (Llama), else LayerNorm
+static int lm_verify_sample_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int B, int T, int H, const bf16_t* norm_w,
+                                 const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, int suppress_token, int n_suppress,
+                                 const int32_t* n_suppress_rows, const lia_block_sampler* smp, const int64_t* block_ids,
+                                 const int32_t* active, int64_t* sampled, int32_t* accepted, int32_t* common, int64_t* next,
+                                 float* p_draft, bf16_t* logits_out, hipStream_t st) {
+  if (!smp) { lia_set_error("%s: NULL sampler", who); return LIA_ERR_INVALID; }
+  if (!smp->uniforms) { lia_set_error("%s: NULL uniforms", who); return LIA_ERR_INVALID; }
+  if (B <= 0) { lia_set_error("%s: B=%d must be >= 1", who, B); return LIA_ERR_INVALID; }
+  if (T < 2) { lia_set_error("%s: T=%d must be >= 2 (the pending token and at least one draft token)", who, T); return LIA_ERR_INVALID; }
+  if ((long)B * T > 0x7fffffffL) { lia_set_error("%s: B=%d x T=%d rows", who, B, T); return LIA_ERR_INVALID; }
+  if (n_suppress < 0 || n_suppress > T) { lia_set_error("%s: n_suppress=%d must be in [0, T=%d]", who, n_suppress, T); return LIA_ERR_INVALID; }
+  if (suppress_token < -1 || (vocab > 0 && suppress_token >= vocab)) { lia_set_error("%s: suppress_token=%d must be -1 or in [0, vocab)", who, suppress_token); return LIA_ERR_INVALID; }
+  if (vocab > LIA_SAMPLE_MAX_VOCAB) { lia_set_error("%s: vocab=%d must be in [1, %d]", who, vocab, LIA_SAMPLE_MAX_VOCAB); return LIA_ERR_INVALID; }
+  if (sample_settings_invalid(who, smp->temperature, smp->top_k, smp->top_p)) return LIA_ERR_INVALID;
+  if (smp->ldu < B) { lia_set_error("%s: ldu=%ld < B=%d", who, smp->ldu, B); return LIA_ERR_INVALID; }
+  if (smp->n_steps < 1) { lia_set_error("%s: n_steps=%d must be >= 1", who, smp->n_steps); return LIA_ERR_INVALID; }
+  if (smp->step0 < 0) { lia_set_error("%s: step0=%d must be >= 0", who, smp->step0); return LIA_ERR_INVALID; }
+  hipError_t copy_err = hipSuccess;
+  const int rc = lm_rows_chunked(who, ctx, hidden, ldh, B * T, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
+    lia_verify_sample_launch(logits, vocab, n, vocab, smp->temperature, smp->top_k, smp->top_p, suppress_token, n_suppress, n_suppress_rows,
+                             T, r0, smp->uniforms, smp->ldu, smp->n_steps, smp->step0, smp->step_rows, block_ids, sampled, p_draft, st);
+    if (logits_out && copy_err == hipSuccess)
+      copy_err = hipMemcpyAsync(logits_out + (size_t)r0 * vocab, logits, (size_t)n * vocab * sizeof(bf16_t), hipMemcpyDeviceToDevice, st);
+  });
+  if (rc) return rc;
+  HIP_TRY(copy_err);
+  lia_verify_accept_launch(block_ids, sampled, active, B, T, accepted, common, next, st);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+#define LIA_VERIFY_SAMPLE_NULL(who, ...)                                                      \
+  do {                                                                                        \
+    const void* const ptrs[] = {__VA_ARGS__};                                                 \
+    static const char* const names[] = {"hidden", "norm weight", "lm_head weight", "block_ids", "sampled", "accepted", "common", "next"}; \
+    for (int i = 0; i < 8; ++i)                                                               \
+      if (!ptrs[i]) { lia_set_error("%s: NULL %s", who, names[i]); return LIA_ERR_INVALID; }  \
+  } while (0)
+
+extern "C" int lia_lm_verify_sample(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* lnw,
+                                    const lia_bf16* lnb, const lia_bf16* emb, int vocab, float eps, int suppress_token, int n_suppress,
+                                    const int32_t* n_suppress_rows, const lia_block_sampler* sampler, const int64_t* block_ids,
+                                    const int32_t* active, int64_t* sampled, int32_t* accepted, int32_t* common, int64_t* next,
+                                    float* p_draft, lia_bf16* logits_out, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  LIA_VERIFY_SAMPLE_NULL("lia_lm_verify_sample", hidden, lnw, emb, block_ids, sampled, accepted, common, next);
+  if (!lnb) { lia_set_error("lia_lm_verify_sample: NULL norm bias"); return LIA_ERR_INVALID; }
+  return lm_verify_sample_impl("lia_lm_verify_sample", ctx, hidden, ldh, B, T, H, lnw, lnb, emb, vocab, eps, suppress_token, n_suppress,
+                               n_suppress_rows, sampler, block_ids, active, sampled, accepted, common, next, p_draft, logits_out,
+                               (hipStream_t)stream);
+}
+
+extern "C" int lia_llama_lm_verify_sample(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* normw,
+                                          const lia_bf16* lm, int vocab, float eps, int suppress_token, int n_suppress,
+                                          const int32_t* n_suppress_rows, const lia_block_sampler* sampler, const int64_t* block_ids,
+                                          const int32_t* active, int64_t* sampled, int32_t* accepted, int32_t* common, int64_t* next,
+                                          float* p_draft, lia_bf16* logits_out, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  LIA_VERIFY_SAMPLE_NULL("lia_llama_lm_verify_sample", hidden, normw, lm, block_ids, sampled, accepted, common, next);
+  return lm_verify_sample_impl("lia_llama_lm_verify_sample", ctx, hidden, ldh, B, T, H, normw, nullptr, lm, vocab, eps, suppress_token,
+                               n_suppress, n_suppress_rows, sampler, block_ids, active, sampled, accepted, common, next, p_draft,
+                               logits_out, (hipStream_t)stream);
 }

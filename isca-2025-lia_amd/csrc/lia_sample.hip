@@ -98,10 +98,16 @@ template <typename T> __device__ __forceinline__ void find_boundary_bin(const T*
   __syncthreads();
 }
 
-__global__ __launch_bounds__(LIA_ROW_THREADS) void lia_sample_kernel(const bf16_t* __restrict__ logits, long ld, int vocab, int vec,
-                                                                     float tau, int top_k, float top_p, int suppress,
-                                                                     const float* __restrict__ uniforms, int64_t* __restrict__ out,
-                                                                     float* __restrict__ stats) {
+// What one row's draw leaves behind for the caller (the same values in every thread; the kernels use thread 0's): the id,
+// lia_sample's four stats, and -- DRAFT only -- the kept weight exp(s - m) of the draft token (0 where it is not kept)
+struct SmpRow { int pick; float t_k, v_p, nkept, W2, w_draft; };
+
+// Passes A - E over one row by the whole LIA_ROW_THREADS workgroup: the one function lia_sample_kernel and lia_verify_sample_kernel
+// both draw with, so that a verify pass's token IS lia_sample's of the same logits and u.  u must be workgroup-uniform.  DRAFT: the
+// thread that meets token `draft` in pass E also leaves its kept weight (no further pass over the row).
+template <bool DRAFT>
+__device__ __forceinline__ SmpRow sample_row(const bf16_t* __restrict__ row, int vocab, bool vec, float tau, int top_k, float top_p,
+                                             int suppress, float u, int draft) {
   __shared__ uint64_t hist[SMP_BINS];            // pass A: uint32 counts (the first half), pass C: uint64 masses
   __shared__ uint64_t nib[16];                   // passes B / D: the 16 low-nibble bins of the boundary bin
   __shared__ uint64_t red64[LIA_ROW_WAVES];
@@ -111,13 +117,14 @@ __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_sample_kernel(const bf16_
   __shared__ int sh_bin, sh_key[2], sh_pick;
   __shared__ uint32_t sh_above32;
   __shared__ uint64_t sh_above64;
+  __shared__ float sh_wd;                        // DRAFT: the draft token's kept weight
   uint32_t* cnt = (uint32_t*)hist;
 
   const int tid = threadIdx.x;
-  const bf16_t* row = logits + (long)blockIdx.x * ld;
   const bool topk_on = top_k > 0 && top_k < vocab;
   const bool topp_on = top_p < 1.0f;
 
+  if (DRAFT && tid == 0) sh_wd = 0.f;              // (pass A's barrier orders it before the owner's store in pass E)
   // ---- pass A: the maximum key; with top-k on, counts per top-12 bin ----
   if (topk_on)
     for (int b = tid; b < SMP_BINS / 2; b += LIA_ROW_THREADS) hist[b] = 0;
@@ -241,7 +248,11 @@ __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_sample_kernel(const bf16_
     float r = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e)
-      if (k[e] >= kap2) { r += expf(score_of_key(k[e], tau) - m); ++nkept; last = i + e; }
+      if (k[e] >= kap2) {
+        const float w = expf(score_of_key(k[e], tau) - m);
+        r += w; ++nkept; last = i + e;
+        if (DRAFT && i + e == draft) sh_wd = w;
+      }
     const float ex = block_excl_scan<float>(r, redf, (float*)nullptr);
     if (tid == LIA_ROW_THREADS - 1) {
       carry_of[j] = carry;
@@ -265,7 +276,7 @@ __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_sample_kernel(const bf16_
 #pragma unroll
   for (int w = 0; w < LIA_ROW_WAVES; ++w) { nkept += (int)red32[w]; last = max(last, (int)(int64_t)red64[w]); }
   const float W2 = carry;
-  const float thr = uniforms[blockIdx.x] * W2;
+  const float thr = u * W2;
   int jc = -1;                        // the first tile whose running sum passes thr
   for (int j = 0; j < ntiles; ++j)
     if (carry_of[j + 1] > thr) { jc = j; break; }
@@ -305,17 +316,64 @@ __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_sample_kernel(const bf16_
     }
     __syncthreads();
   }
-  if (tid == 0) {
-    int pick = jc >= 0 ? sh_pick : last;
-    if (pick < 0 || pick >= vocab) pick = last >= 0 ? last : 0;
-    out[blockIdx.x] = pick;
+  SmpRow res;
+  int pick = jc >= 0 ? sh_pick : last;
+  if (pick < 0 || pick >= vocab) pick = last >= 0 ? last : 0;
+  res.pick = pick;
+  res.t_k = t_k;
+  res.v_p = v_p;
+  res.nkept = (float)nkept;
+  res.W2 = W2;
+  res.w_draft = DRAFT ? sh_wd : 0.f;
+  return res;
+}
+
+__global__ __launch_bounds__(LIA_ROW_THREADS) void lia_sample_kernel(const bf16_t* __restrict__ logits, long ld, int vocab, int vec,
+                                                                     float tau, int top_k, float top_p, int suppress,
+                                                                     const float* __restrict__ uniforms, int64_t* __restrict__ out,
+                                                                     float* __restrict__ stats) {
+  const SmpRow r = sample_row<false>(logits + (long)blockIdx.x * ld, vocab, vec, tau, top_k, top_p, suppress, uniforms[blockIdx.x], -1);
+  if (threadIdx.x == 0) {
+    out[blockIdx.x] = r.pick;
     if (stats) {
       float* so = stats + 4 * (long)blockIdx.x;
-      so[0] = t_k;
-      so[1] = v_p;
-      so[2] = (float)nkept;
-      so[3] = W2;
+      so[0] = r.t_k;
+      so[1] = r.v_p;
+      so[2] = r.nkept;
+      so[3] = r.W2;
     }
+  }
+}
+
+// Speculative sampling ("Sampled verification"): lia_sample's draw behind every position of a draft block.  Chunk row
+// r = r0 + blockIdx.x of the block is block row b = r / T at position t = r % T; `suppress` counts as -inf where t is below
+// n_suppress_rows[b] (or n_suppress with a NULL table); the draw uses U[s, b] of the generation's table (ldu floats per step) at
+// step s = step_rows[b] (or step0) + t -- and u = 0 without a read at s >= n_steps, a position that can never be kept.  The table
+// entry is wave-uniform and goes through readfirstlane: the pass bounds that depend on it stay scalar.  p_draft (or NULL): the
+// probability that this position's draw confirms the draft token block_ids[b, t + 1] -- its kept weight over the kept mass, 0 where
+// it is not kept and at t = T - 1.
+__global__ __launch_bounds__(LIA_ROW_THREADS) void lia_verify_sample_kernel(const bf16_t* __restrict__ logits, long ld, int vocab, int vec,
+                                                                            float tau, int top_k, float top_p, int suppress,
+                                                                            int n_suppress, const int* __restrict__ n_suppress_rows,
+                                                                            int T, int r0, const float* __restrict__ uniforms, long ldu,
+                                                                            int n_steps, int step0, const int* __restrict__ step_rows,
+                                                                            const int64_t* __restrict__ block_ids,
+                                                                            int64_t* __restrict__ sampled, float* __restrict__ p_draft) {
+  const int r = r0 + (int)blockIdx.x;
+  const int b = r / T, t = r % T;
+  const int sup = t < (n_suppress_rows ? __builtin_amdgcn_readfirstlane(n_suppress_rows[b]) : n_suppress) ? suppress : -1;
+  const long s = (long)(step_rows ? __builtin_amdgcn_readfirstlane(step_rows[b]) : step0) + t;
+  float u = 0.f;
+  if (s >= 0 && s < n_steps) u = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(uniforms[s * ldu + b])));
+  int draft = -1;
+  if (p_draft && t < T - 1) {
+    const int64_t d = block_ids[(long)r + 1];
+    draft = d >= 0 && d < (int64_t)vocab ? (int)d : -1;
+  }
+  const SmpRow o = sample_row<true>(logits + (long)blockIdx.x * ld, vocab, vec, tau, top_k, top_p, sup, u, draft);
+  if (threadIdx.x == 0) {
+    sampled[r] = o.pick;
+    if (p_draft) p_draft[r] = o.w_draft > 0.f ? o.w_draft / o.W2 : 0.f;
   }
 }
 
@@ -325,4 +383,14 @@ extern "C" void lia_sample_launch(const bf16_t* logits, long ld, int B, int voca
   const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
   hipLaunchKernelGGL(lia_sample_kernel, dim3(B), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, tau, top_k, top_p, suppress,
                      uniforms, out, stats);
+}
+
+extern "C" void lia_verify_sample_launch(const bf16_t* logits, long ld, int n, int vocab, float tau, int top_k, float top_p, int suppress,
+                                         int n_suppress, const int* n_suppress_rows, int T, int r0, const float* uniforms, long ldu,
+                                         int n_steps, int step0, const int* step_rows, const int64_t* block_ids, int64_t* sampled,
+                                         float* p_draft, hipStream_t st) {
+  if (n <= 0) return;
+  const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
+  hipLaunchKernelGGL(lia_verify_sample_kernel, dim3(n), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, tau, top_k, top_p, suppress,
+                     n_suppress, n_suppress_rows, T, r0, uniforms, ldu, n_steps, step0, step_rows, block_ids, sampled, p_draft);
 }

@@ -42,6 +42,12 @@ class KV(ctypes.Structure):
     _fields_ = [("k", c_void_p), ("v", c_void_p), ("smax", c_int), ("batch", c_int), ("on_device", c_int)]
 
 
+class BlockSampler(ctypes.Structure):
+    """lia_block_sampler: the settings and the U table of a sampled verify pass"""
+    _fields_ = [("temperature", c_float), ("top_k", c_int), ("top_p", c_float), ("uniforms", c_void_p), ("ldu", c_long),
+                ("n_steps", c_int), ("step0", c_int), ("step_rows", c_void_p)]
+
+
 # name -> (restype, argtypes).  Every symbol include/lia_hip.h declares is listed here; the CPU test
 # suite checks the shared object exports all of them.
 SIGNATURES = {
@@ -117,6 +123,12 @@ SIGNATURES = {
     "lia_embed_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "lia_lm_verify_rows": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lia_lm_verify_sample": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_int,
+                                     c_void_p, ctypes.POINTER(BlockSampler), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p]),
+    "lia_llama_lm_verify_sample": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_int, c_int,
+                                           c_void_p, ctypes.POINTER(BlockSampler), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p]),
     "lia_embed_padded": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "lia_attention_padded": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_void_p, c_void_p]),

@@ -28,8 +28,10 @@ def _chk(t, dtype=torch.bfloat16):
         raise ValueError(f"expected a contiguous {dtype} CUDA tensor, got {t.dtype} {t.device} contiguous={t.is_contiguous()}")
 
 
-# lia_lm_verify's outputs, all on the device: greedy int64 [B, T], accepted int32 [B], common int32 [1], next int64 [B]
-VerifyResult = collections.namedtuple("VerifyResult", "greedy accepted common next")
+# lia_lm_verify's outputs, all on the device: greedy int64 [B, T], accepted int32 [B], common int32 [1], next int64 [B].  On the
+# sampled route (lia_lm_verify_sample) `greedy` holds the SAMPLED ids, p_draft is float32 [B, T] and logits bf16 [B, T, vocab], each
+# where it was asked for.
+VerifyResult = collections.namedtuple("VerifyResult", "greedy accepted common next logits p_draft", defaults=(None, None))
 
 
 class Context:
@@ -310,6 +312,54 @@ class Context:
                                              int(suppress_token), int(n_suppress), _ptr(block_ids), _ptr(active), _ptr(out.greedy),
                                              _ptr(out.accepted), _ptr(out.common), _ptr(out.next), self._st(stream)), "lia_llama_lm_verify")
         return out
+
+    def _verify_sample(self, name, norm, head, hidden, block_ids, block, eps, suppress_token, n_suppress, n_suppress_rows, active,
+                       return_logits, return_p_draft, stream):
+        for t in norm + (head,):
+            _chk(t)
+        B, T, H, out = self._verify_args(hidden, block_ids, active)
+        dev = hidden.device
+        U = block.uniforms
+        _chk(U, torch.float32)
+        if U.dim() != 2:
+            raise ValueError(f"uniforms must be the generation's [steps, rows] table, got shape {tuple(U.shape)}")
+        if n_suppress_rows is not None:
+            _chk(n_suppress_rows, torch.int32)
+            if n_suppress_rows.numel() != B:
+                raise ValueError(f"n_suppress_rows has {n_suppress_rows.numel()} entries, block_ids {B} rows")
+        step_rows = block.step_rows
+        if step_rows is not None:
+            step_rows = torch.as_tensor(step_rows).to(device=dev, dtype=torch.int32).contiguous()
+            if step_rows.numel() != B:
+                raise ValueError(f"step_rows has {step_rows.numel()} entries, block_ids {B} rows")
+            if U.is_cuda:
+                torch.cuda.current_stream().synchronize()      # (the library's stream reads what torch's just copied)
+            self._step_rows = step_rows                        # alive until the next call: the launch below is asynchronous
+        args = N.BlockSampler(float(block.temperature), int(block.top_k), float(block.top_p), U.data_ptr(), U.stride(0), U.shape[0],
+                              int(block.step0), None if step_rows is None else step_rows.data_ptr())
+        vocab = head.shape[0]
+        logits = torch.empty((B, T, vocab), dtype=torch.bfloat16, device=dev) if return_logits else None
+        p_draft = torch.empty((B, T), dtype=torch.float32, device=dev) if return_p_draft else None
+        N.check(getattr(self.lib, name)(self.handle, _ptr(hidden), H, B, T, H, *[_ptr(t) for t in norm], _ptr(head), vocab, eps,
+                                        int(suppress_token), int(n_suppress), _ptr(n_suppress_rows), ctypes.byref(args), _ptr(block_ids),
+                                        _ptr(active), _ptr(out.greedy), _ptr(out.accepted), _ptr(out.common), _ptr(out.next),
+                                        _ptr(p_draft), _ptr(logits), self._st(stream)), name)
+        return out._replace(logits=logits, p_draft=p_draft)
+
+    def lm_verify_sample(self, hidden, lnw, lnb, emb, block_ids, block, eps=1e-5, suppress_token=-1, n_suppress=0, n_suppress_rows=None,
+                         active=None, return_logits=False, return_p_draft=False, stream=None):
+        """lia_lm_verify_sample: lm_verify with lia_sample's draw behind every block position in place of the argmax.  block
+        (sampling.Sampler.block / block_rows): the settings, the generation's U table and the step origin -- position t of row b
+        draws with U[step + t, b], 0 past the table.  n_suppress_rows (int32 [B], device) replaces n_suppress where given.
+        -> VerifyResult with the sampled ids as `greedy`; logits / p_draft where asked for."""
+        return self._verify_sample("lia_lm_verify_sample", (lnw, lnb), emb, hidden, block_ids, block, eps, suppress_token, n_suppress,
+                                   n_suppress_rows, active, return_logits, return_p_draft, stream)
+
+    def llama_lm_verify_sample(self, hidden, normw, lm, block_ids, block, eps=1e-5, suppress_token=-1, n_suppress=0, n_suppress_rows=None,
+                               active=None, return_logits=False, return_p_draft=False, stream=None):
+        """lia_llama_lm_verify_sample: lm_verify_sample with the final RMSNorm and the untied lm_head of a Llama"""
+        return self._verify_sample("lia_llama_lm_verify_sample", (normw,), lm, hidden, block_ids, block, eps, suppress_token, n_suppress,
+                                   n_suppress_rows, active, return_logits, return_p_draft, stream)
 
     def score_chunk_rows(self, M, H, vocab):
         """rows per chunk lm_score would use for M rows in this context's workspace (0: not even min(M, 256) rows fit)"""

@@ -125,13 +125,30 @@ def build_parser():
     p.add_argument("--draft-model", default=None, type=str,
                    help="speculative greedy decoding: an OPT / Llama shape name or checkpoint directory of the same vocabulary, kept all "
                         "resident (policies 3 / 3) beside the target; it proposes --draft-tokens tokens per round and one pass of the "
-                        "target's weights verifies them (same ids as plain greedy; not with --do-sample or --cpu-layers -1)")
+                        "target's weights verifies them (same ids as plain greedy; with --do-sample only together with --sampled-verify; "
+                        "not with --cpu-layers -1)")
     p.add_argument("--draft-tokens", default=4, type=int, help="with --draft-model: draft tokens per round")
     p.add_argument("--acceptance", default="common", choices=["common", "row"],
                    help="with --draft-model: common = every row keeps the minimum over the rows per round; row = every row keeps what it "
                         "accepted itself on a ragged KV cache (OPT with --prefill-policy 3 --decoding-policy 3)")
+    p.add_argument("--sampled-verify", action="store_true",
+                   help="with --draft-model and --do-sample: speculative SAMPLED decoding -- the verify pass draws every block position "
+                        "with the generation's own uniforms, a draft token is accepted iff it equals the draw (the ids are the same "
+                        "function of the logits and --sample-seed as plain --do-sample)")
+    p.add_argument("--draft-coupled", action="store_true",
+                   help="with --sampled-verify: the draft model samples its own logits with the target's settings and uniforms (it guesses "
+                        "the draw, not the argmax)")
     add_init_args(p)
     return p
+
+
+def check_spec_sample_flags(args):
+    """--sampled-verify / --draft-coupled without what they modify: refused by name"""
+    if args.sampled_verify and not (args.draft_model and args.do_sample):
+        raise SystemExit("[ERROR] --sampled-verify needs --draft-model and --do-sample: it verifies the draft with the sampler's own draws")
+    if args.draft_coupled and not args.sampled_verify:
+        raise SystemExit("[ERROR] --draft-coupled needs --sampled-verify (with --draft-model and --do-sample): the draft model draws with "
+                         "the target's uniforms, which only a sampled verify pass confirms")
 
 
 def synthetic_prompt(vocab, n_tokens, batch, seed=0):
@@ -351,7 +368,7 @@ def load_draft(args):
     d.pin_weight, d.enable_cxl, d.cpu_layers, d.stream_format = True, False, 0, args.stream_format
     model = load_model(d)
     attach_scheduler(model, d.stream_format or default_stream_format())
-    return ModelDrafter(model)
+    return ModelDrafter(model, coupled=args.draft_coupled)
 
 
 def summarize_speculation(spec_log, total_list, batch_size, out=print, acceptance="common"):
@@ -600,6 +617,7 @@ def main(argv=None):
 
 def _main(args, rec=None):
     print(args)
+    check_spec_sample_flags(args)
     if args.prompt is not None and args.prompt_file is not None:
         raise SystemExit("[ERROR] --prompt and --prompt-file exclude each other: one prompt for every row, or one per line of the file")
     if not args.benchmark:
@@ -654,6 +672,8 @@ def _main(args, rec=None):
         generate_kwargs.update(draft=load_draft(args), draft_tokens=args.draft_tokens, spec_log=spec_log)
         if args.acceptance != "common":
             generate_kwargs.update(acceptance=args.acceptance)
+        if args.sampled_verify:
+            generate_kwargs.update(sampled_verify=True)
     tokenizer = load_tokenizer(args.model_id)
     if args.prompt_file is not None:
         input_ids, generate_kwargs["attention_mask"] = prompt_file_inputs(args, model.shape.vocab, tokenizer,

@@ -78,6 +78,67 @@ class Sampler:
         self.u = self.uniforms[step]
         return self
 
+    def at_rows(self, steps):
+        """a Sampler of the same settings whose u[b] = U[steps[b], b], 0 where steps[b] is past the table: row b at ITS step (a
+        coupled drafter's draft step, row mode).  self is not touched."""
+        n, B = self.uniforms.shape
+        steps = torch.as_tensor(steps, dtype=torch.int64).to(self.uniforms.device)
+        if steps.dim() == 0:
+            steps = steps.expand(B)
+        u = self.uniforms[steps.clamp(0, n - 1), torch.arange(B, device=self.uniforms.device)]
+        out = Sampler(self.temperature, self.top_k, self.top_p, self.uniforms)
+        out.u = torch.where((steps >= 0) & (steps < n), u, torch.zeros_like(u)).contiguous()
+        if out.u.is_cuda:
+            torch.cuda.current_stream().synchronize()      # the library's compute stream reads u
+        return out
+
+    def block(self, step0):
+        """what a sampled verify pass reads (speculative decoding): every row has generated step0 tokens, block
+        position t of row b draws with U[step0 + t, b]"""
+        return SamplerBlock(self, int(step0), None)
+
+    def block_rows(self, steps):
+        """block() with one origin per row (row mode): block position t of row b draws with U[steps[b] + t, b]"""
+        return SamplerBlock(self, 0, torch.as_tensor(steps, dtype=torch.int32).contiguous())
+
     def __call__(self, ctx, logits, suppress_token, stream=None):
         """the sampled ids (device int64 [B]) of logits [B, vocab] on ctx's compute stream"""
         return ctx.sample(logits, self.temperature, self.top_k, self.top_p, self.u, suppress_token=suppress_token, stream=stream)
+
+
+class SamplerBlock:
+    """A view of a generation's Sampler for one verify round: the settings, the table (`uniforms` [n_steps, ldu]; row b is column
+    b), and the step origin -- step0 for every row, or step_rows (int32 [B], CPU).  A position whose step is >= n_steps draws with
+    u = 0 and reads nothing: it can never be kept."""
+
+    def __init__(self, sampler, step0, step_rows):
+        self.sampler, self.step0, self.step_rows = sampler, step0, step_rows
+        self.temperature, self.top_k, self.top_p = sampler.temperature, sampler.top_k, sampler.top_p
+        self.uniforms = sampler.uniforms
+        self.n_steps, self.ldu = int(sampler.uniforms.shape[0]), int(sampler.uniforms.stride(0))
+
+    def steps(self, t=0):
+        """int64 [B]: the step of block position t per row"""
+        B = self.uniforms.shape[1]
+        base = torch.full((B,), self.step0, dtype=torch.int64) if self.step_rows is None else self.step_rows.to(torch.int64)
+        return base + t
+
+    def step(self, t):
+        """the Sampler of block position t: what a coupled drafter's draft step t draws with"""
+        return self.sampler.at_rows(self.steps(t))
+
+    def draft_steps(self, k):
+        """step(0) .. step(k - 1) from one gather and one synchronise: a coupled drafter's round"""
+        U = self.uniforms
+        n, B = U.shape
+        s = (self.steps()[None, :] + torch.arange(k, dtype=torch.int64)[:, None]).to(U.device)
+        u = U[s.clamp(0, n - 1), torch.arange(B, device=U.device)[None, :]]
+        u = torch.where((s >= 0) & (s < n), u, torch.zeros_like(u)).contiguous()
+        if u.is_cuda:
+            torch.cuda.current_stream().synchronize()      # the library's compute stream reads u
+        out = []
+        for i in range(k):
+            smp = Sampler(self.temperature, self.top_k, self.top_p, U)
+            smp.u = u[i]
+            out.append(smp)
+        return out

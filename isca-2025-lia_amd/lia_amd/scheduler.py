@@ -330,7 +330,7 @@ class OffloadScheduler:
 
     def verify(self, block_ids, kv_state, suppress_token=-1, n_suppress=0, active=None, prefill_policy=1, decoding_policy=1,
                no_overlap=False, pin_weight=False, gpu_percentage=0, num_minibatch=1, enable_cxl=False, append_policy=None,
-               **_decode_only):
+               sampler=None, return_logits=False, **_decode_only):
         """Speculative verification: one pass of the weights over block_ids [B, T] = [pending | d_1 .. d_{T-1}]
         appended at kv_state.len on a NON-EMPTY cache.  forward()'s phases with the last layer on every position, lm_verify in
         place of lm_head and LIA_OPT_BLOCK_ATTENTION set around the layers; the K/V rows are delivered as in forward().  Returns
@@ -338,7 +338,9 @@ class OffloadScheduler:
         is pos0 + common + 1 -- the rows behind it are dead and are rewritten by the next round (nothing is outstanding into them:
         _deliver has synchronised both streams and awaited the policy-0 stores).  suppress_token counts as -inf at block positions
         < n_suppress; active (int32 / bool [B] or None): rows with 0 never limit common.  A fixed cpu_layers is passed through as
-        in score()."""
+        in score().  sampler (sampling.SamplerBlock, sampled verification): the head is lm_verify_sample -- res.greedy holds the
+        draws of U[step + t, b], res.p_draft the chance of each to confirm the draft; return_logits (with a sampler, for tests and
+        measurements) also returns the block's logits.  Everything else is the same pass."""
         from . import speculative
         check_verify_block(block_ids, kv_state)
         B, T = block_ids.shape
@@ -360,7 +362,11 @@ class OffloadScheduler:
                 hidden = self._run_layers(s, kv_state)
         finally:
             ctx.set_option(N.LIA_OPT_BLOCK_ATTENTION, 0)
-        res = ctx.lm_verify(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, sh.ln_eps, suppress_token, n_suppress, act_dev)
+        if sampler is None:
+            res = ctx.lm_verify(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, sh.ln_eps, suppress_token, n_suppress, act_dev)
+        else:
+            res = ctx.lm_verify_sample(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, sampler, sh.ln_eps, suppress_token,
+                                       n_suppress, active=act_dev, return_logits=return_logits, return_p_draft=True)
         self._deliver(s, kv_state)
         common = int(res.common.item())
         kv_state.len = pos0 + common + 1
@@ -368,14 +374,15 @@ class OffloadScheduler:
 
     def verify_rows(self, block_ids, kv_state, row_lens, suppress_token=-1, n_suppress_rows=None, active=None, prefill_policy=1,
                     decoding_policy=1, no_overlap=False, pin_weight=False, gpu_percentage=0, num_minibatch=1, enable_cxl=False,
-                    **_decode_only):
+                    sampler=None, return_logits=False, **_decode_only):
         """verify() on a ragged cache (DESIGN.md 3.11, row mode): row b of block_ids [B, T] is appended at ITS cache length
         row_lens[b] (int32 [B]; the caller owns it).  Policies 3 / 3 only -- every layer's cache in HBM.  verify()'s phases with the
         library's row-length table (lia_ctx_set_row_lens) set around the embedding and the layer calls and cleared in a finally:
         while it is set every layer call is the ragged form (per-row positions, K/V scatter, ragged block attention), with
         max(row_lens) as the scalar position that sizes buffers.  num_minibatch > 1 serves slices of the table as it does of the key
         starts.  suppress_token counts as -inf at block positions < n_suppress_rows[b] (int32 [B] or None: zeros).  Returns
-        ops.VerifyResult (device tensors); kv_state.len is NOT advanced."""
+        ops.VerifyResult (device tensors); kv_state.len is NOT advanced.  sampler (sampling.SamplerBlock of block_rows) /
+        return_logits: as in verify()."""
         row_lens = np.ascontiguousarray(np.asarray(row_lens, dtype=np.int32))
         flags = dict(prefill_policy=prefill_policy, decoding_policy=decoding_policy, cpu_layers=int(_decode_only.get("cpu_layers") or 0))
         sh = self.model.shape
@@ -401,7 +408,11 @@ class OffloadScheduler:
                 hidden = self._run_layers(s, kv_state)
             finally:
                 ctx.set_row_lens(None)
-            res = ctx.lm_verify_rows(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, nsup_dev, sh.ln_eps, suppress_token, act_dev)
+            if sampler is None:
+                res = ctx.lm_verify_rows(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, nsup_dev, sh.ln_eps, suppress_token, act_dev)
+            else:
+                res = ctx.lm_verify_sample(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, sampler, sh.ln_eps, suppress_token,
+                                           n_suppress_rows=nsup_dev, active=act_dev, return_logits=return_logits, return_p_draft=True)
             self._deliver(s, kv_state)
         finally:
             kv_state.len = len0

@@ -1,4 +1,4 @@
-"""Speculative greedy decoding: a drafter proposes k tokens per row, the target model verifies the block
+"""Speculative decoding: a drafter proposes k tokens per row, the target model verifies the block
 [pending | proposal] in ONE pass of its weights (scheduler.verify) and keeps what its own greedy search would have produced.
 
 The cache length stays one integer per batch: a round accepts `common` draft tokens on every row, the minimum over the active rows'
@@ -15,6 +15,10 @@ Row mode, generate(..., acceptance="row") (speculative_search_rows): OPT targets
 (policies 3 / 3) keep one cache length PER ROW -- row b appends accepted[b] + 1 tokens per round, whatever the other rows accept, and
 the number of target passes is set by the slowest row's own acceptance.  The drafter then needs
 propose_rows(rows: list of 1-D int64 CPU tensors, k, suppress_rows) -> int64 [B, k]  with suppress_rows = (token, [n per row]).
+
+Sampled verification, generate(..., do_sample=True, sampled_verify=True, draft=...): the verify pass draws every block position with
+the uniform the plain sampled loop would use there (U[generated so far + t, row]); a draft token is accepted iff it equals that
+draw, and the emitted token is always the draw.  The ids are the same function of (logits, U) as plain sampled decoding's.
 """
 import time
 
@@ -22,7 +26,10 @@ import numpy as np
 import torch
 
 REFUSALS = {
-    "do_sample": "draft together with do_sample=True is not supported: verification keeps the GREEDY token of every position",
+    "do_sample": "draft together with do_sample=True is not supported: verification keeps the GREEDY token of every position "
+                 "(sampled_verify=True verifies with the sampler's own draws instead)",
+    "sampled_verify": "sampled_verify=True needs do_sample=True and draft=: it is speculative decoding whose verify pass draws every "
+                      "position with the generation's own uniforms",
     "return_logits": "draft together with return_logits=True is not supported: a verify pass never materialises the logits",
     "dp": "draft together with a data-parallel group is not supported: the ranks would accept different counts",
     "cpu_layers": "draft together with cpu_layers=-1 (the online cooperative split) is not supported: the controller samples "
@@ -115,9 +122,12 @@ def block_attention_for(sched, shape, B, T, pos0):
     return bool(mode)
 
 
-def check_settings(model, sched, draft, draft_tokens, do_sample, return_logits, lia):
-    """every refusal of generate(draft=), by name (ValueError)"""
-    if do_sample:
+def check_settings(model, sched, draft, draft_tokens, do_sample, return_logits, lia, sampled_verify=False):
+    """every refusal of generate(draft=), by name (ValueError).  Sampling is opt-in: do_sample=True is served with
+    sampled_verify=True only, and sampled_verify=True with do_sample=True only."""
+    if sampled_verify and not do_sample:
+        raise ValueError(REFUSALS["sampled_verify"])
+    if do_sample and not sampled_verify:
         raise ValueError(REFUSALS["do_sample"])
     if return_logits:
         raise ValueError(REFUSALS["return_logits"])
@@ -184,13 +194,18 @@ class ModelDrafter:
     feeds the tokens its cache lacks -- one, or two after a fully accepted round -- through the decode / append paths and runs
     k - 1 more decode steps whose argmax stays on the device.  Its cache length is rolled back to the common prefix of what it was
     fed and the ids it is given; it prefills again when that prefix is empty, the batch changed or the cache is too small (a new
-    conversation, a new turn of past=)."""
+    conversation, a new turn of past=).
+
+    coupled=True (sampled verification only): the loops hand propose / propose_rows the round's sampling.SamplerBlock, and draft
+    step i samples the drafter's own logits with the target's settings and the target's uniform of that position, U[g_b + i, b]
+    (0 past the table) -- it guesses the target's DRAW, not its argmax, and is right wherever the two models' running masses put
+    that uniform on the same token.  A drafter only ever changes how many positions a round keeps, never a token."""
 
     FLAGS = dict(prefill_policy=3, decoding_policy=3, gpu_percentage=100, pin_weight=True)
 
-    def __init__(self, model, reserve=64):
+    def __init__(self, model, reserve=64, coupled=False):
         from .generation import _scheduler_of
-        self.model, self.sched, self.reserve = model, _scheduler_of(model), reserve
+        self.model, self.sched, self.reserve, self.coupled = model, _scheduler_of(model), reserve, bool(coupled)
         self.vocab = model.shape.vocab
         self.kv = None
         self.fed = None          # int64 [B, kv.len]: the tokens whose K/V the cache holds
@@ -203,7 +218,13 @@ class ModelDrafter:
             return LlamaKVState(self.model, B, smax)
         return self.sched.new_kv_state(B, n, smax - n, **self.FLAGS)
 
-    def propose(self, ids, k, suppress=(-1, 0)):
+    def _step_kw(self, sampler, k):
+        """the forward keywords of draft steps 0 .. k - 1: the coupled draws (gathered once per round), or none (the argmax)"""
+        if not self.coupled or sampler is None:
+            return [{}] * k
+        return [{"sampler": s} for s in sampler.draft_steps(k)]
+
+    def propose(self, ids, k, suppress=(-1, 0), sampler=None):
         ids = torch.as_tensor(ids, dtype=torch.int64).cpu()
         B, n = ids.shape
         tok, n_sup = suppress
@@ -219,10 +240,10 @@ class ModelDrafter:
             self.prefills += 1
         self.kv.len = keep
         cur = ids[:, keep:]
-        dev = []
+        dev, step_kw = [], self._step_kw(sampler, k)
         for i in range(k):
             sup = tok if i < n_sup else -1
-            _, nxt = self.sched.forward(cur, self.kv, max_new_tokens=k, suppress_token=sup, **self.FLAGS)
+            _, nxt = self.sched.forward(cur, self.kv, max_new_tokens=k, suppress_token=sup, **step_kw[i], **self.FLAGS)
             dev.append(nxt)
             cur = nxt.view(B, 1)
         out = torch.stack(dev, dim=1).cpu()
@@ -231,7 +252,7 @@ class ModelDrafter:
         return out
 
 
-    def propose_rows(self, rows, k, suppress_rows=(-1, None), pad_token_id=1):
+    def propose_rows(self, rows, k, suppress_rows=(-1, None), pad_token_id=1, sampler=None):
         """Row mode's baseline: every round is a fresh generation of its own -- the rows right-aligned (left padded to the longest),
         prefilled through the attention_mask machinery (the scheduler's key starts), then k - 1 decode steps.  No cache is kept
         between rounds.  suppress_rows = (token, [n per row]): `token` is suppressed at the steps below the SMALLEST n, so the
@@ -253,10 +274,10 @@ class ModelDrafter:
         self.kv = self.fed = None                      # (a later propose() of common mode starts from a fresh cache)
         self.sched.set_key_starts(starts if starts.any() else None)
         try:
-            cur, dev = ids, []
+            cur, dev, step_kw = ids, [], self._step_kw(sampler, k)
             for i in range(k):
                 sup = tok if i < n_sup else -1
-                _, nxt = self.sched.forward(cur, kv, max_new_tokens=k, suppress_token=sup, **self.FLAGS)
+                _, nxt = self.sched.forward(cur, kv, max_new_tokens=k, suppress_token=sup, **step_kw[i], **self.FLAGS)
                 dev.append(nxt)
                 cur = nxt.view(B, 1)
             out = torch.stack(dev, dim=1).cpu()
@@ -267,14 +288,30 @@ class ModelDrafter:
         return out
 
 
+# Sampled verification reaches the schedulers and the drafters through keywords that exist only on that route: without a sampler
+# the loops make exactly the calls they made before it existed.
+def _first_kw(sampler):
+    return {} if sampler is None else {"sampler": sampler.at(0)}
+
+
+def _verify_kw(view):
+    return {} if view is None else {"sampler": view}
+
+
+def _draft_kw(draft, view):
+    """the round's sampler view, for drafters that declare `coupled` only"""
+    return {"sampler": view} if (view is not None and getattr(draft, "coupled", False)) else {}
+
+
 def speculative_search_rows(model, sched, input_ids, max_new_tokens, min_new_tokens, eos_token_id, pad_token_id, token_latency, lia,
-                            draft, draft_tokens, spec_log=None, step_hook=None, max_steps=None, starts=None):
+                            draft, draft_tokens, spec_log=None, step_hook=None, max_steps=None, starts=None, sampler=None):
     """speculative_search with one cache length per row (acceptance="row").  Row b has generated g[b] tokens, caches T + g[b] - 1
     positions (its last token is pending), and appends greedy[b, :accepted[b] + 1] per round, cut behind its EOS token and at
     max_new_tokens.  A finished or full row is inactive: its block is pad tokens, its length stands still, it never holds another
     row back.  The output is _greedy_search's: finished rows padded with pad_token_id up to the length the greedy loop would have
     reached (the longest row's).  latency_list has one entry per target pass; spec_log receives (min over the active rows,
-    accepted per row) per round."""
+    accepted per row) per round.  sampler (the generation's sampling.Sampler, sampled verification): the first forward draws with
+    U[0], a round's block position t of row b with U[g[b] + t, b]; the sampled ids stand where `greedy` stood."""
     k = draft_tokens
     ids = torch.as_tensor(input_ids, dtype=torch.int64).cpu()
     if ids.dim() != 2:
@@ -301,7 +338,7 @@ def speculative_search_rows(model, sched, input_ids, max_new_tokens, min_new_tok
         step_hook(0)
     tic = time.time()
     suppress = eos_token_id if (eos_token_id is not None and 0 < min_new_tokens) else -1
-    _, nxt = sched.forward(ids, kv, max_new_tokens=max_new_tokens, suppress_token=suppress, **lia)
+    _, nxt = sched.forward(ids, kv, max_new_tokens=max_new_tokens, suppress_token=suppress, **_first_kw(sampler), **lia)
     for b, token in enumerate(nxt.cpu().tolist()):
         append(b, token)
     latency_list.append(time.time() - tic)
@@ -318,13 +355,15 @@ def speculative_search_rows(model, sched, input_ids, max_new_tokens, min_new_tok
         n_sup = np.clip(min_new_tokens - g, 0, k + 1).astype(np.int32) if eos_token_id is not None else np.zeros(B, np.int32)
         sup_tok = eos_token_id if n_sup.any() else -1
         rows = [ids_buf[b, :T + g[b]] for b in range(B)]
-        prop = torch.as_tensor(draft.propose_rows(rows, k, (sup_tok, np.minimum(n_sup, k).tolist())), dtype=torch.int64).cpu()
+        view = None if sampler is None else sampler.block_rows(g)
+        prop = torch.as_tensor(draft.propose_rows(rows, k, (sup_tok, np.minimum(n_sup, k).tolist()), **_draft_kw(draft, view)),
+                               dtype=torch.int64).cpu()
         if tuple(prop.shape) != (B, k):
             raise ValueError(f"draft.propose_rows returned shape {tuple(prop.shape)}, expected {(B, k)}")
         block = torch.cat([torch.stack([r[-1] for r in rows])[:, None], prop], dim=1)
         block[torch.from_numpy(~active)] = pad_token_id                      # an inactive row is fed pad tokens
         res = sched.verify_rows(block, kv, row_lens, suppress_token=sup_tok, n_suppress_rows=n_sup,
-                                active=torch.from_numpy(active.astype(np.int32)), **lia)
+                                active=torch.from_numpy(active.astype(np.int32)), **_verify_kw(view), **lia)
         greedy, acc = res.greedy.cpu(), res.accepted.cpu().tolist()
         if spec_log is not None:
             spec_log.append((min(a for a, on in zip(acc, active) if on), acc))
@@ -341,11 +380,14 @@ def speculative_search_rows(model, sched, input_ids, max_new_tokens, min_new_tok
 
 def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, eos_token_id, pad_token_id, token_latency, lia,
                        draft, draft_tokens, spec_log=None, step_hook=None, max_steps=None, past=None, return_state=False,
-                       reserve_tokens=0, starts=None):
+                       reserve_tokens=0, starts=None, sampler=None):
     """_greedy_search with a drafter: the ordinary prefill, then rounds of propose -> verify -> append.  The EOS / pad / unfinished
     bookkeeping is applied token by token as the greedy loop applies it; a finished row is inactive (it never limits `common`, its
     block is pad tokens, as the greedy loop feeds them); a round ends behind the token at which a row finishes, so the cache holds
-    exactly what the greedy loop would have fed.  latency_list has one entry per target pass."""
+    exactly what the greedy loop would have fed.  latency_list has one entry per target pass.
+    sampler (the generation's sampling.Sampler, sampled verification): the first forward draws with U[0] as the plain sampled loop
+    does, and a round that starts with g generated tokens draws block position t with U[g + t] -- the token at generated step s is
+    lia_sample(logits(prefix), U[s]) on either loop; the sampled ids stand where `greedy` stood."""
     from .generation import GenerationState, turn_positions
     k = draft_tokens
     ids = torch.as_tensor(input_ids, dtype=torch.int64).cpu()
@@ -400,7 +442,7 @@ def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, 
         step_hook(0)
     tic = time.time()
     suppress = eos_token_id if (eos_token_id is not None and 0 < min_new_tokens) else -1
-    _, nxt = sched.forward(first, kv, max_new_tokens=max_new_tokens, suppress_token=suppress, **lia)
+    _, nxt = sched.forward(first, kv, max_new_tokens=max_new_tokens, suppress_token=suppress, **_first_kw(sampler), **lia)
     over, _ = append(nxt.cpu())
     latency_list.append(time.time() - tic)
     rnd = 0
@@ -414,13 +456,14 @@ def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, 
         n_sup = int(np.clip(min_new_tokens - g, 0, k + 1)) if eos_token_id is not None else 0
         sup_tok = eos_token_id if n_sup else -1
         active = state["unfinished"]
-        prop = torch.as_tensor(draft.propose(ids_buf[:, :T + g], k, (sup_tok, min(n_sup, k))), dtype=torch.int64).cpu()
+        view = None if sampler is None else sampler.block(g)
+        prop = torch.as_tensor(draft.propose(ids_buf[:, :T + g], k, (sup_tok, min(n_sup, k)), **_draft_kw(draft, view)), dtype=torch.int64).cpu()
         if tuple(prop.shape) != (B, k):
             raise ValueError(f"draft.propose returned shape {tuple(prop.shape)}, expected {(B, k)}")
         if eos_token_id is not None:
             prop = prop * active[:, None] + pad_token_id * (1 - active[:, None])      # a finished row is fed pad tokens
         block = torch.cat([ids_buf[:, T + g - 1:T + g], prop], dim=1)
-        res, common = sched.verify(block, kv, suppress_token=sup_tok, n_suppress=n_sup, active=active.to(torch.int32), **lia)
+        res, common = sched.verify(block, kv, suppress_token=sup_tok, n_suppress=n_sup, active=active.to(torch.int32), **_verify_kw(view), **lia)
         greedy = res.greedy.cpu()
         if spec_log is not None:
             spec_log.append((common, res.accepted.cpu().tolist()))

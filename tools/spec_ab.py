@@ -22,7 +22,18 @@ loop, in the same process, the two modes' generations taken in turn --reps times
 independently per round (uniform on 0 .. k, seeded), the same script for both modes.  Per k and mode: the verify pass (median, and
 the min .. max of the generations' medians: the run-to-run spread), the passes, tokens/s; then the accepted counts per round, each
 line marked on or off the script (off: some active row's count inside the run differs from its scripted one -- such a line is not
-a figure of an acceptance rate).  The ModelDrafter's row-mode round (a fresh left-padded prefill + k - 1 steps) is timed at the end."""
+a figure of an acceptance rate).  The ModelDrafter's row-mode round (a fresh left-padded prefill + k - 1 steps) is timed at the end.
+
+    python tools/spec_ab.py --config ... --sampled 1.0,4,1.0 [--coupled] [--acceptance common,row] [--draft opt-125m | none]
+
+--sampled tau,k,p: sampled verification (generate(do_sample=True, sampled_verify=True)) in the same process as the plain sampled run
+and the greedy verify, their generations taken in turn --reps times.  Per k and mode: the sampled verify pass beside the greedy
+verify pass and a plain sampled decode step (medians, and the min .. max of the generations' medians), tokens/s, the accepted draft
+tokens per round beside the mean p_draft of the same rounds' first positions (the expectation of a first token's acceptance), and how
+many rows left the plain sampled ids, with the first step at which one did (a verify pass and a decode step round differently: such
+rows are still exact samples of the verify pass's distribution).  The ReplayDrafter replays the plain SAMPLED run.  With --draft, a
+ModelDrafter of that shape (random weights of its own: real checkpoints are not available here) drafts greedily and, with --coupled,
+with the target's uniforms; each line is marked on or off what its drafter would be expected to give only by its p_draft column."""
 import argparse
 import os
 import statistics
@@ -87,6 +98,80 @@ def rows_ab(a, model, prompt, rec, plain, step, ks, modes, kw, generate, ReplayD
                 print(f"      round {r:2d} [{'on ' if on else 'OFF'} script] kept {lo if m == 'common' else 'per row'}, accepted per row {acc}", flush=True)
 
 
+def sampled_ab(a, model, prompt, rec, step, ks, modes, kw, generate, ReplayDrafter, ModelDrafter):
+    """--sampled: the plain sampled run, then per k and mode a greedy verify and a sampled verify generation taken in turn"""
+    import torch
+    tau, top_k, top_p = a.sampled.split(",")
+    smp = dict(do_sample=True, temperature=float(tau), top_k=int(top_k), top_p=float(top_p), sample_seed=0)
+    B = prompt.shape[0]
+    sched = model._lia_scheduler
+    generate(model, prompt, max_new_tokens=a.new, max_steps=2, **smp, **kw)
+    runs = [generate(model, prompt, max_new_tokens=a.new, **smp, **kw) for _ in range(a.reps)]
+    srec = runs[-1][0]
+    meds = [statistics.median(lat[1:]) for _, lat in runs]
+    sstep = statistics.median([v for _, lat in runs for v in lat[1:]])
+    print(f"  plain sampled (tau {tau}, top-k {top_k}, top-p {top_p}): decode step {1e3 * sstep:8.2f} ms (generations' medians "
+          f"{1e3 * min(meds):.2f} .. {1e3 * max(meds):.2f}; plain greedy {1e3 * step:.2f}), {B / sstep:8.2f} tokens/s", flush=True)
+    seen = []                                          # the p_draft of every sampled verify pass
+    ver, ver_rows = sched.verify, sched.verify_rows
+
+    def verify(*args, **k2):
+        out = ver(*args, **k2)
+        if k2.get("sampler") is not None:
+            seen.append(out[0].p_draft)
+        return out
+
+    def verify_rows(*args, **k2):
+        out = ver_rows(*args, **k2)
+        if k2.get("sampler") is not None:
+            seen.append(out.p_draft)
+        return out
+    sched.verify, sched.verify_rows = verify, verify_rows
+
+    def line(what, k, m, gens, plain_ids):
+        every = [v for sl, _, _, _ in gens for v in sl[1:]]
+        gm = [statistics.median(sl[1:]) for sl, _, _, _ in gens]
+        slat, log, out, pd = gens[-1]
+        left = (out != plain_ids).any(dim=1)
+        first = int((out != plain_ids).int().argmax(dim=1)[left].min()) - prompt.shape[1] if bool(left.any()) else None
+        acc1 = [x >= 1 for _, acc in log for x in acc]
+        print(f"  k {k} {m:6s} {what:22s}: verify pass {1e3 * statistics.median(every):8.2f} ms (generations' medians {1e3 * min(gm):.2f} .. "
+              f"{1e3 * max(gm):.2f}; {statistics.median(every) / sstep:5.2f} x a sampled step), {len(slat) - 1:3d} passes, "
+              f"{B * (a.new - 1) / sum(slat[1:]):8.2f} tokens/s ({sstep * (a.new - 1) / sum(slat[1:]):5.2f} x plain sampled), kept per round "
+              f"{[lo for lo, _ in log]}" + (f", first draft token accepted {sum(acc1) / len(acc1):.3f} of {len(acc1)} (round, row) pairs, mean p_draft "
+              f"{sum(pd) / len(pd):.3f}" if pd else "") + (f", rows that left the plain ids {int(left.sum())} of {B}"
+              + (f" (first at step {first})" if first is not None else "")), flush=True)
+
+    drafters = [("replay", lambda ids: ReplayDrafter(ids))]
+    if a.draft != "none":
+        _, dmodel = build(a.draft, ModelDrafter.FLAGS)
+        drafters.append((a.draft + " greedy", lambda ids: ModelDrafter(dmodel)))
+        if a.coupled:
+            drafters.append((a.draft + " coupled", lambda ids: ModelDrafter(dmodel, coupled=True)))
+    for k in ks:
+        for m in modes:
+            extra = {} if m == "common" else {"acceptance": "row"}
+            for name, make in drafters:
+                greedy, sampled = [], []
+                for rep_ in range(a.reps):
+                    if name == "replay":               # the parent route: a greedy verify of the greedy recording, untouched code
+                        log = []
+                        out, slat = generate(model, prompt, max_new_tokens=a.new, draft=make(rec), draft_tokens=k, spec_log=log, **extra, **kw)
+                        greedy.append((slat, log, out, []))
+                    log = []
+                    del seen[:]
+                    out, slat = generate(model, prompt, max_new_tokens=a.new, draft=make(srec), draft_tokens=k, spec_log=log, sampled_verify=True,
+                                         **extra, **smp, **kw)
+                    sampled.append((slat, log, out, [float(p[:, 0].mean()) for p in seen]))
+                if greedy:
+                    line("greedy verify, " + name, k, m, greedy, rec[:, :prompt.shape[1] + a.new])
+                line("sampled verify, " + name, k, m, sampled, srec)
+    sched.verify, sched.verify_rows = ver, ver_rows
+    if a.draft != "none":
+        dmodel._lia_scheduler.close()
+        dmodel.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True, choices=sorted(CONFIGS))
@@ -99,7 +184,11 @@ def main():
     ap.add_argument("--acceptance", type=str, default="common", help="common | row | common,row (row: policies 3 / 3 only)")
     ap.add_argument("--reps", type=int, default=2, help="with --acceptance common,row: generations per k and mode, taken in turn")
     ap.add_argument("--pool", type=int, default=16, help="candidate prompts the batch is chosen from (0: take the first --batch)")
+    ap.add_argument("--sampled", type=str, default=None, help="tau,top_k,top_p: sampled verification beside plain sampling and the greedy verify")
+    ap.add_argument("--coupled", action="store_true", help="with --sampled and --draft: also a ModelDrafter that draws with the target's uniforms")
     a = ap.parse_args()
+    if a.coupled and not a.sampled:
+        ap.error("--coupled needs --sampled")
     import torch
     from lia_amd.generation import generate
     from lia_amd.speculative import ModelDrafter, ReplayDrafter
@@ -131,6 +220,11 @@ def main():
     step = statistics.median(lat[1:])
     print(f"  plain greedy: prefill {1e3 * lat[0]:9.1f} ms, decode step {1e3 * step:8.2f} ms (median of {len(lat) - 1}), {B / step:8.2f} tokens/s", flush=True)
     modes = a.acceptance.split(",")
+    if a.sampled:
+        sampled_ab(a, model, prompt, rec, step, ks, modes, kw, generate, ReplayDrafter, ModelDrafter)
+        model._lia_scheduler.close()
+        model.close()
+        return
     if modes != ["common"]:
         rows_ab(a, model, prompt, rec, plain, step, ks, modes, kw, generate, ReplayDrafter)
         if a.draft != "none":
