@@ -323,6 +323,52 @@ int lia_llama_lm_verify_sample(lia_ctx* ctx, const lia_bf16* hidden, long ldh, i
                                const int32_t* active, int64_t* sampled, int32_t* accepted, int32_t* common, int64_t* next,
                                float* p_draft, lia_bf16* logits_out, void* stream);
 
+/* ---- rejection verification ("Rejection verification"): the verify head for a STOCHASTIC drafter -- the rule of
+ * Leviathan et al.  The drafter drew the draft token x = block_ids[b, t + 1] from Q_t, lia_sample's filtered distribution of its own
+ * bf16 logits draft_logits[b * ldd_row + t * ldd_pos + i] (t < T - 1) under the target's settings and the target's suppress rule;
+ * P_t is the filtered distribution of this pass's logits behind block position t.  Per chunk (lia_lm_score's CHUNK RULE and
+ * workspace), for block row b at position t, with s = step0 + t:
+ *   p_tok[b, t] = P_t(x), q_tok[b, t] = Q_t(x): kept weight over kept mass, 0 where x is not kept; both 0 at t = T - 1
+ *   ok[b, t]    = s < n_steps  and  q_tok > 0  and  u_acc[s * ldu + b] * q_tok < p_tok;   0 at t = T - 1.  A position with s >= n_steps
+ *                 reads neither table (u = 0) and is rejected: its token lies beyond the generation's last step
+ *   resid_mass[b, t] = R = sum_i r_i,  r_i = max(P_t(i) - Q_t(i), 0);  0 at t = T - 1
+ *   token[b, t] = t < T - 1 and R > 0: the smallest id whose running residual mass in id order exceeds u_res[s * ldu + b] * R, else
+ *                 the last id with r_i > 0 -- what the round emits if t is its first rejected position;
+ *                 t = T - 1 (the bonus token) or R = 0 (P_t = Q_t): lia_sample's id for P_t's row and u_res[s * ldu + b] -- the same
+ *                 device function, the same bits
+ * then  accepted[b] = the first t with ok[b, t] = 0 (T - 1 where active[b] = 0),  common = min_b accepted[b],
+ *       next[b] = accepted[b] > common ? block_ids[b, common + 1] : token[b, common]
+ * (a row that accepted the draft token behind `common` keeps it: it is a valid sample).  The emitted tokens are an exact sample of the
+ * target's filtered distribution but NOT the ids plain sampling would draw from the same seed.
+ * p_tok / q_tok / resid_mass: fp32 [B, T], device, each or NULL.  logits_out as in lia_lm_verify_sample.  Common mode only.
+ * LIA_ERR_INVALID, by name: lia_lm_verify_sample's refusals for the shapes, the suppress arguments and the settings; a NULL
+ * rejector, draft_logits, u_acc, u_res, token or ok; ldd_row or ldd_pos < vocab; with vocab % 8 == 0 (rows read 16 bytes at a time) a
+ * draft_logits that is not 16-byte aligned or a pitch that is no multiple of 8; a non-NULL n_suppress_rows.  LIA_ERR_MEMORY as
+ * lia_lm_score. */
+typedef struct {
+  float temperature;
+  int top_k;
+  float top_p;
+  const float* u_acc;           /* device fp32 [n_steps, ldu], [step, row] */
+  const float* u_res;           /* the same shape */
+  long ldu;
+  int n_steps;
+  int step0;
+  const lia_bf16* draft_logits; /* device bf16, row b position t at b * ldd_row + t * ldd_pos */
+  long ldd_row;
+  long ldd_pos;
+} lia_block_rejector;
+int lia_lm_verify_reject(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* lnw, const lia_bf16* lnb,
+                         const lia_bf16* emb, int vocab, float eps, int suppress_token, int n_suppress, const int32_t* n_suppress_rows,
+                         const lia_block_rejector* rejector, const int64_t* block_ids, const int32_t* active, int64_t* token, int32_t* ok,
+                         int32_t* accepted, int32_t* common, int64_t* next, float* p_tok, float* q_tok, float* resid_mass,
+                         lia_bf16* logits_out, void* stream);
+int lia_llama_lm_verify_reject(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* normw,
+                               const lia_bf16* lm, int vocab, float eps, int suppress_token, int n_suppress,
+                               const int32_t* n_suppress_rows, const lia_block_rejector* rejector, const int64_t* block_ids,
+                               const int32_t* active, int64_t* token, int32_t* ok, int32_t* accepted, int32_t* common, int64_t* next,
+                               float* p_tok, float* q_tok, float* resid_mass, lia_bf16* logits_out, void* stream);
+
 /* ---- Llama-family layer (BASELINE.json config 4; build-defined: the reference's LlamaDecoderLayer_forward,
  * decoder.py:121-169, has no policy plumbing -- SURVEY.md quirk 3).  Arithmetic = HF transformers' eager bf16 Llama.
  * weights[9]: 0 input_norm.w  1 q.w [h*d,H]  2 k.w [kvh*d,H]  3 v.w  4 o.w [H,h*d]  5 post_norm.w  6 gate.w [F,H]

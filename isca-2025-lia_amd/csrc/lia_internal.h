@@ -44,6 +44,12 @@ extern "C" void lia_verify_sample_launch(const bf16_t* logits, long ld, int n, i
                                          int n_suppress, const int* n_suppress_rows, int T, int r0, const float* uniforms, long ldu,
                                          int n_steps, int step0, const int* step_rows, const int64_t* block_ids, int64_t* sampled,
                                          float* p_draft, hipStream_t st);
+extern "C" void lia_verify_reject_launch(const bf16_t* logits, long ld, int n, int vocab, const bf16_t* draft_logits, long ldd_row,
+                                         long ldd_pos, float tau, int top_k, float top_p, int suppress, int n_suppress, int T, int r0,
+                                         const float* u_acc, const float* u_res, long ldu, int n_steps, int step0, const int64_t* block_ids,
+                                         int64_t* token, int* ok, float* p_tok, float* q_tok, float* resid_mass, hipStream_t st);
+extern "C" void lia_verify_reject_accept_launch(const int64_t* block_ids, const int64_t* token, const int* ok, const int* active, int B, int T,
+                                                int* accepted, int* common, int64_t* next, hipStream_t st);
 extern "C" void lia_token_logprobs_launch(const bf16_t* logits, long ld, int M, int vocab, const int64_t* targets, float* logprobs,
                                           int64_t* greedy, hipStream_t st);
 extern "C" void lia_verify_argmax_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress, int T, int r0,

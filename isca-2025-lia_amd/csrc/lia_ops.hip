@@ -457,3 +457,82 @@ extern "C" int lia_llama_lm_verify_sample(lia_ctx* ctx, const lia_bf16* hidden, 
                                n_suppress, n_suppress_rows, sampler, block_ids, active, sampled, accepted, common, next, p_draft,
                                logits_out, (hipStream_t)stream);
 }
+
+// ------------------------------------------------------------------------------------------------
+// rejection verification: lm_verify_sample_impl's chunks with lia_verify_reject_kernel (the accept test and the residual draw of a
+// stochastic drafter's block, lia_sample.hip), then the acceptance kernel on its ok / token
+// ------------------------------------------------------------------------------------------------
+static int lm_verify_reject_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int B, int T, int H, const bf16_t* norm_w,
+                                 const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, int suppress_token, int n_suppress,
+                                 const int32_t* n_suppress_rows, const lia_block_rejector* rej, const int64_t* block_ids,
+                                 const int32_t* active, int64_t* token, int32_t* ok, int32_t* accepted, int32_t* common, int64_t* next,
+                                 float* p_tok, float* q_tok, float* resid_mass, bf16_t* logits_out, hipStream_t st) {
+  if (!rej) { lia_set_error("%s: NULL rejector", who); return LIA_ERR_INVALID; }
+  if (!rej->draft_logits) { lia_set_error("%s: NULL draft_logits", who); return LIA_ERR_INVALID; }
+  if (!rej->u_acc) { lia_set_error("%s: NULL u_acc", who); return LIA_ERR_INVALID; }
+  if (!rej->u_res) { lia_set_error("%s: NULL u_res", who); return LIA_ERR_INVALID; }
+  if (n_suppress_rows) { lia_set_error("%s: n_suppress_rows must be NULL (rejection verification is common mode only)", who); return LIA_ERR_INVALID; }
+  if (B <= 0) { lia_set_error("%s: B=%d must be >= 1", who, B); return LIA_ERR_INVALID; }
+  if (T < 2) { lia_set_error("%s: T=%d must be >= 2 (the pending token and at least one draft token)", who, T); return LIA_ERR_INVALID; }
+  if ((long)B * T > 0x7fffffffL) { lia_set_error("%s: B=%d x T=%d rows", who, B, T); return LIA_ERR_INVALID; }
+  if (n_suppress < 0 || n_suppress > T) { lia_set_error("%s: n_suppress=%d must be in [0, T=%d]", who, n_suppress, T); return LIA_ERR_INVALID; }
+  if (suppress_token < -1 || (vocab > 0 && suppress_token >= vocab)) { lia_set_error("%s: suppress_token=%d must be -1 or in [0, vocab)", who, suppress_token); return LIA_ERR_INVALID; }
+  if (vocab > LIA_SAMPLE_MAX_VOCAB) { lia_set_error("%s: vocab=%d must be in [1, %d]", who, vocab, LIA_SAMPLE_MAX_VOCAB); return LIA_ERR_INVALID; }
+  if (sample_settings_invalid(who, rej->temperature, rej->top_k, rej->top_p)) return LIA_ERR_INVALID;
+  if (rej->ldu < B) { lia_set_error("%s: ldu=%ld < B=%d", who, rej->ldu, B); return LIA_ERR_INVALID; }
+  if (rej->n_steps < 1) { lia_set_error("%s: n_steps=%d must be >= 1", who, rej->n_steps); return LIA_ERR_INVALID; }
+  if (rej->step0 < 0) { lia_set_error("%s: step0=%d must be >= 0", who, rej->step0); return LIA_ERR_INVALID; }
+  if (rej->ldd_row < vocab) { lia_set_error("%s: ldd_row=%ld < vocab=%d", who, rej->ldd_row, vocab); return LIA_ERR_INVALID; }
+  if (rej->ldd_pos < vocab) { lia_set_error("%s: ldd_pos=%ld < vocab=%d", who, rej->ldd_pos, vocab); return LIA_ERR_INVALID; }
+  if (vocab % 8 == 0 && (((uintptr_t)rej->draft_logits & 15) || rej->ldd_row % 8 || rej->ldd_pos % 8)) {
+    lia_set_error("%s: draft_logits=%p ldd_row=%ld ldd_pos=%ld: with vocab %% 8 == 0 the rows are read 16 bytes at a time -- a 16-byte "
+                  "aligned pointer and pitches that are multiples of 8", who, (const void*)rej->draft_logits, rej->ldd_row, rej->ldd_pos);
+    return LIA_ERR_INVALID;
+  }
+  hipError_t copy_err = hipSuccess;
+  const int rc = lm_rows_chunked(who, ctx, hidden, ldh, B * T, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
+    lia_verify_reject_launch(logits, vocab, n, vocab, (const bf16_t*)rej->draft_logits, rej->ldd_row, rej->ldd_pos, rej->temperature, rej->top_k,
+                             rej->top_p, suppress_token, n_suppress, T, r0, rej->u_acc, rej->u_res, rej->ldu, rej->n_steps, rej->step0,
+                             block_ids, token, ok, p_tok, q_tok, resid_mass, st);
+    if (logits_out && copy_err == hipSuccess)
+      copy_err = hipMemcpyAsync(logits_out + (size_t)r0 * vocab, logits, (size_t)n * vocab * sizeof(bf16_t), hipMemcpyDeviceToDevice, st);
+  });
+  if (rc) return rc;
+  HIP_TRY(copy_err);
+  lia_verify_reject_accept_launch(block_ids, token, ok, active, B, T, accepted, common, next, st);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+#define LIA_VERIFY_REJECT_NULL(who, ...)                                                      \
+  do {                                                                                        \
+    const void* const ptrs[] = {__VA_ARGS__};                                                 \
+    static const char* const names[] = {"hidden", "norm weight", "lm_head weight", "block_ids", "token", "ok", "accepted", "common", "next"}; \
+    for (int i = 0; i < 9; ++i)                                                               \
+      if (!ptrs[i]) { lia_set_error("%s: NULL %s", who, names[i]); return LIA_ERR_INVALID; }  \
+  } while (0)
+
+extern "C" int lia_lm_verify_reject(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* lnw,
+                                    const lia_bf16* lnb, const lia_bf16* emb, int vocab, float eps, int suppress_token, int n_suppress,
+                                    const int32_t* n_suppress_rows, const lia_block_rejector* rejector, const int64_t* block_ids,
+                                    const int32_t* active, int64_t* token, int32_t* ok, int32_t* accepted, int32_t* common, int64_t* next,
+                                    float* p_tok, float* q_tok, float* resid_mass, lia_bf16* logits_out, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  LIA_VERIFY_REJECT_NULL("lia_lm_verify_reject", hidden, lnw, emb, block_ids, token, ok, accepted, common, next);
+  if (!lnb) { lia_set_error("lia_lm_verify_reject: NULL norm bias"); return LIA_ERR_INVALID; }
+  return lm_verify_reject_impl("lia_lm_verify_reject", ctx, hidden, ldh, B, T, H, lnw, lnb, emb, vocab, eps, suppress_token, n_suppress,
+                               n_suppress_rows, rejector, block_ids, active, token, ok, accepted, common, next, p_tok, q_tok, resid_mass,
+                               logits_out, (hipStream_t)stream);
+}
+
+extern "C" int lia_llama_lm_verify_reject(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* normw,
+                                          const lia_bf16* lm, int vocab, float eps, int suppress_token, int n_suppress,
+                                          const int32_t* n_suppress_rows, const lia_block_rejector* rejector, const int64_t* block_ids,
+                                          const int32_t* active, int64_t* token, int32_t* ok, int32_t* accepted, int32_t* common,
+                                          int64_t* next, float* p_tok, float* q_tok, float* resid_mass, lia_bf16* logits_out, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  LIA_VERIFY_REJECT_NULL("lia_llama_lm_verify_reject", hidden, normw, lm, block_ids, token, ok, accepted, common, next);
+  return lm_verify_reject_impl("lia_llama_lm_verify_reject", ctx, hidden, ldh, B, T, H, normw, nullptr, lm, vocab, eps, suppress_token,
+                               n_suppress, n_suppress_rows, rejector, block_ids, active, token, ok, accepted, common, next, p_tok, q_tok,
+                               resid_mass, logits_out, (hipStream_t)stream);
+}

@@ -98,33 +98,34 @@ template <typename T> __device__ __forceinline__ void find_boundary_bin(const T*
   __syncthreads();
 }
 
+// The row passes' LDS, shared by every kernel of this file (each is one row workgroup running the passes one after the other)
+__shared__ uint64_t hist[SMP_BINS];            // pass A: uint32 counts (the first half), pass C: uint64 masses
+__shared__ uint64_t nib[16];                   // passes B / D: the 16 low-nibble bins of the boundary bin
+__shared__ uint64_t red64[LIA_ROW_WAVES];
+__shared__ uint32_t red32[LIA_ROW_WAVES];
+__shared__ float redf[LIA_ROW_WAVES];
+__shared__ float carry_of[SMP_MAX_TILES + 1];  // pass E: running sum before tile j
+__shared__ int sh_bin, sh_key[2], sh_pick;
+__shared__ uint32_t sh_above32;
+__shared__ uint64_t sh_above64;
+__shared__ float sh_wd;                        // DRAFT: the draft token's kept weight
+
 // What one row's draw leaves behind for the caller (the same values in every thread; the kernels use thread 0's): the id,
 // lia_sample's four stats, and -- DRAFT only -- the kept weight exp(s - m) of the draft token (0 where it is not kept)
 struct SmpRow { int pick; float t_k, v_p, nkept, W2, w_draft; };
 
-// Passes A - E over one row by the whole LIA_ROW_THREADS workgroup: the one function lia_sample_kernel and lia_verify_sample_kernel
-// both draw with, so that a verify pass's token IS lia_sample's of the same logits and u.  u must be workgroup-uniform.  DRAFT: the
-// thread that meets token `draft` in pass E also leaves its kept weight (no further pass over the row).
-template <bool DRAFT>
-__device__ __forceinline__ SmpRow sample_row(const bf16_t* __restrict__ row, int vocab, bool vec, float tau, int top_k, float top_p,
-                                             int suppress, float u, int draft) {
-  __shared__ uint64_t hist[SMP_BINS];            // pass A: uint32 counts (the first half), pass C: uint64 masses
-  __shared__ uint64_t nib[16];                   // passes B / D: the 16 low-nibble bins of the boundary bin
-  __shared__ uint64_t red64[LIA_ROW_WAVES];
-  __shared__ uint32_t red32[LIA_ROW_WAVES];
-  __shared__ float redf[LIA_ROW_WAVES];
-  __shared__ float carry_of[SMP_MAX_TILES + 1];  // pass E: running sum before tile j
-  __shared__ int sh_bin, sh_key[2], sh_pick;
-  __shared__ uint32_t sh_above32;
-  __shared__ uint64_t sh_above64;
-  __shared__ float sh_wd;                        // DRAFT: the draft token's kept weight
+// Passes A - D over one row by the whole LIA_ROW_THREADS workgroup: the row's kept set K2 = {key >= kap2} and the score m of its maximum
+// (the weight of a kept token is exp(s - m)), the same values in every thread.  t_k / v_p: lia_sample's boundary stats.
+struct SmpFilt { int kap2; float m, t_k, v_p; };
+
+__device__ __forceinline__ SmpFilt filter_row(const bf16_t* __restrict__ row, int vocab, bool vec, float tau, int top_k, float top_p,
+                                              int suppress) {
   uint32_t* cnt = (uint32_t*)hist;
 
   const int tid = threadIdx.x;
   const bool topk_on = top_k > 0 && top_k < vocab;
   const bool topp_on = top_p < 1.0f;
 
-  if (DRAFT && tid == 0) sh_wd = 0.f;              // (pass A's barrier orders it before the owner's store in pass E)
   // ---- pass A: the maximum key; with top-k on, counts per top-12 bin ----
   if (topk_on)
     for (int b = tid; b < SMP_BINS / 2; b += LIA_ROW_THREADS) hist[b] = 0;
@@ -236,6 +237,26 @@ __device__ __forceinline__ SmpRow sample_row(const bf16_t* __restrict__ row, int
     kap2 = max(kap1, sh_key[0]);
     v_p = score_of_key(sh_key[1], tau);
   }
+
+  SmpFilt f;
+  f.kap2 = kap2;
+  f.m = m;
+  f.t_k = t_k;
+  f.v_p = v_p;
+  return f;
+}
+
+// Passes A - E over one row by the whole LIA_ROW_THREADS workgroup: the one function lia_sample_kernel and lia_verify_sample_kernel
+// both draw with, so that a verify pass's token IS lia_sample's of the same logits and u.  u must be workgroup-uniform.  DRAFT: the
+// thread that meets token `draft` in pass E also leaves its kept weight (no further pass over the row).
+template <bool DRAFT>
+__device__ __forceinline__ SmpRow sample_row(const bf16_t* __restrict__ row, int vocab, bool vec, float tau, int top_k, float top_p,
+                                             int suppress, float u, int draft) {
+  const int tid = threadIdx.x;
+  if (DRAFT && tid == 0) sh_wd = 0.f;              // (pass A's barrier orders it before the owner's store in pass E)
+  const SmpFilt f = filter_row(row, vocab, vec, tau, top_k, top_p, suppress);
+  const int kap2 = f.kap2;
+  const float m = f.m, t_k = f.t_k, v_p = f.v_p;
 
   // ---- pass E: running sums of the kept weights in token order, one carry per tile ----
   const int ntiles = (vocab + SMP_TILE - 1) / SMP_TILE;
@@ -377,6 +398,189 @@ __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_verify_sample_kernel(cons
   }
 }
 
+// ---- rejection verification ("Rejection verification") ------------------------------------------------------
+// the probabilities of tokens i .. i + 7 under a filtered row: kept weight over kept mass, 0 for a token that is not kept (or past
+// the end of the row)
+__device__ __forceinline__ void load_probs8(const bf16_t* __restrict__ row, int i, int vocab, bool vec, int suppress, float tau, int kap2,
+                                            float m, float W, float p[8]) {
+  int k[8];
+  load_keys8(row, i, vocab, vec, suppress, k);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) p[e] = k[e] >= kap2 ? expf(score_of_key(k[e], tau) - m) / W : 0.f;
+}
+
+// Chunk row r = r0 + blockIdx.x is block row b = r / T at position t = r % T.  At t < T - 1 the draft token x = block_ids[b, t + 1]
+// was drawn from Q_t, the filtered distribution of draft_logits[b, t, :] (the target's settings, the same suppress rule); P_t is that
+// of this pass's logits row.  Passes A - D run on the target row, then on the draft row (the same LDS); one pass over both rows sums
+// their kept weights (a fixed-order reduction: W_p, W_q); one more, in pass E's tiling, the running residual r_i = max(P_t(i) -
+// Q_t(i), 0) in token order -- the thread that meets x leaves P_t(x) and Q_t(x) -- and the tile where the running sum passes
+// U_res[s, b] * R is walked again for the token (else the last id with r_i > 0).  ok = (Q_t(x) > 0 and U_acc[s, b] * Q_t(x) < P_t(x))
+// at step s = step0 + t; a position with s >= n_steps reads no table entry and is rejected.  R == 0 (P_t <= Q_t everywhere: P_t = Q_t)
+// and t = T - 1 (the bonus token) take the plain draw of P_t with U_res[s, b]: sample_row, lia_sample's own function.
+__global__ __launch_bounds__(LIA_ROW_THREADS) void lia_verify_reject_kernel(
+    const bf16_t* __restrict__ logits, long ld, int vocab, int vec, const bf16_t* __restrict__ draft_logits, long ldd_row, long ldd_pos,
+    int vecd, float tau, int top_k, float top_p, int suppress, int n_suppress, int T, int r0, const float* __restrict__ u_acc,
+    const float* __restrict__ u_res, long ldu, int n_steps, int step0, const int64_t* __restrict__ block_ids, int64_t* __restrict__ token,
+    int* __restrict__ ok, float* __restrict__ p_tok, float* __restrict__ q_tok, float* __restrict__ resid_mass) {
+  __shared__ float sh_px, sh_qx;
+  const int tid = threadIdx.x;
+  const int r = r0 + (int)blockIdx.x;
+  const int b = r / T, t = r % T;
+  const int sup = t < n_suppress ? suppress : -1;
+  const long s = (long)step0 + t;
+  const bool inside = s >= 0 && s < n_steps;
+  float ua = 0.f, ur = 0.f;
+  if (inside) {
+    ua = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(u_acc[s * ldu + b])));
+    ur = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(u_res[s * ldu + b])));
+  }
+  const bf16_t* prow = logits + (long)blockIdx.x * ld;
+  bool plain = t == T - 1;
+  int pick = 0, accept = 0;
+  float px = 0.f, qx = 0.f, R = 0.f;
+  if (!plain) {
+    const bf16_t* qrow = draft_logits + (long)b * ldd_row + (long)t * ldd_pos;
+    const int64_t d = block_ids[(long)r + 1];
+    const int x = d >= 0 && d < (int64_t)vocab ? (int)d : -1;
+    if (tid == 0) { sh_px = 0.f; sh_qx = 0.f; }
+    const SmpFilt fp = filter_row(prow, vocab, vec, tau, top_k, top_p, sup);
+    __syncthreads();                      // (the draft row's passes reuse the LDS the target row's last reads came from)
+    const SmpFilt fq = filter_row(qrow, vocab, vecd, tau, top_k, top_p, sup);
+    // ---- the kept masses: per-thread sums in token order, then the waves in order ----
+    float wp = 0.f, wq = 0.f;
+    for (int i = tid * 8; i < vocab; i += SMP_TILE) {
+      int kp[8], kq[8];
+      load_keys8(prow, i, vocab, vec, sup, kp);
+      load_keys8(qrow, i, vocab, vecd, sup, kq);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (kp[e] >= fp.kap2) wp += expf(score_of_key(kp[e], tau) - fp.m);
+        if (kq[e] >= fq.kap2) wq += expf(score_of_key(kq[e], tau) - fq.m);
+      }
+    }
+    float Wp, Wq;
+    (void)block_excl_scan<float>(wp, redf, &Wp);
+    (void)block_excl_scan<float>(wq, redf, &Wq);
+    // ---- the running residual in token order, one carry per tile ----
+    const int ntiles = (vocab + SMP_TILE - 1) / SMP_TILE;
+    float carry = 0.f;
+    int last = -1;
+    for (int j = 0; j < ntiles; ++j) {
+      const int i = j * SMP_TILE + tid * 8;
+      float pv[8], qv[8], rs = 0.f;
+      load_probs8(prow, i, vocab, vec, sup, tau, fp.kap2, fp.m, Wp, pv);
+      load_probs8(qrow, i, vocab, vecd, sup, tau, fq.kap2, fq.m, Wq, qv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float re = fmaxf(pv[e] - qv[e], 0.f);
+        rs += re;
+        if (re > 0.f) last = i + e;
+        if (i + e == x) { sh_px = pv[e]; sh_qx = qv[e]; }
+      }
+      const float ex = block_excl_scan<float>(rs, redf, (float*)nullptr);
+      if (tid == LIA_ROW_THREADS - 1) {
+        carry_of[j] = carry;
+        redf[0] = ex + rs;              // the tile's total as the walk below computes it at the tile's last token
+      }
+      __syncthreads();
+      carry = carry + redf[0];
+      __syncthreads();
+    }
+    if (tid == 0) carry_of[ntiles] = carry;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+    if ((tid & 63) == 0) red32[tid >> 6] = (uint32_t)last;
+    if (tid == 0) sh_pick = 0x7fffffff;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < LIA_ROW_WAVES; ++w) last = max(last, (int)red32[w]);
+    px = sh_px;
+    qx = sh_qx;
+    R = carry;
+    accept = inside && qx > 0.f && ua * qx < px;
+    const float thr = ur * R;
+    int jc = -1;                        // the first tile whose running sum passes thr
+    for (int j = 0; j < ntiles; ++j)
+      if (carry_of[j + 1] > thr) { jc = j; break; }
+    __syncthreads();                    // (red32 is reused below)
+    if (jc >= 0) {
+      // walk tile jc again: the same sums in the same order, then the first token with r_i > 0 whose running sum passes thr
+      const int i = jc * SMP_TILE + tid * 8;
+      float pv[8], qv[8], rv[8], rs = 0.f;
+      load_probs8(prow, i, vocab, vec, sup, tau, fp.kap2, fp.m, Wp, pv);
+      load_probs8(qrow, i, vocab, vecd, sup, tau, fq.kap2, fq.m, Wq, qv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        rv[e] = fmaxf(pv[e] - qv[e], 0.f);
+        rs += rv[e];
+      }
+      const float ex = block_excl_scan<float>(rs, redf, (float*)nullptr);
+      const float c0 = carry_of[jc];
+      float q = 0.f;
+      int pk = 0x7fffffff, lastc = -1;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        q += rv[e];
+        if (rv[e] > 0.f) {
+          lastc = i + e;
+          if (pk == 0x7fffffff && c0 + (ex + q) > thr) pk = i + e;
+        }
+      }
+      if (pk != 0x7fffffff) atomicMin(&sh_pick, pk);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) lastc = max(lastc, __shfl_xor(lastc, o, 64));
+      if ((tid & 63) == 0) red32[tid >> 6] = (uint32_t)lastc;
+      __syncthreads();
+      if (tid == 0 && sh_pick == 0x7fffffff) {
+        int lc = -1;
+        for (int w = 0; w < LIA_ROW_WAVES; ++w) lc = max(lc, (int)red32[w]);
+        sh_pick = lc;
+      }
+      __syncthreads();
+    }
+    pick = jc >= 0 ? sh_pick : last;
+    if (pick < 0 || pick >= vocab) pick = last >= 0 ? last : 0;
+    plain = !(R > 0.f);
+    __syncthreads();                    // (the plain draw below reuses every LDS word read above)
+  }
+  if (plain) pick = sample_row<false>(prow, vocab, vec, tau, top_k, top_p, sup, ur, -1).pick;
+  if (tid == 0) {
+    token[r] = pick;
+    ok[r] = accept;
+    if (p_tok) p_tok[r] = px;
+    if (q_tok) q_tok[r] = qx;
+    if (resid_mass) resid_mass[r] = R;
+  }
+}
+
+// one workgroup: accepted[b] = the first position whose draft token was rejected (T - 1: none, or an inactive row), common = their
+// minimum, next[b] = the draft token behind position `common` where row b accepted it, else the token the head computed there
+__global__ __launch_bounds__(256) void lia_verify_reject_accept_kernel(const int64_t* __restrict__ block_ids, const int64_t* __restrict__ token,
+                                                                       const int* __restrict__ ok, const int* __restrict__ active, int B, int T,
+                                                                       int* __restrict__ accepted, int* __restrict__ common,
+                                                                       int64_t* __restrict__ next) {
+  __shared__ int smin[4];
+  const int tid = threadIdx.x;
+  int lo = T - 1;
+  for (int b = tid; b < B; b += 256) {
+    int a = T - 1;
+    if (!active || active[b]) {
+      a = 0;
+      while (a < T - 1 && ok[(long)b * T + a]) ++a;
+    }
+    accepted[b] = a;
+    lo = min(lo, a);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) lo = min(lo, __shfl_xor(lo, o, 64));
+  if ((tid & 63) == 0) smin[tid >> 6] = lo;
+  __syncthreads();
+  lo = min(min(smin[0], smin[1]), min(smin[2], smin[3]));
+  if (tid == 0) common[0] = lo;
+  // (each thread reads back the accepted[] entries it wrote itself)
+  for (int b = tid; b < B; b += 256) next[b] = accepted[b] > lo ? block_ids[(long)b * T + lo + 1] : token[(long)b * T + lo];
+}
+
 extern "C" void lia_sample_launch(const bf16_t* logits, long ld, int B, int vocab, float tau, int top_k, float top_p, int suppress,
                                   const float* uniforms, int64_t* out, float* stats, hipStream_t st) {
   if (B <= 0) return;
@@ -393,4 +597,22 @@ extern "C" void lia_verify_sample_launch(const bf16_t* logits, long ld, int n, i
   const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
   hipLaunchKernelGGL(lia_verify_sample_kernel, dim3(n), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, tau, top_k, top_p, suppress,
                      n_suppress, n_suppress_rows, T, r0, uniforms, ldu, n_steps, step0, step_rows, block_ids, sampled, p_draft);
+}
+
+extern "C" void lia_verify_reject_launch(const bf16_t* logits, long ld, int n, int vocab, const bf16_t* draft_logits, long ldd_row,
+                                         long ldd_pos, float tau, int top_k, float top_p, int suppress, int n_suppress, int T, int r0,
+                                         const float* u_acc, const float* u_res, long ldu, int n_steps, int step0, const int64_t* block_ids,
+                                         int64_t* token, int* ok, float* p_tok, float* q_tok, float* resid_mass, hipStream_t st) {
+  if (n <= 0) return;
+  const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
+  const int vecd = (ldd_row % 8 == 0) && (ldd_pos % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)draft_logits & 15) == 0);
+  hipLaunchKernelGGL(lia_verify_reject_kernel, dim3(n), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, draft_logits, ldd_row, ldd_pos,
+                     vecd, tau, top_k, top_p, suppress, n_suppress, T, r0, u_acc, u_res, ldu, n_steps, step0, block_ids, token, ok, p_tok,
+                     q_tok, resid_mass);
+}
+
+extern "C" void lia_verify_reject_accept_launch(const int64_t* block_ids, const int64_t* token, const int* ok, const int* active, int B, int T,
+                                                int* accepted, int* common, int64_t* next, hipStream_t st) {
+  if (B <= 0) return;
+  hipLaunchKernelGGL(lia_verify_reject_accept_kernel, dim3(1), dim3(256), 0, st, block_ids, token, ok, active, B, T, accepted, common, next);
 }

@@ -48,6 +48,12 @@ class BlockSampler(ctypes.Structure):
                 ("n_steps", c_int), ("step0", c_int), ("step_rows", c_void_p)]
 
 
+class BlockRejector(ctypes.Structure):
+    """lia_block_rejector: the settings, the U_acc / U_res tables and the drafter's logits of a rejection verify pass"""
+    _fields_ = [("temperature", c_float), ("top_k", c_int), ("top_p", c_float), ("u_acc", c_void_p), ("u_res", c_void_p), ("ldu", c_long),
+                ("n_steps", c_int), ("step0", c_int), ("draft_logits", c_void_p), ("ldd_row", c_long), ("ldd_pos", c_long)]
+
+
 # name -> (restype, argtypes).  Every symbol include/lia_hip.h declares is listed here; the CPU test
 # suite checks the shared object exports all of them.
 SIGNATURES = {
@@ -129,6 +135,12 @@ SIGNATURES = {
     "lia_llama_lm_verify_sample": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_int, c_int,
                                            c_void_p, ctypes.POINTER(BlockSampler), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lia_lm_verify_reject": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_int,
+                                     c_void_p, ctypes.POINTER(BlockRejector), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lia_llama_lm_verify_reject": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_int, c_int,
+                                           c_void_p, ctypes.POINTER(BlockRejector), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lia_embed_padded": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "lia_attention_padded": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_void_p, c_void_p]),

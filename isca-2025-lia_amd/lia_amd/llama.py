@@ -257,10 +257,11 @@ class LlamaScheduler:
         return lp.view(B, T), greedy.view(B, T)
 
     def verify(self, block_ids, kv_state, suppress_token=-1, n_suppress=0, active=None, gpu_percentage=100, num_minibatch=1,
-               pin_weight=True, enable_cxl=False, sampler=None, return_logits=False, **_ignored):
+               pin_weight=True, enable_cxl=False, sampler=None, return_logits=False, rejector=None, **_ignored):
         """Speculative verification: OffloadScheduler.verify for a Llama -- the block [pending | draft] appended at kv_state.len,
         every position through the last layer with the block attention kernel, lia_llama_lm_verify; -> (ops.VerifyResult, common),
-        kv_state.len = pos0 + common + 1.  sampler / return_logits: sampled verification, as OffloadScheduler.verify."""
+        kv_state.len = pos0 + common + 1.  sampler / return_logits / rejector: sampled and rejection verification, as
+        OffloadScheduler.verify."""
         check_verify_block(block_ids, kv_state)
         m, sh = self.model, self.model.shape
         pos0 = kv_state.len
@@ -272,7 +273,10 @@ class LlamaScheduler:
                 self.ctx.set_option(N.LIA_OPT_BLOCK_ATTENTION, 0)
         ids_dev = block_ids.to(device="cuda", dtype=torch.int64).contiguous()
         act_dev = None if active is None else torch.as_tensor(active).to(device="cuda", dtype=torch.int32).contiguous()
-        if sampler is None:
+        if rejector is not None:
+            res = self.ctx.llama_lm_verify_reject(x, m.final_norm_w, m.lm_head, ids_dev, rejector, sh.rms_eps, suppress_token, n_suppress,
+                                                  active=act_dev, return_logits=return_logits, return_probs=True)
+        elif sampler is None:
             res = self.ctx.llama_lm_verify(x, m.final_norm_w, m.lm_head, ids_dev, sh.rms_eps, suppress_token, n_suppress, act_dev)
         else:
             res = self.ctx.llama_lm_verify_sample(x, m.final_norm_w, m.lm_head, ids_dev, sampler, sh.rms_eps, suppress_token, n_suppress,

@@ -31,7 +31,10 @@ def _chk(t, dtype=torch.bfloat16):
 # lia_lm_verify's outputs, all on the device: greedy int64 [B, T], accepted int32 [B], common int32 [1], next int64 [B].  On the
 # sampled route (lia_lm_verify_sample) `greedy` holds the SAMPLED ids, p_draft is float32 [B, T] and logits bf16 [B, T, vocab], each
 # where it was asked for.
-VerifyResult = collections.namedtuple("VerifyResult", "greedy accepted common next logits p_draft", defaults=(None, None))
+# On the rejection route (lia_lm_verify_reject) `greedy` holds `token` -- per position the residual draw, the bonus draw at T - 1 -- and
+# ok is int32 [B, T], p_tok / q_tok / resid_mass float32 [B, T] where asked for.
+VerifyResult = collections.namedtuple("VerifyResult", "greedy accepted common next logits p_draft ok p_tok q_tok resid_mass",
+                                      defaults=(None,) * 6)
 
 
 class Context:
@@ -360,6 +363,52 @@ class Context:
         """lia_llama_lm_verify_sample: lm_verify_sample with the final RMSNorm and the untied lm_head of a Llama"""
         return self._verify_sample("lia_llama_lm_verify_sample", (normw,), lm, hidden, block_ids, block, eps, suppress_token, n_suppress,
                                    n_suppress_rows, active, return_logits, return_p_draft, stream)
+
+    def _verify_reject(self, name, norm, head, hidden, block_ids, rej, eps, suppress_token, n_suppress, active, return_logits,
+                       return_probs, stream):
+        for t in norm + (head,):
+            _chk(t)
+        B, T, H, out = self._verify_args(hidden, block_ids, active)
+        dev = hidden.device
+        vocab = head.shape[0]
+        for U, what in ((rej.u_acc, "u_acc"), (rej.u_res, "u_res")):
+            _chk(U, torch.float32)
+            if U.dim() != 2 or tuple(U.shape) != tuple(rej.u_acc.shape):
+                raise ValueError(f"{what} must be a [steps, rows] table of u_acc's shape, got shape {tuple(U.shape)}")
+        dl = rej.draft_logits
+        if dl is None:
+            raise ValueError("the rejector carries no draft_logits: the drafter's logits of this round's k draft steps")
+        if dl.dtype != torch.bfloat16 or not dl.is_cuda or dl.dim() != 3 or dl.stride(2) != 1:
+            raise ValueError(f"draft_logits must be a bf16 CUDA tensor [B, k, vocab] with unit stride along the vocabulary, got {dl.dtype} "
+                             f"{dl.device} shape {tuple(dl.shape)}")
+        if tuple(dl.shape) != (B, T - 1, vocab):
+            raise ValueError(f"draft_logits has shape {tuple(dl.shape)}, the block needs {(B, T - 1, vocab)}")
+        torch.cuda.current_stream().synchronize()              # (the library's stream reads what torch's wrote: the drafter's logits)
+        args = N.BlockRejector(float(rej.temperature), int(rej.top_k), float(rej.top_p), rej.u_acc.data_ptr(), rej.u_res.data_ptr(),
+                               rej.u_acc.stride(0), rej.u_acc.shape[0], int(rej.step0), dl.data_ptr(), dl.stride(0), dl.stride(1))
+        ok = torch.empty((B, T), dtype=torch.int32, device=dev)
+        logits = torch.empty((B, T, vocab), dtype=torch.bfloat16, device=dev) if return_logits else None
+        probs = [torch.empty((B, T), dtype=torch.float32, device=dev) if return_probs else None for _ in range(3)]
+        N.check(getattr(self.lib, name)(self.handle, _ptr(hidden), H, B, T, H, *[_ptr(t) for t in norm], _ptr(head), vocab, eps,
+                                        int(suppress_token), int(n_suppress), None, ctypes.byref(args), _ptr(block_ids), _ptr(active),
+                                        _ptr(out.greedy), _ptr(ok), _ptr(out.accepted), _ptr(out.common), _ptr(out.next), _ptr(probs[0]),
+                                        _ptr(probs[1]), _ptr(probs[2]), _ptr(logits), self._st(stream)), name)
+        return out._replace(logits=logits, ok=ok, p_tok=probs[0], q_tok=probs[1], resid_mass=probs[2])
+
+    def lm_verify_reject(self, hidden, lnw, lnb, emb, block_ids, rejector, eps=1e-5, suppress_token=-1, n_suppress=0, active=None,
+                         return_logits=False, return_probs=False, stream=None):
+        """lia_lm_verify_reject: the verify head for a stochastic drafter (accept x ~ Q with min(1, P(x) / Q(x)), else a draw of the
+        residual).  rejector (sampling.RejectorBlock): the settings, the U_acc / U_res tables, the step origin and the drafter's
+        logits [B, T - 1, vocab] behind block_ids[:, 1:].  -> VerifyResult with `token` as `greedy`, ok, and p_tok / q_tok /
+        resid_mass / logits where asked for.  Common mode only."""
+        return self._verify_reject("lia_lm_verify_reject", (lnw, lnb), emb, hidden, block_ids, rejector, eps, suppress_token, n_suppress,
+                                   active, return_logits, return_probs, stream)
+
+    def llama_lm_verify_reject(self, hidden, normw, lm, block_ids, rejector, eps=1e-5, suppress_token=-1, n_suppress=0, active=None,
+                               return_logits=False, return_probs=False, stream=None):
+        """lia_llama_lm_verify_reject: lm_verify_reject with the final RMSNorm and the untied lm_head of a Llama"""
+        return self._verify_reject("lia_llama_lm_verify_reject", (normw,), lm, hidden, block_ids, rejector, eps, suppress_token, n_suppress,
+                                   active, return_logits, return_probs, stream)
 
     def score_chunk_rows(self, M, H, vocab):
         """rows per chunk lm_score would use for M rows in this context's workspace (0: not even min(M, 256) rows fit)"""

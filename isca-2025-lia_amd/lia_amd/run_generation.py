@@ -138,6 +138,10 @@ def build_parser():
     p.add_argument("--draft-coupled", action="store_true",
                    help="with --sampled-verify: the draft model samples its own logits with the target's settings and uniforms (it guesses "
                         "the draw, not the argmax)")
+    p.add_argument("--verify-rule", default="draw", choices=["draw", "rejection"],
+                   help="with --sampled-verify: draw = accept a draft token iff it equals the sampler's own draw; rejection = the draft model "
+                        "samples its own logits and a token is accepted with probability min(1, p / q), else a draw of the residual "
+                        "(an exact sample, but not the ids of plain --do-sample; common acceptance only, not with --draft-coupled)")
     add_init_args(p)
     return p
 
@@ -149,6 +153,14 @@ def check_spec_sample_flags(args):
     if args.draft_coupled and not args.sampled_verify:
         raise SystemExit("[ERROR] --draft-coupled needs --sampled-verify (with --draft-model and --do-sample): the draft model draws with "
                          "the target's uniforms, which only a sampled verify pass confirms")
+    if getattr(args, "verify_rule", "draw") == "rejection":
+        if not args.sampled_verify:
+            raise SystemExit("[ERROR] --verify-rule rejection needs --sampled-verify (with --draft-model and --do-sample)")
+        if args.draft_coupled:
+            raise SystemExit("[ERROR] --verify-rule rejection together with --draft-coupled: the rejection rule's drafter draws with "
+                             "uniforms of its own")
+        if args.acceptance != "common":
+            raise SystemExit("[ERROR] --verify-rule rejection together with --acceptance row is not supported")
 
 
 def synthetic_prompt(vocab, n_tokens, batch, seed=0):
@@ -368,7 +380,7 @@ def load_draft(args):
     d.pin_weight, d.enable_cxl, d.cpu_layers, d.stream_format = True, False, 0, args.stream_format
     model = load_model(d)
     attach_scheduler(model, d.stream_format or default_stream_format())
-    return ModelDrafter(model, coupled=args.draft_coupled)
+    return ModelDrafter(model, coupled=args.draft_coupled, stochastic=getattr(args, "verify_rule", "draw") == "rejection")
 
 
 def summarize_speculation(spec_log, total_list, batch_size, out=print, acceptance="common"):
@@ -674,6 +686,8 @@ def _main(args, rec=None):
             generate_kwargs.update(acceptance=args.acceptance)
         if args.sampled_verify:
             generate_kwargs.update(sampled_verify=True)
+            if args.verify_rule != "draw":
+                generate_kwargs.update(verify_rule=args.verify_rule)
     tokenizer = load_tokenizer(args.model_id)
     if args.prompt_file is not None:
         input_ids, generate_kwargs["attention_mask"] = prompt_file_inputs(args, model.shape.vocab, tokenizer,

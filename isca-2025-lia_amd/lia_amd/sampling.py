@@ -142,3 +142,45 @@ class SamplerBlock:
             smp.u = u[i]
             out.append(smp)
         return out
+
+
+def draw_reject_tables(max_new_tokens, n_rows, sample_seed=None, device="cuda"):
+    """U_draft, U_acc, U_res of rejection verification, each [max_new_tokens, n_rows] float32 in [0, 1): from a SECOND private
+    generator seeded from sample_seed, else from the device's default generator -- drawn after U either way, so U keeps the values
+    plain sampling draws from the same seed"""
+    shape = (3, max_new_tokens, n_rows)
+    if sample_seed is None:
+        return torch.rand(shape, dtype=torch.float32, device=device)
+    g = torch.Generator(device=device)
+    g.manual_seed((sample_seed + 0x5DEECE66D) % (1 << 63))
+    return torch.rand(shape, dtype=torch.float32, device=device, generator=g)
+
+
+class Rejector:
+    """The randomness of a generation that verifies with the rejection rule (speculative.py): the generation's Sampler (U: the
+    first token behind the prefill) and the three tables of the rounds."""
+
+    def __init__(self, sampler, tables):
+        self.sampler = sampler
+        self.u_draft, self.u_acc, self.u_res = tables[0], tables[1], tables[2]
+
+    def block(self, step0):
+        """the view of a round that starts with step0 generated tokens: block position t is step step0 + t"""
+        return RejectorBlock(self, int(step0))
+
+
+class RejectorBlock:
+    """What a rejection verify pass reads: the settings, U_acc / U_res ([n_steps, ldu], row b is column b), the step origin and --
+    set by the loop between propose and verify -- draft_logits, the drafter's bf16 logits [B, k, vocab] of the round's draft steps.
+    draft_steps(k): the Samplers a stochastic drafter draws step 0 .. k - 1 with, U_draft[step0 + i] (0 past the table)."""
+
+    def __init__(self, rejector, step0):
+        smp = rejector.sampler
+        self.temperature, self.top_k, self.top_p = smp.temperature, smp.top_k, smp.top_p
+        self.u_draft, self.u_acc, self.u_res = rejector.u_draft, rejector.u_acc, rejector.u_res
+        self.step0 = step0
+        self.n_steps = int(self.u_acc.shape[0])
+        self.draft_logits = None
+
+    def draft_steps(self, k):
+        return Sampler(self.temperature, self.top_k, self.top_p, self.u_draft).block(self.step0).draft_steps(k)

@@ -330,7 +330,7 @@ class OffloadScheduler:
 
     def verify(self, block_ids, kv_state, suppress_token=-1, n_suppress=0, active=None, prefill_policy=1, decoding_policy=1,
                no_overlap=False, pin_weight=False, gpu_percentage=0, num_minibatch=1, enable_cxl=False, append_policy=None,
-               sampler=None, return_logits=False, **_decode_only):
+               sampler=None, return_logits=False, rejector=None, **_decode_only):
         """Speculative verification: one pass of the weights over block_ids [B, T] = [pending | d_1 .. d_{T-1}]
         appended at kv_state.len on a NON-EMPTY cache.  forward()'s phases with the last layer on every position, lm_verify in
         place of lm_head and LIA_OPT_BLOCK_ATTENTION set around the layers; the K/V rows are delivered as in forward().  Returns
@@ -340,7 +340,9 @@ class OffloadScheduler:
         < n_suppress; active (int32 / bool [B] or None): rows with 0 never limit common.  A fixed cpu_layers is passed through as
         in score().  sampler (sampling.SamplerBlock, sampled verification): the head is lm_verify_sample -- res.greedy holds the
         draws of U[step + t, b], res.p_draft the chance of each to confirm the draft; return_logits (with a sampler, for tests and
-        measurements) also returns the block's logits.  Everything else is the same pass."""
+        measurements) also returns the block's logits.  rejector (sampling.RejectorBlock, rejection verification of a stochastic
+        drafter's block): the head is lm_verify_reject -- res.greedy holds `token`, res.ok / p_tok / q_tok / resid_mass the accept
+        test.  Everything else is the same pass."""
         from . import speculative
         check_verify_block(block_ids, kv_state)
         B, T = block_ids.shape
@@ -362,7 +364,10 @@ class OffloadScheduler:
                 hidden = self._run_layers(s, kv_state)
         finally:
             ctx.set_option(N.LIA_OPT_BLOCK_ATTENTION, 0)
-        if sampler is None:
+        if rejector is not None:
+            res = ctx.lm_verify_reject(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, rejector, sh.ln_eps, suppress_token,
+                                       n_suppress, active=act_dev, return_logits=return_logits, return_probs=True)
+        elif sampler is None:
             res = ctx.lm_verify(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, sh.ln_eps, suppress_token, n_suppress, act_dev)
         else:
             res = ctx.lm_verify_sample(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, sampler, sh.ln_eps, suppress_token,

@@ -19,6 +19,11 @@ propose_rows(rows: list of 1-D int64 CPU tensors, k, suppress_rows) -> int64 [B,
 Sampled verification, generate(..., do_sample=True, sampled_verify=True, draft=...): the verify pass draws every block position with
 the uniform the plain sampled loop would use there (U[generated so far + t, row]); a draft token is accepted iff it equals that
 draw, and the emitted token is always the draw.  The ids are the same function of (logits, U) as plain sampled decoding's.
+
+Rejection verification, generate(..., do_sample=True, sampled_verify=True, verify_rule="rejection", draft=ModelDrafter(m,
+stochastic=True)): the drafter SAMPLES its own logits (U_draft), the verify pass accepts a draft token x with probability
+min(1, P(x) / Q(x)) (U_acc) and emits a draw of norm(max(P - Q, 0)) at the first rejection (U_res) -- the rule of Leviathan et al.
+The output is an exact sample of the target's filtered distribution, but NOT the ids plain sampling draws from the same seed.
 """
 import time
 
@@ -35,6 +40,37 @@ REFUSALS = {
     "cpu_layers": "draft together with cpu_layers=-1 (the online cooperative split) is not supported: the controller samples "
                   "single-token decode steps; name a fixed cpu_layers",
 }
+
+
+VERIFY_RULES = ("draw", "rejection")
+REJECT_REFUSALS = {
+    "rule": "verify_rule must be 'draw' (accept a draft token iff it equals the sampler's own draw) or 'rejection' (accept it with "
+            "probability min(1, p / q), else draw from the residual)",
+    "sampled_verify": "verify_rule='rejection' needs sampled_verify=True (with do_sample=True and draft=): it is a rule of sampled "
+                      "verification",
+    "stochastic": "verify_rule='rejection' needs a drafter that declares stochastic=True and keeps draft_logits: the rule divides by "
+                  "the probability the drafter drew its token with",
+    "coupled": "a drafter cannot be stochastic and coupled: a coupled drafter draws with the TARGET's uniforms (verify_rule='draw'), a "
+               "stochastic one with uniforms of its own (verify_rule='rejection')",
+    "row": "verify_rule='rejection' together with acceptance='row' is not supported: the row-mode drafter suppresses at the smallest n "
+           "of the rows, so Q would not be what every row's token was drawn from",
+}
+
+
+def check_verify_rule(verify_rule, sampled_verify, draft, acceptance):
+    """every refusal of generate(verify_rule=), by name (ValueError), before any forward"""
+    if verify_rule not in VERIFY_RULES:
+        raise ValueError(REJECT_REFUSALS["rule"] + f", got {verify_rule!r}")
+    if getattr(draft, "stochastic", False) and getattr(draft, "coupled", False):
+        raise ValueError(REJECT_REFUSALS["coupled"])
+    if verify_rule != "rejection":
+        return
+    if not sampled_verify or draft is None:
+        raise ValueError(REJECT_REFUSALS["sampled_verify"])
+    if not getattr(draft, "stochastic", False):
+        raise ValueError(REJECT_REFUSALS["stochastic"] + f", got {type(draft).__name__}")
+    if acceptance == "row":
+        raise ValueError(REJECT_REFUSALS["row"])
 
 
 ACCEPTANCE = ("common", "row")
@@ -199,13 +235,22 @@ class ModelDrafter:
     coupled=True (sampled verification only): the loops hand propose / propose_rows the round's sampling.SamplerBlock, and draft
     step i samples the drafter's own logits with the target's settings and the target's uniform of that position, U[g_b + i, b]
     (0 past the table) -- it guesses the target's DRAW, not its argmax, and is right wherever the two models' running masses put
-    that uniform on the same token.  A drafter only ever changes how many positions a round keeps, never a token."""
+    that uniform on the same token.  A drafter only ever changes how many positions a round keeps, never a token.
+
+    stochastic=True (rejection verification only): the loop hands propose the round's sampling.RejectorBlock, and draft step i
+    samples the drafter's own logits with the target's settings and a uniform of its own, U_draft[g + i, b]; step i suppresses iff
+    i < n_sup, the rule the verify head applies to both models' rows.  The k steps' logits stay on the device as draft_logits
+    (bf16 [B, k, vocab]): the Q the tokens were drawn from."""
 
     FLAGS = dict(prefill_policy=3, decoding_policy=3, gpu_percentage=100, pin_weight=True)
 
-    def __init__(self, model, reserve=64, coupled=False):
+    def __init__(self, model, reserve=64, coupled=False, stochastic=False):
         from .generation import _scheduler_of
+        if coupled and stochastic:
+            raise ValueError(REJECT_REFUSALS["coupled"])
         self.model, self.sched, self.reserve, self.coupled = model, _scheduler_of(model), reserve, bool(coupled)
+        self.stochastic = bool(stochastic)
+        self.draft_logits = None
         self.vocab = model.shape.vocab
         self.kv = None
         self.fed = None          # int64 [B, kv.len]: the tokens whose K/V the cache holds
@@ -224,7 +269,7 @@ class ModelDrafter:
             return [{}] * k
         return [{"sampler": s} for s in sampler.draft_steps(k)]
 
-    def propose(self, ids, k, suppress=(-1, 0), sampler=None):
+    def propose(self, ids, k, suppress=(-1, 0), sampler=None, rejector=None):
         ids = torch.as_tensor(ids, dtype=torch.int64).cpu()
         B, n = ids.shape
         tok, n_sup = suppress
@@ -241,12 +286,18 @@ class ModelDrafter:
         self.kv.len = keep
         cur = ids[:, keep:]
         dev, step_kw = [], self._step_kw(sampler, k)
+        keep_logits = self.stochastic and rejector is not None
+        if keep_logits:
+            step_kw, kept = [{"sampler": smp} for smp in rejector.draft_steps(k)], []
         for i in range(k):
             sup = tok if i < n_sup else -1
-            _, nxt = self.sched.forward(cur, self.kv, max_new_tokens=k, suppress_token=sup, **step_kw[i], **self.FLAGS)
+            logits, nxt = self.sched.forward(cur, self.kv, max_new_tokens=k, suppress_token=sup, **step_kw[i], **self.FLAGS)
             dev.append(nxt)
+            if keep_logits:
+                kept.append(logits)
             cur = nxt.view(B, 1)
         out = torch.stack(dev, dim=1).cpu()
+        self.draft_logits = torch.stack(kept, dim=1) if keep_logits else None
         self.fed = torch.cat([ids, out[:, :k - 1]], dim=1)
         self.rounds += 1
         return out
@@ -301,6 +352,10 @@ def _verify_kw(view):
 def _draft_kw(draft, view):
     """the round's sampler view, for drafters that declare `coupled` only"""
     return {"sampler": view} if (view is not None and getattr(draft, "coupled", False)) else {}
+
+
+def _reject_kw(view):
+    return {} if view is None else {"rejector": view}
 
 
 def speculative_search_rows(model, sched, input_ids, max_new_tokens, min_new_tokens, eos_token_id, pad_token_id, token_latency, lia,
@@ -380,15 +435,20 @@ def speculative_search_rows(model, sched, input_ids, max_new_tokens, min_new_tok
 
 def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, eos_token_id, pad_token_id, token_latency, lia,
                        draft, draft_tokens, spec_log=None, step_hook=None, max_steps=None, past=None, return_state=False,
-                       reserve_tokens=0, starts=None, sampler=None):
+                       reserve_tokens=0, starts=None, sampler=None, rejector=None):
     """_greedy_search with a drafter: the ordinary prefill, then rounds of propose -> verify -> append.  The EOS / pad / unfinished
     bookkeeping is applied token by token as the greedy loop applies it; a finished row is inactive (it never limits `common`, its
     block is pad tokens, as the greedy loop feeds them); a round ends behind the token at which a row finishes, so the cache holds
     exactly what the greedy loop would have fed.  latency_list has one entry per target pass.
     sampler (the generation's sampling.Sampler, sampled verification): the first forward draws with U[0] as the plain sampled loop
     does, and a round that starts with g generated tokens draws block position t with U[g + t] -- the token at generated step s is
-    lia_sample(logits(prefix), U[s]) on either loop; the sampled ids stand where `greedy` stood."""
+    lia_sample(logits(prefix), U[s]) on either loop; the sampled ids stand where `greedy` stood.
+    rejector (the generation's sampling.Rejector, in place of sampler: rejection verification): the first forward draws with U[0]; a
+    round hands the drafter and the verify pass the view of step origin g, gives the view the drafter's draft_logits, and emits the
+    `common` draft tokens every active row accepted and then res.next -- per row its own accepted draft token or the head's token."""
     from .generation import GenerationState, turn_positions
+    if rejector is not None:
+        sampler = None
     k = draft_tokens
     ids = torch.as_tensor(input_ids, dtype=torch.int64).cpu()
     if ids.dim() != 2:
@@ -442,7 +502,8 @@ def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, 
         step_hook(0)
     tic = time.time()
     suppress = eos_token_id if (eos_token_id is not None and 0 < min_new_tokens) else -1
-    _, nxt = sched.forward(first, kv, max_new_tokens=max_new_tokens, suppress_token=suppress, **_first_kw(sampler), **lia)
+    _, nxt = sched.forward(first, kv, max_new_tokens=max_new_tokens, suppress_token=suppress,
+                           **_first_kw(sampler if rejector is None else rejector.sampler), **lia)
     over, _ = append(nxt.cpu())
     latency_list.append(time.time() - tic)
     rnd = 0
@@ -457,14 +518,22 @@ def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, 
         sup_tok = eos_token_id if n_sup else -1
         active = state["unfinished"]
         view = None if sampler is None else sampler.block(g)
-        prop = torch.as_tensor(draft.propose(ids_buf[:, :T + g], k, (sup_tok, min(n_sup, k)), **_draft_kw(draft, view)), dtype=torch.int64).cpu()
+        rview = None if rejector is None else rejector.block(g)
+        prop = torch.as_tensor(draft.propose(ids_buf[:, :T + g], k, (sup_tok, min(n_sup, k)), **_draft_kw(draft, view), **_reject_kw(rview)),
+                               dtype=torch.int64).cpu()
         if tuple(prop.shape) != (B, k):
             raise ValueError(f"draft.propose returned shape {tuple(prop.shape)}, expected {(B, k)}")
         if eos_token_id is not None:
             prop = prop * active[:, None] + pad_token_id * (1 - active[:, None])      # a finished row is fed pad tokens
         block = torch.cat([ids_buf[:, T + g - 1:T + g], prop], dim=1)
-        res, common = sched.verify(block, kv, suppress_token=sup_tok, n_suppress=n_sup, active=active.to(torch.int32), **_verify_kw(view), **lia)
-        greedy = res.greedy.cpu()
+        if rview is not None:
+            rview.draft_logits = draft.draft_logits        # [B, k, vocab]: the Q behind prop (a finished row's is never looked at)
+        res, common = sched.verify(block, kv, suppress_token=sup_tok, n_suppress=n_sup, active=active.to(torch.int32), **_verify_kw(view),
+                                   **_reject_kw(rview), **lia)
+        if rview is None:
+            greedy = res.greedy.cpu()
+        else:                                              # the accepted draft tokens, then each row's token behind them
+            greedy = torch.cat([block[:, 1:common + 1], res.next.cpu()[:, None]], dim=1)
         if spec_log is not None:
             spec_log.append((common, res.accepted.cpu().tolist()))
         n_app = 0

@@ -33,7 +33,10 @@ tokens per round beside the mean p_draft of the same rounds' first positions (th
 many rows left the plain sampled ids, with the first step at which one did (a verify pass and a decode step round differently: such
 rows are still exact samples of the verify pass's distribution).  The ReplayDrafter replays the plain SAMPLED run.  With --draft, a
 ModelDrafter of that shape (random weights of its own: real checkpoints are not available here) drafts greedily and, with --coupled,
-with the target's uniforms; each line is marked on or off what its drafter would be expected to give only by its p_draft column."""
+with the target's uniforms; each line is marked on or off what its drafter would be expected to give only by its p_draft column.
+--verify-rule rejection adds, per k in common mode, a stochastic ModelDrafter verified with the rejection rule and one line with the
+first-token acceptance of the three drafters side by side, next to the mean sum min(p, q) of the rejection rounds (1 - the head's
+residual mass: the acceptance the rule reaches in expectation)."""
 import argparse
 import os
 import statistics
@@ -115,10 +118,14 @@ def sampled_ab(a, model, prompt, rec, step, ks, modes, kw, generate, ReplayDraft
     seen = []                                          # the p_draft of every sampled verify pass
     ver, ver_rows = sched.verify, sched.verify_rows
 
+    resid = []                                         # the residual mass behind the first position of every rejection verify pass
+
     def verify(*args, **k2):
         out = ver(*args, **k2)
         if k2.get("sampler") is not None:
             seen.append(out[0].p_draft)
+        if k2.get("rejector") is not None:
+            resid.append(float(out[0].resid_mass[:, 0].mean()))
         return out
 
     def verify_rows(*args, **k2):
@@ -141,6 +148,7 @@ def sampled_ab(a, model, prompt, rec, step, ks, modes, kw, generate, ReplayDraft
               f"{[lo for lo, _ in log]}" + (f", first draft token accepted {sum(acc1) / len(acc1):.3f} of {len(acc1)} (round, row) pairs, mean p_draft "
               f"{sum(pd) / len(pd):.3f}" if pd else "") + (f", rows that left the plain ids {int(left.sum())} of {B}"
               + (f" (first at step {first})" if first is not None else "")), flush=True)
+        return sum(acc1) / max(len(acc1), 1)
 
     drafters = [("replay", lambda ids: ReplayDrafter(ids))]
     if a.draft != "none":
@@ -151,6 +159,7 @@ def sampled_ab(a, model, prompt, rec, step, ks, modes, kw, generate, ReplayDraft
     for k in ks:
         for m in modes:
             extra = {} if m == "common" else {"acceptance": "row"}
+            shares = {}
             for name, make in drafters:
                 greedy, sampled = [], []
                 for rep_ in range(a.reps):
@@ -165,7 +174,19 @@ def sampled_ab(a, model, prompt, rec, step, ks, modes, kw, generate, ReplayDraft
                     sampled.append((slat, log, out, [float(p[:, 0].mean()) for p in seen]))
                 if greedy:
                     line("greedy verify, " + name, k, m, greedy, rec[:, :prompt.shape[1] + a.new])
-                line("sampled verify, " + name, k, m, sampled, srec)
+                shares[name.split()[-1]] = line("sampled verify, " + name, k, m, sampled, srec)
+            if a.verify_rule == "rejection" and a.draft != "none" and m == "common":
+                gens = []
+                del resid[:]
+                for rep_ in range(a.reps):
+                    log = []
+                    out, slat = generate(model, prompt, max_new_tokens=a.new, draft=ModelDrafter(dmodel, stochastic=True), draft_tokens=k, spec_log=log,
+                                         sampled_verify=True, verify_rule="rejection", **smp, **kw)
+                    gens.append((slat, log, out, []))
+                shares["rejection"] = line("rejection, " + a.draft + " stochastic", k, m, gens, srec)
+                print(f"  k {k} first draft token accepted: rejection {shares['rejection']:.3f} (mean sum min(p, q) of the same rounds' first positions "
+                      f"{1 - sum(resid) / len(resid):.3f}), coupled {shares.get('coupled', float('nan')):.3f}, greedy drafter "
+                      f"{shares.get('greedy', float('nan')):.3f}", flush=True)
     sched.verify, sched.verify_rows = ver, ver_rows
     if a.draft != "none":
         dmodel._lia_scheduler.close()
@@ -186,9 +207,14 @@ def main():
     ap.add_argument("--pool", type=int, default=16, help="candidate prompts the batch is chosen from (0: take the first --batch)")
     ap.add_argument("--sampled", type=str, default=None, help="tau,top_k,top_p: sampled verification beside plain sampling and the greedy verify")
     ap.add_argument("--coupled", action="store_true", help="with --sampled and --draft: also a ModelDrafter that draws with the target's uniforms")
+    ap.add_argument("--verify-rule", type=str, default="draw", choices=["draw", "rejection"],
+                    help="with --sampled and --draft: rejection = also a stochastic ModelDrafter verified with the rejection rule (common mode), "
+                         "its first-token acceptance beside the coupled and the greedy drafter's and the mean sum min(p, q)")
     a = ap.parse_args()
     if a.coupled and not a.sampled:
         ap.error("--coupled needs --sampled")
+    if a.verify_rule != "draw" and not a.sampled:
+        ap.error("--verify-rule rejection needs --sampled")
     import torch
     from lia_amd.generation import generate
     from lia_amd.speculative import ModelDrafter, ReplayDrafter
