@@ -587,6 +587,49 @@ int lia_stream_land(lia_streamer* s, int landing, const void* host_ptr, size_t p
 int lia_stream_decode_landed(lia_streamer* s, int landing, int slot, size_t n_values, int format);
 int lia_stream_decode_cached(lia_streamer* s, int entry, int slot, const void* host_ptr, size_t packed_bytes, size_t n_values, int format,
                              int pinned);
+/* Where the decode mode's entries lie: a pure host function (no device, no streamer), so that tests and the planner can ask it.
+ * The pool has three regions, filled in this order up to LIA_CACHE_MAX_ENTRIES entries in all:
+ *   slots:     the bytes of slots keep_slots .. n_slots - 1 of the slot allocation (n_slots x slot_bytes);
+ *   staging:   the staging allocation (n_slots x staging_bytes) behind the keep_slots landing buffers.  landing_bytes == 0: a
+ *              landing buffer is a whole staging area (the geometry before lia_stream_cache_configure); otherwise landing buffer b
+ *              starts at b x landing_stride, landing_stride = landing_bytes + LIA_CACHE_READ_SLACK rounded up to 256;
+ *   workspace: bytes [lend_offset, lend_offset + lend_bytes) of the context's workspace, lend_offset rounded up to 256 (the bytes
+ *              lost to the rounding come off lend_bytes).  lend_bytes == 0: none.
+ * Every entry starts on a multiple of 256 bytes of its allocation, keeps LIA_CACHE_READ_SLACK bytes behind entry_bytes and lies
+ * inside one region.  offset[e] is entry e's byte offset from the start of ITS allocation (slots / staging / workspace); entries
+ * 0 .. in_slots - 1 are in the slots, the next in_staging in the staging allocation, the last in_workspace in the workspace.
+ * Returns LIA_OK -- with n_entries == 0 where the mode has nothing to offer: keep_slots < 1, keep_slots >= n_slots, no staging
+ * allocation, entry_bytes == 0 -- or LIA_ERR_INVALID (*out zeroed) for a landing_stride larger than a staging area. */
+#define LIA_CACHE_MAX_ENTRIES 64
+#define LIA_CACHE_READ_SLACK 4096
+typedef struct lia_cache_geometry {
+  int n_entries, in_slots, in_staging, in_workspace;
+  size_t entry_stride;      /* entry_bytes + LIA_CACHE_READ_SLACK rounded up to 256 */
+  size_t landing_stride;    /* distance between two landing buffers in the staging allocation */
+  size_t landing_capacity;  /* the largest encoded layer lia_stream_land takes */
+  size_t offset[LIA_CACHE_MAX_ENTRIES];
+} lia_cache_geometry;
+int lia_cache_geometry_plan(int n_slots, size_t slot_bytes, size_t staging_bytes, int keep_slots, size_t entry_bytes, size_t landing_bytes,
+                            size_t lend_offset, size_t lend_bytes, lia_cache_geometry* out);
+/* Opt-in geometry of the decode mode, refused while the mode is on and sticky until changed; all zero = the geometry above
+ * without it, bit for bit.
+ *   landing_bytes: the largest encoded layer that will be landed.  Landing buffers shrink from a whole staging area to this (+ read
+ *       slack) and the rest of the staging allocation holds entries; lia_stream_land refuses a larger layer.
+ *   lend_workspace != 0: while the mode is on, the context's workspace beyond its first workspace_keep_bytes (rounded up to 256)
+ *       holds entries as well.  The context then offers only the kept part: lia_ctx_workspace_bytes returns it, every call that
+ *       takes workspace (layer forwards, lm_head, score / verify / sample chunk loops, lia_gemm) sizes itself by it, and a call that
+ *       needs more returns LIA_ERR_MEMORY without touching an entry.  Bytes [0, keep) are not written by the mode.
+ * lia_stream_cache_enable lends and lia_stream_cache_disable takes back, by events alone: the pool's first copy runs behind
+ * whatever the context's compute stream had queued and behind the K/V deliveries still draining from the workspace's slabs; the
+ * compute stream's next launch runs behind the mode's last decode.  Calls that use the workspace must be on the context's compute
+ * stream while a streamer of that context has this set.  lia_stream_cache_layout: the geometry lia_stream_cache_enable(s, keep_slots,
+ * entry_bytes) would use now (its n_entries is lia_stream_cache_capacity); with the mode on, the one in use. */
+int lia_stream_cache_configure(lia_streamer* s, size_t landing_bytes, int lend_workspace, size_t workspace_keep_bytes);
+int lia_stream_cache_layout(lia_streamer* s, int keep_slots, size_t entry_bytes, lia_cache_geometry* out);
+/* the workspace a call on this context may use now: what lia_ctx_create allocated, or the kept part while the rest is lent */
+size_t lia_ctx_workspace_bytes(lia_ctx* ctx);
+/* the workspace itself (device memory, NULL for a context created without one): for tests and tools that inspect it */
+void* lia_ctx_workspace_ptr(lia_ctx* ctx);
 
 /* ---- host memory tiers ------------------------------------------------------------------------------
  * The four exports of the reference's libnuma shim, lia/cxl/numa_alloc.c:7,25,66,108 (same names, same

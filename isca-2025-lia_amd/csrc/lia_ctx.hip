@@ -61,7 +61,7 @@ extern "C" int lia_ctx_create(int device, size_t workspace_bytes, lia_ctx** out)
     HIP_TRY(hipEventCreateWithFlags(&c->slab_ready[i], hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&c->slab_done[i], hipEventDisableTiming));
   }
-  c->ws_bytes = workspace_bytes;
+  c->ws_bytes = c->ws_alloc_bytes = workspace_bytes;
   if (workspace_bytes) HIP_TRY(hipMalloc((void**)&c->ws, workspace_bytes));
   c->gemm_opts.fuse_combine = 1;
   *out = c;
@@ -98,6 +98,36 @@ extern "C" void lia_ctx_destroy(lia_ctx* c) {
   if (c->d2h != c->compute) (void)hipStreamDestroy(c->d2h);
   (void)hipStreamDestroy(c->compute);
   delete c;
+}
+
+extern "C" size_t lia_ctx_workspace_bytes(lia_ctx* c) { return c ? c->ws_bytes : 0; }
+extern "C" void* lia_ctx_workspace_ptr(lia_ctx* c) { return c ? (void*)c->ws : nullptr; }
+
+int ctx_ws_lend(lia_ctx* c, const void* borrower, size_t keep, hipStream_t first_writer, hipEvent_t scratch_event) {
+  if (c->ws_lent_to || !c->ws || keep >= c->ws_alloc_bytes || (keep & 255)) {
+    lia_set_error("workspace lend: keep=%zu of %zu bytes (%s)", keep, c->ws_alloc_bytes, c->ws_lent_to ? "lent already" : "nothing to lend");
+    return LIA_ERR_INVALID;
+  }
+  if (first_writer != c->compute) {
+    HIP_TRY(hipEventRecord(scratch_event, c->compute));
+    HIP_TRY(hipStreamWaitEvent(first_writer, scratch_event, 0));
+  }
+  // a K/V delivery of the prefill may still read a slab, which lies beyond any decode step's keep
+  for (int i = 0; i < 2; ++i)
+    if (c->slab_used[i]) HIP_TRY(hipStreamWaitEvent(first_writer, c->slab_done[i], 0));
+  // a norm the previous layer call chained into a buffer that is about to be lent is gone
+  if (c->normed_buf && (const char*)c->normed_buf >= c->ws + keep) ws_invalidate(c);
+  c->ws_bytes = keep;
+  c->ws_lent_to = borrower;
+  return LIA_OK;
+}
+
+int ctx_ws_take_back(lia_ctx* c, const void* borrower, hipEvent_t idle) {
+  if (c->ws_lent_to != borrower) return LIA_OK;
+  HIP_TRY(hipStreamWaitEvent(c->compute, idle, 0));
+  c->ws_bytes = c->ws_alloc_bytes;
+  c->ws_lent_to = nullptr;
+  return LIA_OK;
 }
 
 extern "C" void* lia_ctx_compute_stream(lia_ctx* c) { return c ? (void*)c->compute : nullptr; }

@@ -130,7 +130,9 @@ struct lia_ctx {
   hipStream_t compute;
   hipStream_t d2h;           // K/V delivery to the host cache (policy 0)
   char* ws;
-  size_t ws_bytes;
+  size_t ws_bytes;           // what a call may use: ws_alloc_bytes, or the kept part [0, keep) while the rest is lent (ctx_ws_lend)
+  size_t ws_alloc_bytes;     // what lia_ctx_create allocated
+  const void* ws_lent_to;    // the streamer whose wire cache holds the lent part; NULL: nothing is lent
   hipEvent_t slab_ready[2];  // recorded on compute when a K/V slab may be copied out
   hipEvent_t slab_done[2];   // recorded on d2h when the slab has been delivered
   bool slab_used[2];
@@ -185,6 +187,14 @@ struct lia_ctx {
 
 // the workspace is about to be reused: a norm the previous layer call chained into it is gone, and so is a pending hint
 static inline void ws_invalidate(lia_ctx* ctx) { ctx->normed_src = nullptr; ctx->chain_armed = false; }
+
+// Lending the workspace's tail to a streamer's wire cache (lia_stream_cache_configure).  Event-only, nothing is allocated.
+//   lend: the context offers bytes [0, keep) from here on (keep a multiple of 256, < ws_alloc_bytes); `first_writer` -- the stream
+//       that writes the lent part first -- is put behind everything queued on the compute stream and behind the K/V deliveries
+//       still draining from the workspace's slabs.  LIA_ERR_INVALID when the workspace is lent already.
+//   take_back: the compute stream's next launch runs behind `idle` (recorded by the borrower behind its last reader).
+LIA_HIDDEN int ctx_ws_lend(lia_ctx* ctx, const void* borrower, size_t keep, hipStream_t first_writer, hipEvent_t scratch_event);
+LIA_HIDDEN int ctx_ws_take_back(lia_ctx* ctx, const void* borrower, hipEvent_t idle);
 
 // Chaining state of one layer call (lia_ctx_chain_next_norm).  take: consume the hint for THIS call's last GEMM (g / b: the next
 // layer's first-norm weights, or NULL) and tell whether the previous call already left norm1(x) in `ln`; publish: after the last

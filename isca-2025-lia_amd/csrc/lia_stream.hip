@@ -40,11 +40,16 @@ struct lia_streamer {
   hipEvent_t bounce_done[2];
   int bounce_next;
   double bytes, busy_ms;
-  // wire cache (lia_stream_cache_*, decode mode): while keep_slots != 0 the slots and staging areas from keep_slots on are a pool of
-  // n_entries wire-format layers, entry_stride bytes apart (the first entries_in_slots of them in the slots' bytes, the rest in the
-  // staging areas'), and the staging areas below keep_slots are landing buffers that no longer belong to a slot
-  int keep_slots, n_entries, entries_in_slots;
-  size_t entry_stride;
+  // wire cache (lia_stream_cache_*, decode mode): while keep_slots != 0 a pool of geo.n_entries wire-format layers lies where
+  // lia_cache_geometry_plan put it -- the slots from keep_slots on, the staging allocation behind the keep_slots landing buffers
+  // (which no longer belong to a slot) and, when configured, the tail of the context's workspace
+  int keep_slots;
+  lia_cache_geometry geo;              // of the mode that is on (zeroed while it is off)
+  // lia_stream_cache_configure: sticky, all zero = whole staging areas as landing buffers and no workspace entries
+  size_t cfg_landing_bytes, cfg_keep_bytes;
+  int cfg_lend;
+  bool lent;                           // this mode holds the context's workspace tail
+  hipEvent_t ws_fence;                 // on the compute stream when the workspace is lent
   std::vector<char> entry_filled;
   std::vector<const void*> entry_src;
   std::vector<size_t> entry_bytes;
@@ -59,12 +64,11 @@ struct lia_streamer {
   int ring_next;
 };
 
-constexpr int LIA_CACHE_MAX_ENTRIES = 64;
 constexpr int LIA_CACHE_TIMING_RING = 16;
 // The decode kernels read a little past the bytes shipped: 16 bytes of stream padding for a consistent encoding, at most
 // (1024 codes) / 2 + 8 bytes behind the level-3 stream whatever the planes hold once the validator passed the tables
-// (lia_pack10_validate), 2 bytes behind pack10a's words.  Every entry keeps this much room behind its layer.
-constexpr size_t LIA_CACHE_READ_SLACK = 4096;
+// (lia_pack10_validate), 2 bytes behind pack10a's words.  Every entry, and every landing buffer sized by
+// lia_stream_cache_configure, keeps LIA_CACHE_READ_SLACK (lia_hip.h) bytes of room behind its layer.
 
 static void streamer_collect_decode(lia_streamer* s, int slot, bool wait) {
   if (s->decode_pending.empty() || !s->decode_pending[slot]) return;
@@ -112,7 +116,8 @@ extern "C" int lia_stream_create(lia_ctx* ctx, int n_slots, size_t slot_bytes, l
   s->bounce[0] = s->bounce[1] = nullptr; s->bounce_done[0] = s->bounce_done[1] = nullptr; s->bounce_next = 0;
   s->bytes = 0; s->busy_ms = 0; s->slots = nullptr; s->staging = nullptr; s->staging_bytes = 0;
   s->dec_ms = s->dec_in = s->dec_out = 0; s->dec_launches = 0;
-  s->keep_slots = s->n_entries = s->entries_in_slots = 0; s->entry_stride = 0; s->cache_idle = nullptr; s->ring_next = 0;
+  s->keep_slots = 0; memset(&s->geo, 0, sizeof(s->geo)); s->cache_idle = nullptr; s->ring_next = 0;
+  s->cfg_landing_bytes = s->cfg_keep_bytes = 0; s->cfg_lend = 0; s->lent = false; s->ws_fence = nullptr;
   HIP_TRY(hipMalloc((void**)&s->slots, s->slot_bytes * n_slots));
   if (ctx->serialized) s->copy = ctx->compute;
   else HIP_TRY(hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking));
@@ -131,6 +136,7 @@ extern "C" int lia_stream_create(lia_ctx* ctx, int n_slots, size_t slot_bytes, l
 
 extern "C" void lia_stream_destroy(lia_streamer* s) {
   if (!s) return;
+  (void)lia_stream_cache_disable(s);     // (the context gets its workspace back)
   (void)hipStreamSynchronize(s->copy);
   for (int i = 0; i < s->n_slots; ++i) {
     (void)hipEventDestroy(s->copied[i]); (void)hipEventDestroy(s->released[i]);
@@ -150,6 +156,7 @@ extern "C" void lia_stream_destroy(lia_streamer* s) {
     for (hipEvent_t e : s->r0) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->r1) (void)hipEventDestroy(e);
     if (s->cache_idle) (void)hipEventDestroy(s->cache_idle);
+    if (s->ws_fence) (void)hipEventDestroy(s->ws_fence);
     if (s->decode != s->ctx->compute) (void)hipStreamDestroy(s->decode);
     (void)hipFree(s->staging);
   }
@@ -248,6 +255,7 @@ static int ensure_staging(lia_streamer* s) {
   s->has_drained.assign(s->n_slots, 0); s->landing_bytes.assign(s->n_slots, 0);
   for (int i = 0; i < s->n_slots; ++i) HIP_TRY(hipEventCreateWithFlags(&s->drained[i], hipEventDisableTiming));
   HIP_TRY(hipEventCreateWithFlags(&s->cache_idle, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&s->ws_fence, hipEventDisableTiming));
   s->r0.resize(LIA_CACHE_TIMING_RING); s->r1.resize(LIA_CACHE_TIMING_RING);
   s->ring_pending.assign(LIA_CACHE_TIMING_RING, 0); s->ring_bytes.assign(LIA_CACHE_TIMING_RING, 0);
   for (int i = 0; i < LIA_CACHE_TIMING_RING; ++i) {
@@ -379,48 +387,76 @@ extern "C" int lia_stream_release(lia_streamer* s, int slot, void* compute_strea
 //       slot's release, and records drained[b].
 //   entry e: lia_stream_decode_cached fills it on first use (one H2D copy, counted like any copy) and decodes it into a kept slot.
 // All copies stay on the copy stream and all decodes on the decode stream; nothing here waits on the host.
-static size_t cache_staging_offset(const lia_streamer* s, int keep_slots) { return align_up((size_t)keep_slots * s->staging_bytes, 256); }
-static size_t cache_stride(size_t entry_bytes) { return align_up(entry_bytes + LIA_CACHE_READ_SLACK, 256); }
-static void cache_counts(const lia_streamer* s, int keep_slots, size_t entry_bytes, int* in_slots, int* in_staging) {
-  *in_slots = *in_staging = 0;
-  if (!s->staging || keep_slots < 1 || keep_slots >= s->n_slots || entry_bytes == 0) return;
-  const size_t stride = cache_stride(entry_bytes);
-  const size_t a = (size_t)(s->n_slots - keep_slots) * s->slot_bytes;
-  const size_t off = cache_staging_offset(s, keep_slots), total = (size_t)s->n_slots * s->staging_bytes;
-  const size_t b = total > off ? total - off : 0;
-  *in_slots = (int)std::min<size_t>(a / stride, LIA_CACHE_MAX_ENTRIES);
-  *in_staging = (int)std::min<size_t>(b / stride, (size_t)(LIA_CACHE_MAX_ENTRIES - *in_slots));
+// the workspace bytes a mode turned on now would borrow: [*offset, *offset + bytes)
+static size_t cache_lend_range(const lia_streamer* s, size_t* offset) {
+  const lia_ctx* c = s->ctx;
+  *offset = align_up(s->cfg_keep_bytes, 256);
+  if (!s->cfg_lend || !c->ws || (c->ws_lent_to && c->ws_lent_to != s) || *offset >= c->ws_alloc_bytes) return 0;
+  return c->ws_alloc_bytes - *offset;
+}
+static int cache_plan(const lia_streamer* s, int keep_slots, size_t entry_bytes, lia_cache_geometry* g) {
+  size_t off = 0;
+  const size_t lend = cache_lend_range(s, &off);
+  return lia_cache_geometry_plan(s->n_slots, s->slot_bytes, s->staging ? s->staging_bytes : 0, keep_slots, entry_bytes, s->cfg_landing_bytes,
+                                 off, lend, g);
 }
 static char* cache_entry_ptr(lia_streamer* s, int e) {
-  if (e < s->entries_in_slots) return s->slots + (size_t)s->keep_slots * s->slot_bytes + (size_t)e * s->entry_stride;
-  return s->staging + cache_staging_offset(s, s->keep_slots) + (size_t)(e - s->entries_in_slots) * s->entry_stride;
+  if (e < s->geo.in_slots) return s->slots + s->geo.offset[e];
+  if (e < s->geo.in_slots + s->geo.in_staging) return s->staging + s->geo.offset[e];
+  return s->ctx->ws + s->geo.offset[e];
+}
+static char* cache_landing_ptr(lia_streamer* s, int landing) { return s->staging + (size_t)landing * s->geo.landing_stride; }
+
+extern "C" int lia_stream_cache_configure(lia_streamer* s, size_t landing_bytes, int lend_workspace, size_t workspace_keep_bytes) {
+  if (!s) return LIA_ERR_INVALID;
+  if (s->keep_slots) { lia_set_error("lia_stream_cache_configure: the mode is on"); return LIA_ERR_INVALID; }
+  if (landing_bytes && s->staging && align_up(landing_bytes + LIA_CACHE_READ_SLACK, 256) > s->staging_bytes) {
+    lia_set_error("lia_stream_cache_configure: a landing buffer of %zu bytes does not fit a staging area of %zu", landing_bytes, s->staging_bytes);
+    return LIA_ERR_INVALID;
+  }
+  s->cfg_landing_bytes = landing_bytes;
+  s->cfg_lend = lend_workspace ? 1 : 0;
+  s->cfg_keep_bytes = lend_workspace ? workspace_keep_bytes : 0;
+  return LIA_OK;
+}
+
+extern "C" int lia_stream_cache_layout(lia_streamer* s, int keep_slots, size_t entry_bytes, lia_cache_geometry* out) {
+  if (!s || !out) return LIA_ERR_INVALID;
+  if (s->keep_slots) { *out = s->geo; return LIA_OK; }
+  return cache_plan(s, keep_slots, entry_bytes, out);
 }
 
 extern "C" int lia_stream_cache_capacity(lia_streamer* s, int keep_slots, size_t entry_bytes) {
   if (!s) return 0;
-  int a, b;
-  cache_counts(s, keep_slots, entry_bytes, &a, &b);
-  return a + b;
+  lia_cache_geometry g;
+  return cache_plan(s, keep_slots, entry_bytes, &g) ? 0 : g.n_entries;
 }
 
 extern "C" int lia_stream_cache_enable(lia_streamer* s, int keep_slots, size_t entry_bytes) {
   if (!s) return LIA_ERR_INVALID;
-  int a = 0, b = 0;
-  cache_counts(s, keep_slots, entry_bytes, &a, &b);
-  if (s->keep_slots || a + b == 0) {
+  lia_cache_geometry g;
+  const int bad = cache_plan(s, keep_slots, entry_bytes, &g);
+  if (s->keep_slots || bad || g.n_entries == 0) {
     lia_set_error("lia_stream_cache_enable: keep_slots=%d entry_bytes=%zu on %d slots (%s)", keep_slots, entry_bytes, s->n_slots,
-                  s->keep_slots ? "the mode is on" : "no room for an entry");
+                  s->keep_slots ? "the mode is on" : bad ? "the configured landing buffers do not fit the staging areas" : "no room for an entry");
     return LIA_ERR_INVALID;
   }
   // the pool's first writer is the copy stream: behind the last consumers of the slots that leave the ring and behind their
   // prefetches' decodes (dropped ones included), which read the staging areas that leave with them
   for (int i = 0; i < s->n_slots; ++i) {
     if (i >= keep_slots && s->has_release[i]) HIP_TRY(hipStreamWaitEvent(s->copy, s->released[i], 0));
-    // (a kept slot: its staging area becomes a landing buffer, still read by the decode of the slot's last legacy prefetch)
+    // (a kept slot: its staging area becomes landing buffers and entries, still read by the decode of the slot's last legacy prefetch)
     if (s->was_marked[i]) HIP_TRY(hipStreamWaitEvent(s->copy, s->copied[i], 0));
     s->has_drained[i] = 0; s->landing_bytes[i] = 0;
   }
-  s->keep_slots = keep_slots; s->entries_in_slots = a; s->n_entries = a + b; s->entry_stride = cache_stride(entry_bytes);
+  // ... and, for the entries in the workspace, behind the compute stream's last use of it and the K/V deliveries draining from it
+  if (g.in_workspace) {
+    size_t keep = 0;
+    (void)cache_lend_range(s, &keep);
+    if (int rc = ctx_ws_lend(s->ctx, s, keep, s->copy, s->ws_fence)) return rc;
+    s->lent = true;
+  }
+  s->keep_slots = keep_slots; s->geo = g;
   std::fill(s->entry_filled.begin(), s->entry_filled.end(), 0);
   return LIA_OK;
 }
@@ -432,7 +468,12 @@ extern "C" int lia_stream_cache_disable(lia_streamer* s) {
   // stream: the latter run behind every decode of the mode by stream order, the former behind this event.
   HIP_TRY(hipEventRecord(s->cache_idle, s->decode));
   HIP_TRY(hipStreamWaitEvent(s->copy, s->cache_idle, 0));
-  s->keep_slots = s->n_entries = s->entries_in_slots = 0; s->entry_stride = 0;
+  // the workspace returns to the context: its next user on the compute stream runs behind the decodes that read the entries there
+  if (s->lent) {
+    if (int rc = ctx_ws_take_back(s->ctx, s, s->cache_idle)) return rc;
+    s->lent = false;
+  }
+  s->keep_slots = 0; memset(&s->geo, 0, sizeof(s->geo));
   std::fill(s->entry_filled.begin(), s->entry_filled.end(), 0);
   return LIA_OK;
 }
@@ -451,13 +492,13 @@ static int cache_copy(lia_streamer* s, char* dst, const void* host_ptr, size_t b
 }
 
 extern "C" int lia_stream_land(lia_streamer* s, int landing, const void* host_ptr, size_t packed_bytes, int pinned) {
-  if (!s || !s->keep_slots || landing < 0 || landing >= s->keep_slots || !host_ptr || packed_bytes == 0 || packed_bytes > s->staging_bytes) {
+  if (!s || !s->keep_slots || landing < 0 || landing >= s->keep_slots || !host_ptr || packed_bytes == 0 || packed_bytes > s->geo.landing_capacity) {
     lia_set_error("lia_stream_land: landing=%d bytes=%zu (decode mode %s, %d landing buffers of %zu)", landing, packed_bytes,
-                  s && s->keep_slots ? "on" : "off", s ? s->keep_slots : 0, s ? s->staging_bytes : 0);
+                  s && s->keep_slots ? "on" : "off", s ? s->keep_slots : 0, s ? s->geo.landing_capacity : 0);
     return LIA_ERR_INVALID;
   }
   if (s->has_drained[landing]) HIP_TRY(hipStreamWaitEvent(s->copy, s->drained[landing], 0));
-  if (int rc = cache_copy(s, s->staging + (size_t)landing * s->staging_bytes, host_ptr, packed_bytes, pinned)) return rc;
+  if (int rc = cache_copy(s, cache_landing_ptr(s, landing), host_ptr, packed_bytes, pinned)) return rc;
   HIP_TRY(hipEventRecord(s->landed[landing], s->copy));
   s->landing_bytes[landing] = packed_bytes;
   return LIA_OK;
@@ -483,7 +524,7 @@ extern "C" int lia_stream_decode_landed(lia_streamer* s, int landing, int slot, 
   }
   HIP_TRY(hipStreamWaitEvent(s->decode, s->landed[landing], 0));
   if (int rc = cache_claim_slot(s, slot)) return rc;
-  if (int rc = launch_decode(s, s->staging + (size_t)landing * s->staging_bytes, slot, n_values, format, (double)s->landing_bytes[landing])) return rc;
+  if (int rc = launch_decode(s, cache_landing_ptr(s, landing), slot, n_values, format, (double)s->landing_bytes[landing])) return rc;
   HIP_TRY(hipEventRecord(s->drained[landing], s->decode));
   s->has_drained[landing] = 1; s->landing_bytes[landing] = 0;
   return cache_slot_ready(s, slot);
@@ -491,10 +532,10 @@ extern "C" int lia_stream_decode_landed(lia_streamer* s, int landing, int slot, 
 
 extern "C" int lia_stream_decode_cached(lia_streamer* s, int entry, int slot, const void* host_ptr, size_t packed_bytes, size_t n_values,
                                         int format, int pinned) {
-  if (!s || !s->keep_slots || entry < 0 || entry >= s->n_entries || slot < 0 || slot >= s->keep_slots || !host_ptr || packed_bytes == 0 ||
-      packed_bytes + LIA_CACHE_READ_SLACK > s->entry_stride || n_values * 2 > s->slot_bytes || !wire_format_known(format) || (n_values % 1024)) {
+  if (!s || !s->keep_slots || entry < 0 || entry >= s->geo.n_entries || slot < 0 || slot >= s->keep_slots || !host_ptr || packed_bytes == 0 ||
+      packed_bytes + LIA_CACHE_READ_SLACK > s->geo.entry_stride || n_values * 2 > s->slot_bytes || !wire_format_known(format) || (n_values % 1024)) {
     lia_set_error("lia_stream_decode_cached: entry=%d slot=%d bytes=%zu n_values=%zu format=%d (%d entries, stride %zu)", entry, slot,
-                  packed_bytes, n_values, format, s ? s->n_entries : 0, s ? s->entry_stride : 0);
+                  packed_bytes, n_values, format, s ? s->geo.n_entries : 0, s ? s->geo.entry_stride : 0);
     return LIA_ERR_INVALID;
   }
   char* const at = cache_entry_ptr(s, entry);

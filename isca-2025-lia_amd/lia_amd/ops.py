@@ -46,8 +46,14 @@ class Context:
         N.check(self.lib.lia_ctx_create(device, workspace_bytes, ctypes.byref(h)), "lia_ctx_create")
         self.handle = h
         self.device = device
-        self.workspace_bytes = workspace_bytes
+        self.workspace_alloc_bytes = workspace_bytes
         self.stream = self.lib.lia_ctx_compute_stream(h)
+
+    @property
+    def workspace_bytes(self):
+        """what a call on this context may use now: the allocation, or its kept part while a streamer's wire cache holds the rest
+        (lia_stream_cache_configure)"""
+        return self.lib.lia_ctx_workspace_bytes(self.handle) if self.handle else 0
 
     def close(self):
         if self.handle:

@@ -31,6 +31,9 @@ class Box:
     # Off in a bare Box, whose rates and predictions are the calibration measurements' (every layer crossing the link every step);
     # planner.wire_cache_default() is what a run of the OPT scheduler will do -- run.py's --auto-plan and --plan set it
     wire_cache: bool = False
+    # ... and, with wire_cache, in landing buffers cut to size and the context's workspace that idles during decode (the scheduler's
+    # LIA_WIRE_CACHE_WS; wire_cache_ws_default()).  Off in a Box that does not ask for it: the measurements behind wire_cache alone
+    wire_cache_ws: bool = False
     host_threads: int = 0
     host_mem_gb: float = 0.0
     calibrated: dict = None           # set by calibrate(): the measured numbers, for the log
@@ -179,15 +182,42 @@ def wire_cache_default():
     return os.environ.get("LIA_WIRE_CACHE", "1") != "0"
 
 
-def wire_cache_layers(shape, box, n_str, n_slots=4, keep_slots=2):
-    """Streamed layers a decode step finds in HBM in their wire format (streaming.WeightPipeline's decode mode): what fits the
-    n_slots - keep_slots streamer slots such a step has no use for and their staging areas (lia_pack10_bound: 1.13 x the raw
-    layer each).  They cost the step their compute, not their copy."""
+def wire_cache_ws_default():
+    """whether that cache also uses cut-to-size landing buffers and the idle workspace (LIA_WIRE_CACHE_WS, default on)"""
+    import os
+    return wire_cache_default() and os.environ.get("LIA_WIRE_CACHE_WS", "1") != "0"
+
+
+def wire_cache_layers(shape, box, n_str, n_slots=4, keep_slots=2, B=0, T=0):
+    """Streamed layers a decode step finds in HBM in their wire format (streaming.WeightPipeline's decode mode), counted by the
+    library's own geometry function (lia_cache_geometry_plan): what fits the n_slots - keep_slots streamer slots such a step has no
+    use for and the staging areas (lia_pack10_bound: 1.13 x the raw layer each) behind the landing buffers; with box.wire_cache_ws
+    the landing buffers are cut to an encoded layer and the workspace a prefill of B x T rows sized, less what a decode step of B
+    rows keeps, holds entries too.  They cost the step their compute, not their copy."""
     if not box.wire_cache or box.wire_ratio >= 1.0 or n_str <= 0 or n_slots <= keep_slots:
         return 0
+    import ctypes
+    from . import _native as N
+    lib = N.lib()
     lb = layer_bytes(shape)
-    entry = lb * box.wire_ratio
-    return min(n_str, int((n_slots - keep_slots) * lb // entry) + int((n_slots - keep_slots) * 1.13 * lb // entry))
+    slot = (lb + 255) // 256 * 256
+    staging = lib.lia_pack10_bound((slot // 2 + 1023) // 1024 * 1024)
+    entry = int(lb * box.wire_ratio)
+    landing = lend_at = lend = 0
+    if box.wire_cache_ws:
+        landing = entry
+        if B > 0 and T > 0:
+            desc = N.LayerDesc(shape.hidden, shape.heads, shape.ffn, 1e-5)
+            lm_bytes = 2 * 256 * shape.hidden + 8 * min(B, 256) * shape.vocab * 4 + (1 << 20)         # OffloadScheduler._ensure
+            ws = max(lib.lia_layer_workspace_bytes(ctypes.byref(desc), B * T), lm_bytes)
+            lend_at = (max(lib.lia_layer_workspace_bytes(ctypes.byref(desc), B), lm_bytes) + 255) // 256 * 256
+            lend = max(ws - lend_at, 0)
+            if lend < (64 << 20):                                                                      # OffloadScheduler.WS_LEND_MIN_BYTES
+                lend = 0
+    g = N.CacheGeometry()
+    if lib.lia_cache_geometry_plan(n_slots, slot, staging, keep_slots, entry, landing, lend_at, lend, ctypes.byref(g)) != 0:
+        lib.lia_cache_geometry_plan(n_slots, slot, staging, keep_slots, entry, 0, lend_at, lend, ctypes.byref(g))
+    return min(n_str, g.n_entries)
 
 
 def estimate(shape, B, T, new, gpu_percentage, decoding_policy, box=None, kv_in_hbm=None):
@@ -211,7 +241,7 @@ def estimate(shape, B, T, new, gpu_percentage, decoding_policy, box=None, kv_in_
     lm_ms = 1e3 * shape.vocab * H * 2 / (box.hbm_gbs * 1e9)
     # a cached layer: its compute, and its wire-format decode kernel's HBM traffic beside the layer in front of it (encoded bytes
     # read, bf16 written: 0.54 ms measured for an OPT-30B layer) -- never cheaper than a resident layer
-    n_cached = wire_cache_layers(shape, box, n_str)
+    n_cached = wire_cache_layers(shape, box, n_str, B=B, T=T)
     cached_ms = compute_ms + 1e3 * lb * (1.0 + box.wire_ratio) / (box.hbm_gbs * 1e9)
     decode_ms = n_gpu * resident_ms + n_cached * cached_ms + (n_str - n_cached) * streamed_ms + lm_ms + 0.5
     # prefill

@@ -129,12 +129,17 @@ def check_verify_rows(block_ids, kv_state, row_lens, flags, n_gpu, L):
 class OffloadScheduler:
     """forward(input_ids, kv_state, **lia flags) -> (logits [B,vocab], next_ids [B]) on the device."""
 
-    def __init__(self, model, device=0, n_slots=None, dp_group=None, wire=None, wire_cache=None):
+    def __init__(self, model, device=0, n_slots=None, dp_group=None, wire=None, wire_cache=None, wire_cache_ws=None):
         self.model, self.device, self.dp = model, device, dp_group
         self.n_slots = n_slots or 4
         # decode steps and small blocks keep the first streamed layers in HBM in their wire format, in the streamer slots such
         # forwards have no use for (WeightPipeline.set_decode_mode); LIA_WIRE_CACHE=0: every layer crosses the link every step
         self.wire_cache = (os.environ.get("LIA_WIRE_CACHE", "1") != "0") if wire_cache is None else bool(wire_cache)
+        # ... and in the context's workspace beyond what such forwards need, which is sized for the prefill and idles during decode
+        # (WeightPipeline.configure_cache); LIA_WIRE_CACHE_WS=0: slots and staging areas only, whole staging areas as landing buffers
+        self.wire_cache_ws = (os.environ.get("LIA_WIRE_CACHE_WS", "1") != "0") if wire_cache_ws is None else bool(wire_cache_ws)
+        self._ws_need = 0           # workspace the forward being prepared needs (_ensure)
+        self._cache_keep = 0        # the largest _ws_need of a forward that ran inside the decode mode on this context
         # wire format of the streamed layers: "pack10" (the lossless encoding of lia_pack10.hip) or "raw" bf16
         fmt = default_stream_format() if wire is None else wire
         self.wire = wire_format_code(fmt)
@@ -182,8 +187,10 @@ class OffloadScheduler:
         need = max(ops.workspace_bytes(self.model.desc, rows), lm_bytes)
         if score_rows:
             need = max(need, N.lib().lia_lm_score_workspace_bytes(score_rows, sh.hidden, sh.vocab))
-        if self.ctx is None or need > self.ctx.workspace_bytes:
+        self._ws_need = need
+        if self.ctx is None or need > self.ctx.workspace_alloc_bytes:
             if self.pipe is not None:
+                self.pipe.set_decode_mode(None)       # the wire cache hands the workspace's tail back before the context goes
                 self.pipe.close()
                 self.pipe = None
             if self.ctx is not None:
@@ -193,6 +200,7 @@ class OffloadScheduler:
             # layers, the wire encoder's buffers -- are handed back first; at batch 1050 the planner's pick ran out of HBM here)
             torch.cuda.empty_cache()
             self.ctx = ops.Context(self.device, need)
+            self._cache_keep = 0
             # the policy-2 host attention team: usable CPUs (affinity mask AND cgroup quota) split over the ranks, never
             # omp_get_max_threads() -- a team larger than the quota stalls every layer's round trip (hostinfo.py)
             if not self.host_threads:
@@ -621,6 +629,11 @@ class OffloadScheduler:
                 ctx.synchronize()
         return x if xlast is None else xlast
 
+    # The least idle workspace worth lending to the wire cache.  Lending ties the entries to the kept size: a forward that needs
+    # more costs a refill of every entry, and a workspace this small (a prefill of a few hundred rows of a small model) holds no
+    # layer of a model that is worth streaming.
+    WS_LEND_MIN_BYTES = 64 << 20
+
     SKINNY_ROWS = 256       # B x T up to which a forward's GEMMs run in the skinny, weight-bandwidth-bound regime (lia_gemm.hip)
 
     def _set_wire_cache(self, s):
@@ -636,14 +649,26 @@ class OffloadScheduler:
         # a decode step, or a block behind a non-empty cache that is kept: an append or a verify pass, not a scoring pass
         step = not s.is_prefill or (s.pos0 > 0 and (s.verify or not s.every_pos))
         if step and s.B * s.T <= self.SKINNY_ROWS:
+            if self.wire_cache_ws:
+                # the mode's forwards keep what _ensure's formula gives the largest of them, so every chunk size and split-K choice
+                # is the one a whole workspace gives; a forward that needs more re-configures (off, on, one refill of the entries)
+                self._cache_keep = max(self._cache_keep, self._ws_need)
+                idle = self.ctx.workspace_alloc_bytes - self._cache_keep
+                pipe.configure_cache(idle >= self.WS_LEND_MIN_BYTES, self._cache_keep)
             pipe.set_decode_mode(range(s.n_gpu, s.L))
         else:
             pipe.set_decode_mode(None)
 
-    def wire_cache_info(self):
-        """{"enabled", "on", "capacity" (layers), "layers" (bound to an entry, in order), "bytes" (wire bytes held in HBM)}"""
+    def wire_cache_info(self, regions=False):
+        """{"enabled", "on", "capacity" (layers), "layers" (bound to an entry, in order), "bytes" (wire bytes held in HBM)};
+        regions: also "workspace" (the context's idle workspace may hold entries) and "regions", the entries of the mode that is on
+        in the idle slots, the staging allocation and the workspace: {"slots", "staging", "workspace"}"""
         info = self.pipe.cache_info() if self.pipe else {"on": False, "capacity": 0, "layers": [], "bytes": 0}
-        return dict(info, enabled=self.wire_cache)
+        info = dict(info, enabled=self.wire_cache)
+        if regions:
+            info.update(workspace=self.wire_cache_ws,
+                        regions=self.pipe.cache_regions() if self.pipe else {"slots": 0, "staging": 0, "workspace": 0})
+        return info
 
     def _deliver(self, s, kv_state):
         """behind lm_head: the deferred K/V deliveries of a policy-0 prefill (tickets, awaited per layer by the first decode

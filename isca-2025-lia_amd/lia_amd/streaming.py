@@ -18,7 +18,8 @@ class WeightPipeline:
     Decode mode (set_decode_mode, lia_stream_cache_*): KEEP_SLOTS slots stay in the ring, the memory of the others holds the first
     streamed layers of a step in their wire format, and a packed layer that is not cached passes two stages with a resource each:
     `landed` (its copy is queued into a landing buffer) and `inflight` (its decode is queued into a slot).  The link runs ahead by
-    landing buffers while the slots cycle through the cached layers."""
+    landing buffers while the slots cycle through the cached layers.  configure_cache (lia_stream_cache_configure) sizes the landing
+    buffers for the layers that are landed and lends the mode the context's workspace beyond what its forwards need: more entries."""
 
     KEEP_SLOTS = 2
 
@@ -37,6 +38,7 @@ class WeightPipeline:
         self.free_landing = []
         self.landed = []            # [(layer_idx, landing buffer)] in issue order: copy queued, decode not yet
         self._plan = None           # (order, bound layers, entry size) of the last cache_plan that found room
+        self._cfg = (0, False, 0)   # (landing bytes, lend the workspace, workspace bytes kept) last asked of configure_cache
         self.slot_ptrs = [self.lib.lia_stream_slot_ptr(h, s) for s in range(n_slots)]
         self.ptr_arrays = [ops.weight_ptr_array(p, model.offsets) for p in self.slot_ptrs]
         if dp_group is not None:
@@ -89,6 +91,28 @@ class WeightPipeline:
                 return cand[:c], size
         return [], 0
 
+    def configure_cache(self, lend_workspace, keep_bytes=0):
+        """Before set_decode_mode: landing buffers sized for the largest encoded layer this model streams (any of them may be landed,
+        not only the ones behind the bound layers), and, lend_workspace, the context's workspace beyond its first keep_bytes as room
+        for entries while the mode is on -- keep_bytes is what the forwards that run inside the mode need.  Another configuration
+        than the last one turns the mode off first (the library refuses to change it underneath its entries): the next
+        set_decode_mode binds and refills.  Returns whether the configuration changed."""
+        if self.dp is not None or self.n_slots <= self.KEEP_SLOTS:
+            return False
+        sizes = [int(self.model.layers[i].stream_bytes) for i in range(len(self.model.layers)) if self._cacheable(i)]
+        cfg = (max(sizes, default=0), bool(lend_workspace), int(keep_bytes) if lend_workspace else 0)
+        if cfg == self._cfg:
+            return False
+        if self.keep:
+            self.set_decode_mode(None)
+        try:
+            N.check(self.lib.lia_stream_cache_configure(self.handle, cfg[0], int(cfg[1]), cfg[2]), "lia_stream_cache_configure")
+        except ValueError:
+            # a layer that hardly compresses: its encoding plus the read slack is larger than a staging area -- whole areas then
+            N.check(self.lib.lia_stream_cache_configure(self.handle, 0, int(cfg[1]), cfg[2]), "lia_stream_cache_configure")
+        self._cfg, self._plan = cfg, None             # (what was asked for: the same request is a no-op whatever the library made of it)
+        return True
+
     def set_decode_mode(self, order):
         """order: the streamed layers a decode step computes on the GPU, in order -> turn the mode on with the first of them bound
         to cache entries (no-op if it is on with these layers); None or nothing to cache: turn it off.  The caller switches between
@@ -126,6 +150,13 @@ class WeightPipeline:
     def cache_info(self):
         return {"on": bool(self.keep), "capacity": len(self.cache), "layers": sorted(self.cache, key=self.cache.get),
                 "bytes": sum(int(self.model.layers[i].stream_bytes) for i in self.cache_filled)}
+
+    def cache_regions(self):
+        """entries of the mode that is on per region: {"slots", "staging", "workspace"} (lia_stream_cache_layout)"""
+        g = N.CacheGeometry()
+        if self.keep:
+            N.check(self.lib.lia_stream_cache_layout(self.handle, self.keep, 1, ctypes.byref(g)), "lia_stream_cache_layout")
+        return {"slots": g.in_slots, "staging": g.in_staging, "workspace": g.in_workspace}
 
     def _land(self, layer_idx):
         st = self.model.layers[layer_idx]
