@@ -219,6 +219,25 @@ int lia_ctx_set_row_lens(lia_ctx* ctx, const int32_t* lens_host, int n_rows);
 int lia_attn_block_takes(int heads, int kv_heads, int head_dim, int T, int S);
 int lia_embed_ragged(const int64_t* ids, const lia_bf16* tok, const lia_bf16* pos, lia_bf16* y, int B, int T, int H,
                      const int32_t* lens_device, const int32_t* starts_device, void* stream);
+/* ---- allowed-token masks (build-defined; DESIGN.md "Constrained decoding"): restrict which tokens a row may emit -- HF's
+ * prefix_allowed_tokens_fn / suppress_tokens / bad_words_ids, a grammar engine's packed bitmask.
+ * A mask row is W = ceil(vocab / 32) int32 words in DEVICE memory; token i is allowed iff bit i & 31 of word i >> 5 is 1 (little
+ * endian: tokens 8j .. 8j + 7 are byte j of the row -- xgrammar's layout); bits at or beyond vocab are ignored.  A token that is
+ * not allowed COUNTS AS -inf, exactly as suppress_token does, and the two compose: in the greedy argmax (the first maximal index
+ * among the rest) and in the sampler (no mass, never kept by top-k or top-p).  Every masked head call gives bit for bit what the
+ * same call without a table gives on logits whose disallowed entries were overwritten with bf16 -inf.  The logits a head writes
+ * (logits, logits_out) stay the raw ones.  A row that allows no token is the caller's to refuse; the kernels do not define it.
+ * lia_ctx_set_token_mask: the table -- row r at mask_device + r * ldm_words, `rows` of them; ldm_words = 0: ONE row serves every row
+ * of every call.  NULL or rows == 0 clears it.  The context keeps the POINTER only: the caller owns the memory and keeps it alive
+ * and unchanged until the compute stream has passed the head call (nothing is copied, nothing synchronises).  WHILE A TABLE IS SET
+ * lia_lm_head, lia_llama_lm_head, lia_sample, lia_lm_verify, lia_lm_verify_rows, lia_llama_lm_verify, lia_lm_verify_sample and
+ * lia_llama_lm_verify_sample run the masked instantiations of their kernels and row i of the call reads table row i -- for the
+ * verify heads i = b * T + t, whichever workspace chunk the row falls into.  Without a table every one of them is the unmasked call,
+ * unchanged.  LIA_ERR_INVALID, by name: rows or ldm_words < 0 or a pointer that is not 4-byte aligned (here); at the head call an
+ * ldm_words that is neither 0 nor >= ceil(vocab / 32), a call with more rows than the table (ldm_words != 0); lia_lm_verify_reject
+ * and lia_llama_lm_verify_reject while a table is set (the drafter's Q would have to be masked the same way).  lia_token_logprobs and
+ * the lm_score calls do not look at the table. */
+int lia_ctx_set_token_mask(lia_ctx* ctx, const int32_t* mask_device, long ldm_words, int rows);
 /* final LN on the last position + tied lm_head + greedy argmax: modeling_opt.py:1563, models.py:424-431,
  * greedy_search.py:367,395.  logits [B,vocab], next_ids [B] (device).  suppress_token >= 0: that token's score
  * counts as -inf (EOS while min_new_tokens is unmet, run_generation.py:173,179-182); -1: none. */

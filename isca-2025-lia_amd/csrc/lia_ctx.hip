@@ -198,6 +198,19 @@ extern "C" int lia_ctx_set_row_lens(lia_ctx* c, const int32_t* lens, int n_rows)
   return LIA_OK;
 }
 
+// the allowed-token table of the head calls: the pointer only -- nothing is copied, nothing waits (the caller keeps the memory alive
+// and unchanged until the compute stream has passed the head call that reads it)
+extern "C" int lia_ctx_set_token_mask(lia_ctx* c, const int32_t* mask_device, long ldm_words, int rows) {
+  if (!c) return LIA_ERR_INVALID;
+  if (!mask_device || rows == 0) { c->token_mask = nullptr; c->token_mask_ld = 0; c->token_mask_rows = 0; return LIA_OK; }
+  if (rows < 0 || ldm_words < 0) { lia_set_error("lia_ctx_set_token_mask: rows=%d ldm=%ld must be >= 0", rows, ldm_words); return LIA_ERR_INVALID; }
+  if ((uintptr_t)mask_device & 3) { lia_set_error("lia_ctx_set_token_mask: mask=%p is not 4-byte aligned", (const void*)mask_device); return LIA_ERR_INVALID; }
+  c->token_mask = (const uint32_t*)mask_device;
+  c->token_mask_ld = ldm_words;
+  c->token_mask_rows = rows;
+  return LIA_OK;
+}
+
 extern "C" int lia_ctx_set_option(lia_ctx* c, int key, long value) {
   if (!c) return LIA_ERR_INVALID;
   switch (key) {

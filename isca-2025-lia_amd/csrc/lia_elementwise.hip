@@ -254,11 +254,16 @@ extern "C" void lia_kv_scatter_ragged_launch(const bf16_t* ksrc, const bf16_t* v
 // Greedy argmax over bf16 logits [B, vocab], first maximal index on ties (greedy_search.py:367,395).
 // `suppress` (or -1): a token whose score counts as -inf -- what HF's MinNewTokensLengthLogitsProcessor does
 // to EOS while min_new_tokens is not reached (run_generation.py:173,179-182 sets min_new_tokens = max_new_tokens).
+// MASKED (lia_ctx_set_token_mask): row r also reads the allowed-token bit row mask + r * ldm (ldm words; 0: one row for every row) --
+// token i counts as -inf unless bit i & 31 of word i >> 5 is set.  One mask byte covers the 8 tokens of a 16-byte load; the scalar
+// path tests single bits (the last word may be partly used: i < vocab bounds it).  MASKED = 0 reads neither argument.
+template <int MASKED>
 __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_argmax_kernel(const bf16_t* __restrict__ logits, int64_t* __restrict__ out,
-                                                          int vocab, int suppress) {
+                                                          int vocab, int suppress, const uint32_t* __restrict__ mask, long ldm) {
   __shared__ float sv[LIA_ROW_WAVES];
   __shared__ int si[LIA_ROW_WAVES];
   const bf16_t* row = logits + (long)blockIdx.x * vocab;
+  const uint32_t* mrow = MASKED ? mask + (long)blockIdx.x * ldm : nullptr;
   float best = -INFINITY;
   int bi = 0x7fffffff;
   if ((vocab & 7) == 0) {
@@ -266,16 +271,20 @@ __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_argmax_kernel(const bf16_
     for (int i = threadIdx.x * 8; i < vocab; i += LIA_ROW_THREADS * 8) {
       const uint4 v = *(const uint4*)(row + i);
       const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+      uint32_t allow = 0xffu;
+      if constexpr (MASKED) allow = ((const uint8_t*)mrow)[i >> 3];
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const int idx = i + e;
-        const float f = idx == suppress ? -INFINITY : bf2f((w[e >> 1] >> ((e & 1) * 16)) & 0xffff);
+        float f = idx == suppress ? -INFINITY : bf2f((w[e >> 1] >> ((e & 1) * 16)) & 0xffff);
+        if constexpr (MASKED) f = (allow >> e) & 1u ? f : -INFINITY;
         if (f > best || (f == best && idx < bi)) { best = f; bi = idx; }
       }
     }
   } else {
     for (int i = threadIdx.x; i < vocab; i += LIA_ROW_THREADS) {
       float f = i == suppress ? -INFINITY : bf2f(row[i]);
+      if constexpr (MASKED) f = (mrow[i >> 5] >> (i & 31)) & 1u ? f : -INFINITY;
       if (f > best || (f == best && i < bi)) { best = f; bi = i; }
     }
   }
@@ -296,7 +305,14 @@ __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_argmax_kernel(const bf16_
 
 extern "C" void lia_argmax_launch(const bf16_t* logits, int64_t* out, int B, int vocab, int suppress, hipStream_t st) {
   if (B <= 0) return;
-  hipLaunchKernelGGL(lia_argmax_kernel, dim3(B), dim3(LIA_ROW_THREADS), 0, st, logits, out, vocab, suppress);   // one 1024-thread workgroup per row: a row of 128 K logits is latency (45 -> 15 us at B 128)
+  hipLaunchKernelGGL(lia_argmax_kernel<0>, dim3(B), dim3(LIA_ROW_THREADS), 0, st, logits, out, vocab, suppress, (const uint32_t*)nullptr, 0L);   // one 1024-thread workgroup per row: a row of 128 K logits is latency (45 -> 15 us at B 128)
+}
+
+// mask: device, row r at mask + r * ldm words (ldm >= ceil(vocab / 32), or 0: one row for every row)
+extern "C" void lia_argmax_masked_launch(const bf16_t* logits, int64_t* out, int B, int vocab, int suppress, const uint32_t* mask, long ldm,
+                                         hipStream_t st) {
+  if (B <= 0) return;
+  hipLaunchKernelGGL(lia_argmax_kernel<1>, dim3(B), dim3(LIA_ROW_THREADS), 0, st, logits, out, vocab, suppress, mask, ldm);
 }
 
 // Small device<->pinned-host transfers of the policy-2 round trip (q|k|v out, attention result in) done by a

@@ -37,6 +37,20 @@ extern "C" void lia_kv_scatter_ragged_launch(const bf16_t* ksrc, const bf16_t* v
                                              int b0, const int* lens, hipStream_t st);
 extern "C" void lia_argmax_launch(const bf16_t* logits, int64_t* out, int B, int vocab, int suppress, hipStream_t st);
 extern "C" void lia_blit_launch(void* dst, const void* src, size_t bytes, hipStream_t st);
+// the MASKED instantiations (lia_ctx_set_token_mask): the launch above with the allowed-token bit rows -- row r of the call (the
+// verify launches: block row r0 + r) reads mask + r * ldm words, ldm >= ceil(vocab / 32), or 0 for one row shared by every row
+extern "C" void lia_argmax_masked_launch(const bf16_t* logits, int64_t* out, int B, int vocab, int suppress, const uint32_t* mask, long ldm,
+                                         hipStream_t st);
+extern "C" void lia_verify_argmax_masked_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress,
+                                                const int* n_suppress_rows, int T, int r0, int64_t* greedy, const uint32_t* mask, long ldm,
+                                                hipStream_t st);
+extern "C" void lia_sample_masked_launch(const bf16_t* logits, long ld, int B, int vocab, float tau, int top_k, float top_p, int suppress,
+                                         const float* uniforms, int64_t* out, float* stats, const uint32_t* mask, long ldm, hipStream_t st);
+extern "C" void lia_verify_sample_masked_launch(const bf16_t* logits, long ld, int n, int vocab, float tau, int top_k, float top_p,
+                                                int suppress, int n_suppress, const int* n_suppress_rows, int T, int r0,
+                                                const float* uniforms, long ldu, int n_steps, int step0, const int* step_rows,
+                                                const int64_t* block_ids, int64_t* sampled, float* p_draft, const uint32_t* mask, long ldm,
+                                                hipStream_t st);
 // lia_sample.hip, lia_score.hip
 extern "C" void lia_sample_launch(const bf16_t* logits, long ld, int B, int vocab, float tau, int top_k, float top_p, int suppress,
                                   const float* uniforms, int64_t* out, float* stats, hipStream_t st);
@@ -183,6 +197,11 @@ struct lia_ctx {
   int* row_lens_dev;
   int row_lens_cap;
   int row_lens_n;             // 0: no table
+  // allowed-token masks (lia_ctx_set_token_mask): the CALLER's device table -- only the pointer is kept.  While it is set the head
+  // calls (lm_head, sample, lm_verify*) take the MASKED kernel instantiations and row i of a call reads table row i
+  const uint32_t* token_mask;  // NULL: no table -- every head call is the unmasked one
+  long token_mask_ld;          // words between rows; 0: one row for every row
+  int token_mask_rows;
 };
 
 // the workspace is about to be reused: a norm the previous layer call chained into it is gone, and so is a pending hint

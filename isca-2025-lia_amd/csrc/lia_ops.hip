@@ -167,11 +167,35 @@ extern "C" int lia_attention_padded(const lia_bf16* q, long ldq, const lia_bf16*
   return LIA_OK;
 }
 
+// The allowed-token table of a head call on `rows` rows (lia_ctx_set_token_mask), checked against the call: LIA_OK with *mask = NULL
+// (no table: the unmasked launches) or the table and its pitch; the refusals by name.  The one place that words them.
+static int token_mask_of(const char* who, const lia_ctx* ctx, long rows, int vocab, const uint32_t** mask, long* ldm) {
+  *mask = nullptr;
+  *ldm = 0;
+  if (!ctx->token_mask) return LIA_OK;
+  const long W = ((long)vocab + 31) / 32;
+  if (ctx->token_mask_ld != 0 && ctx->token_mask_ld < W) {
+    lia_set_error("%s: the token mask has ldm=%ld words per row, vocab=%d needs ceil(vocab / 32) = %ld (or 0: one row for every row)", who,
+                  ctx->token_mask_ld, vocab, W);
+    return LIA_ERR_INVALID;
+  }
+  if (ctx->token_mask_ld != 0 && rows > ctx->token_mask_rows) {
+    lia_set_error("%s: the call has %ld rows, the token mask table %d (lia_ctx_set_token_mask)", who, rows, ctx->token_mask_rows);
+    return LIA_ERR_INVALID;
+  }
+  *mask = ctx->token_mask;
+  *ldm = ctx->token_mask_ld;
+  return LIA_OK;
+}
+
 // norm_b == nullptr: RMSNorm (Llama), else LayerNorm
 static int lm_head_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, int B, int T, int H, const bf16_t* norm_w, const bf16_t* norm_b,
                         const bf16_t* emb, int vocab, float eps, int suppress_token, bf16_t* logits, int64_t* next_ids, hipStream_t st) {
   size_t scratch = align_up((size_t)B * H * 2, 256);
   size_t gemm_need = (size_t)8 * B * vocab * 4;
+  const uint32_t* mask;
+  long ldm;
+  if (int mrc = token_mask_of(who, ctx, B, vocab, &mask, &ldm)) return mrc;
   if (ctx->ws_bytes < scratch) { lia_set_error("%s: workspace too small", who); return LIA_ERR_MEMORY; }
   ws_invalidate(ctx);
   bf16_t* lno = (bf16_t*)ctx->ws;
@@ -184,7 +208,8 @@ static int lm_head_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, int
   size_t have = ctx->ws_bytes - scratch;
   int rc = gemm_checked(ctx, lno, H, emb, B, vocab, H, ep, om, (float*)(ctx->ws + scratch), std::min(have, gemm_need), 0, st);
   if (rc) return rc;
-  lia_argmax_launch(logits, next_ids, B, vocab, suppress_token, st);
+  if (mask) lia_argmax_masked_launch(logits, next_ids, B, vocab, suppress_token, mask, ldm, st);
+  else lia_argmax_launch(logits, next_ids, B, vocab, suppress_token, st);
   HIP_TRY(hipGetLastError());
   return LIA_OK;
 }
@@ -228,7 +253,11 @@ extern "C" int lia_sample(lia_ctx* ctx, const lia_bf16* logits, long ld, int B, 
   if (ld < vocab) { lia_set_error("lia_sample: ld=%ld < vocab=%d", ld, vocab); return LIA_ERR_INVALID; }
   if (sample_settings_invalid("lia_sample", temperature, top_k, top_p)) return LIA_ERR_INVALID;
   if (suppress_token < -1 || suppress_token >= vocab) { lia_set_error("lia_sample: suppress_token=%d must be -1 or in [0, vocab)", suppress_token); return LIA_ERR_INVALID; }
-  lia_sample_launch(logits, ld, B, vocab, temperature, top_k, top_p, suppress_token, uniforms, next_ids, stats, (hipStream_t)stream);
+  const uint32_t* mask;
+  long ldm;
+  if (int mrc = token_mask_of("lia_sample", ctx, B, vocab, &mask, &ldm)) return mrc;
+  if (mask) lia_sample_masked_launch(logits, ld, B, vocab, temperature, top_k, top_p, suppress_token, uniforms, next_ids, stats, mask, ldm, (hipStream_t)stream);
+  else lia_sample_launch(logits, ld, B, vocab, temperature, top_k, top_p, suppress_token, uniforms, next_ids, stats, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return LIA_OK;
 }
@@ -338,8 +367,12 @@ static int lm_verify_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, l
   if ((long)B * T > 0x7fffffffL) { lia_set_error("%s: B=%d x T=%d rows", who, B, T); return LIA_ERR_INVALID; }
   if (n_suppress < 0 || n_suppress > T) { lia_set_error("%s: n_suppress=%d must be in [0, T=%d]", who, n_suppress, T); return LIA_ERR_INVALID; }
   if (suppress_token < -1 || (vocab > 0 && suppress_token >= vocab)) { lia_set_error("%s: suppress_token=%d must be -1 or in [0, vocab)", who, suppress_token); return LIA_ERR_INVALID; }
+  const uint32_t* mask;
+  long ldm;
+  if (int mrc = token_mask_of(who, ctx, (long)B * T, vocab, &mask, &ldm)) return mrc;
   const int rc = lm_rows_chunked(who, ctx, hidden, ldh, B * T, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
-    lia_verify_argmax_rows_launch(logits, vocab, n, vocab, suppress_token, n_suppress, n_suppress_rows, T, r0, greedy, st);
+    if (mask) lia_verify_argmax_masked_launch(logits, vocab, n, vocab, suppress_token, n_suppress, n_suppress_rows, T, r0, greedy, mask, ldm, st);
+    else lia_verify_argmax_rows_launch(logits, vocab, n, vocab, suppress_token, n_suppress, n_suppress_rows, T, r0, greedy, st);
   });
   if (rc) return rc;
   lia_verify_accept_launch(block_ids, greedy, active, B, T, accepted, common, next, st);
@@ -411,10 +444,18 @@ static int lm_verify_sample_impl(const char* who, lia_ctx* ctx, const bf16_t* hi
   if (smp->ldu < B) { lia_set_error("%s: ldu=%ld < B=%d", who, smp->ldu, B); return LIA_ERR_INVALID; }
   if (smp->n_steps < 1) { lia_set_error("%s: n_steps=%d must be >= 1", who, smp->n_steps); return LIA_ERR_INVALID; }
   if (smp->step0 < 0) { lia_set_error("%s: step0=%d must be >= 0", who, smp->step0); return LIA_ERR_INVALID; }
+  const uint32_t* mask;
+  long ldm;
+  if (int mrc = token_mask_of(who, ctx, (long)B * T, vocab, &mask, &ldm)) return mrc;
   hipError_t copy_err = hipSuccess;
   const int rc = lm_rows_chunked(who, ctx, hidden, ldh, B * T, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
-    lia_verify_sample_launch(logits, vocab, n, vocab, smp->temperature, smp->top_k, smp->top_p, suppress_token, n_suppress, n_suppress_rows,
-                             T, r0, smp->uniforms, smp->ldu, smp->n_steps, smp->step0, smp->step_rows, block_ids, sampled, p_draft, st);
+    if (mask)
+      lia_verify_sample_masked_launch(logits, vocab, n, vocab, smp->temperature, smp->top_k, smp->top_p, suppress_token, n_suppress,
+                                      n_suppress_rows, T, r0, smp->uniforms, smp->ldu, smp->n_steps, smp->step0, smp->step_rows, block_ids,
+                                      sampled, p_draft, mask, ldm, st);
+    else
+      lia_verify_sample_launch(logits, vocab, n, vocab, smp->temperature, smp->top_k, smp->top_p, suppress_token, n_suppress, n_suppress_rows,
+                               T, r0, smp->uniforms, smp->ldu, smp->n_steps, smp->step0, smp->step_rows, block_ids, sampled, p_draft, st);
     if (logits_out && copy_err == hipSuccess)
       copy_err = hipMemcpyAsync(logits_out + (size_t)r0 * vocab, logits, (size_t)n * vocab * sizeof(bf16_t), hipMemcpyDeviceToDevice, st);
   });
@@ -467,6 +508,11 @@ static int lm_verify_reject_impl(const char* who, lia_ctx* ctx, const bf16_t* hi
                                  const int32_t* n_suppress_rows, const lia_block_rejector* rej, const int64_t* block_ids,
                                  const int32_t* active, int64_t* token, int32_t* ok, int32_t* accepted, int32_t* common, int64_t* next,
                                  float* p_tok, float* q_tok, float* resid_mass, bf16_t* logits_out, hipStream_t st) {
+  if (ctx->token_mask) {
+    lia_set_error("%s: a token mask is set (lia_ctx_set_token_mask): rejection verification takes none -- the drafter's Q would have to be "
+                  "masked the same way", who);
+    return LIA_ERR_INVALID;
+  }
   if (!rej) { lia_set_error("%s: NULL rejector", who); return LIA_ERR_INVALID; }
   if (!rej->draft_logits) { lia_set_error("%s: NULL draft_logits", who); return LIA_ERR_INVALID; }
   if (!rej->u_acc) { lia_set_error("%s: NULL u_acc", who); return LIA_ERR_INVALID; }

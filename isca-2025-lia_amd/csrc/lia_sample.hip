@@ -30,8 +30,13 @@ __device__ __forceinline__ float score_of_key(int k, float tau) {
   return bf2f((bf16_t)h) / tau;                // the IEEE fp32 division of the contract
 }
 
-// keys of tokens i .. i + 7 (-1 past the end of the row); the suppressed token's key is that of -inf
-__device__ __forceinline__ void load_keys8(const bf16_t* __restrict__ row, int i, int vocab, bool vec, int suppress, int k[8]) {
+// keys of tokens i .. i + 7 (-1 past the end of the row); the suppressed token's key is that of -inf.  MASKED
+// (lia_ctx_set_token_mask): so is that of a token whose bit in the row's allowed-token mask is clear -- mrow: the mask row as bytes;
+// i is a multiple of 8, so byte i >> 3 holds the bits of exactly these 8 tokens.  The passes need nothing else: membership, the
+// histograms' bins and the weights are functions of the key.
+template <int MASKED = 0>
+__device__ __forceinline__ void load_keys8(const bf16_t* __restrict__ row, int i, int vocab, bool vec, int suppress, int k[8],
+                                           const uint8_t* __restrict__ mrow = nullptr) {
   if (vec && i < vocab) {            // vec: vocab % 8 == 0 and 16-byte aligned rows
     const uint4 v = *(const uint4*)(row + i);
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};
@@ -43,6 +48,14 @@ __device__ __forceinline__ void load_keys8(const bf16_t* __restrict__ row, int i
   }
   const unsigned d = (unsigned)(suppress - i);
   if (d < 8u) k[d] = SMP_KEY_NEG_INF;
+  if constexpr (MASKED) {
+    if (i < vocab) {
+      const uint32_t allow = mrow[i >> 3];
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (k[e] >= 0 && !((allow >> e) & 1u)) k[e] = SMP_KEY_NEG_INF;
+    }
+  }
 }
 
 // smallest key in (-inf, +inf] whose score is >= t (keys above SMP_KEY_NEG_INF: a -inf score is never kept)
@@ -118,8 +131,9 @@ struct SmpRow { int pick; float t_k, v_p, nkept, W2, w_draft; };
 // (the weight of a kept token is exp(s - m)), the same values in every thread.  t_k / v_p: lia_sample's boundary stats.
 struct SmpFilt { int kap2; float m, t_k, v_p; };
 
+template <int MASKED = 0>
 __device__ __forceinline__ SmpFilt filter_row(const bf16_t* __restrict__ row, int vocab, bool vec, float tau, int top_k, float top_p,
-                                              int suppress) {
+                                              int suppress, const uint8_t* __restrict__ mrow = nullptr) {
   uint32_t* cnt = (uint32_t*)hist;
 
   const int tid = threadIdx.x;
@@ -133,7 +147,7 @@ __device__ __forceinline__ SmpFilt filter_row(const bf16_t* __restrict__ row, in
   int kmax = -1;
   for (int i = tid * 8; i < vocab; i += SMP_TILE) {
     int k[8];
-    load_keys8(row, i, vocab, vec, suppress, k);
+    load_keys8<MASKED>(row, i, vocab, vec, suppress, k, mrow);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       kmax = max(kmax, k[e]);
@@ -160,7 +174,7 @@ __device__ __forceinline__ SmpFilt filter_row(const bf16_t* __restrict__ row, in
     __syncthreads();
     for (int i = tid * 8; i < vocab; i += SMP_TILE) {
       int k[8];
-      load_keys8(row, i, vocab, vec, suppress, k);
+      load_keys8<MASKED>(row, i, vocab, vec, suppress, k, mrow);
 #pragma unroll
       for (int e = 0; e < 8; ++e)
         if (k[e] >= 0 && (k[e] >> 4) == bk) atomicAdd((uint32_t*)&nib[k[e] & 15], 1u);
@@ -192,7 +206,7 @@ __device__ __forceinline__ SmpFilt filter_row(const bf16_t* __restrict__ row, in
     __syncthreads();
     for (int i = tid * 8; i < vocab; i += SMP_TILE) {
       int k[8];
-      load_keys8(row, i, vocab, vec, suppress, k);
+      load_keys8<MASKED>(row, i, vocab, vec, suppress, k, mrow);
 #pragma unroll
       for (int e = 0; e < 8; ++e)
         if (k[e] >= kap1) {
@@ -213,7 +227,7 @@ __device__ __forceinline__ SmpFilt filter_row(const bf16_t* __restrict__ row, in
     const int bp = sh_bin;
     for (int i = tid * 8; i < vocab; i += SMP_TILE) {
       int k[8];
-      load_keys8(row, i, vocab, vec, suppress, k);
+      load_keys8<MASKED>(row, i, vocab, vec, suppress, k, mrow);
 #pragma unroll
       for (int e = 0; e < 8; ++e)
         if (k[e] >= kap1 && (k[e] >> 4) == bp) {
@@ -249,12 +263,12 @@ __device__ __forceinline__ SmpFilt filter_row(const bf16_t* __restrict__ row, in
 // Passes A - E over one row by the whole LIA_ROW_THREADS workgroup: the one function lia_sample_kernel and lia_verify_sample_kernel
 // both draw with, so that a verify pass's token IS lia_sample's of the same logits and u.  u must be workgroup-uniform.  DRAFT: the
 // thread that meets token `draft` in pass E also leaves its kept weight (no further pass over the row).
-template <bool DRAFT>
+template <bool DRAFT, int MASKED = 0>
 __device__ __forceinline__ SmpRow sample_row(const bf16_t* __restrict__ row, int vocab, bool vec, float tau, int top_k, float top_p,
-                                             int suppress, float u, int draft) {
+                                             int suppress, float u, int draft, const uint8_t* __restrict__ mrow = nullptr) {
   const int tid = threadIdx.x;
   if (DRAFT && tid == 0) sh_wd = 0.f;              // (pass A's barrier orders it before the owner's store in pass E)
-  const SmpFilt f = filter_row(row, vocab, vec, tau, top_k, top_p, suppress);
+  const SmpFilt f = filter_row<MASKED>(row, vocab, vec, tau, top_k, top_p, suppress, mrow);
   const int kap2 = f.kap2;
   const float m = f.m, t_k = f.t_k, v_p = f.v_p;
 
@@ -265,7 +279,7 @@ __device__ __forceinline__ SmpRow sample_row(const bf16_t* __restrict__ row, int
   for (int j = 0; j < ntiles; ++j) {
     const int i = j * SMP_TILE + tid * 8;
     int k[8];
-    load_keys8(row, i, vocab, vec, suppress, k);
+    load_keys8<MASKED>(row, i, vocab, vec, suppress, k, mrow);
     float r = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e)
@@ -305,7 +319,7 @@ __device__ __forceinline__ SmpRow sample_row(const bf16_t* __restrict__ row, int
     // walk tile jc again: the same sums in the same order, then the first kept token whose running sum passes thr
     const int i = jc * SMP_TILE + tid * 8;
     int k[8];
-    load_keys8(row, i, vocab, vec, suppress, k);
+    load_keys8<MASKED>(row, i, vocab, vec, suppress, k, mrow);
     float wv[8], r = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -349,11 +363,15 @@ __device__ __forceinline__ SmpRow sample_row(const bf16_t* __restrict__ row, int
   return res;
 }
 
+// MASKED (lia_ctx_set_token_mask): row r draws under the allowed-token bit row mask + r * ldm (ldm words; 0: one row for every row)
+template <int MASKED>
 __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_sample_kernel(const bf16_t* __restrict__ logits, long ld, int vocab, int vec,
                                                                      float tau, int top_k, float top_p, int suppress,
                                                                      const float* __restrict__ uniforms, int64_t* __restrict__ out,
-                                                                     float* __restrict__ stats) {
-  const SmpRow r = sample_row<false>(logits + (long)blockIdx.x * ld, vocab, vec, tau, top_k, top_p, suppress, uniforms[blockIdx.x], -1);
+                                                                     float* __restrict__ stats, const uint32_t* __restrict__ mask, long ldm) {
+  const uint8_t* mrow = MASKED ? (const uint8_t*)(mask + (long)blockIdx.x * ldm) : nullptr;
+  const SmpRow r = sample_row<false, MASKED>(logits + (long)blockIdx.x * ld, vocab, vec, tau, top_k, top_p, suppress, uniforms[blockIdx.x], -1,
+                                             mrow);
   if (threadIdx.x == 0) {
     out[blockIdx.x] = r.pick;
     if (stats) {
@@ -372,14 +390,17 @@ __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_sample_kernel(const bf16_
 // step s = step_rows[b] (or step0) + t -- and u = 0 without a read at s >= n_steps, a position that can never be kept.  The table
 // entry is wave-uniform and goes through readfirstlane: the pass bounds that depend on it stay scalar.  p_draft (or NULL): the
 // probability that this position's draw confirms the draft token block_ids[b, t + 1] -- its kept weight over the kept mass, 0 where
-// it is not kept and at t = T - 1.
+// it is not kept and at t = T - 1.  MASKED (lia_ctx_set_token_mask): the BLOCK row's mask row, mask + r * ldm words (a chunk boundary
+// inside a block row changes r0, never r).
+template <int MASKED>
 __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_verify_sample_kernel(const bf16_t* __restrict__ logits, long ld, int vocab, int vec,
                                                                             float tau, int top_k, float top_p, int suppress,
                                                                             int n_suppress, const int* __restrict__ n_suppress_rows,
                                                                             int T, int r0, const float* __restrict__ uniforms, long ldu,
                                                                             int n_steps, int step0, const int* __restrict__ step_rows,
                                                                             const int64_t* __restrict__ block_ids,
-                                                                            int64_t* __restrict__ sampled, float* __restrict__ p_draft) {
+                                                                            int64_t* __restrict__ sampled, float* __restrict__ p_draft,
+                                                                            const uint32_t* __restrict__ mask, long ldm) {
   const int r = r0 + (int)blockIdx.x;
   const int b = r / T, t = r % T;
   const int sup = t < (n_suppress_rows ? __builtin_amdgcn_readfirstlane(n_suppress_rows[b]) : n_suppress) ? suppress : -1;
@@ -391,7 +412,8 @@ __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_verify_sample_kernel(cons
     const int64_t d = block_ids[(long)r + 1];
     draft = d >= 0 && d < (int64_t)vocab ? (int)d : -1;
   }
-  const SmpRow o = sample_row<true>(logits + (long)blockIdx.x * ld, vocab, vec, tau, top_k, top_p, sup, u, draft);
+  const uint8_t* mrow = MASKED ? (const uint8_t*)(mask + (long)r * ldm) : nullptr;
+  const SmpRow o = sample_row<true, MASKED>(logits + (long)blockIdx.x * ld, vocab, vec, tau, top_k, top_p, sup, u, draft, mrow);
   if (threadIdx.x == 0) {
     sampled[r] = o.pick;
     if (p_draft) p_draft[r] = o.w_draft > 0.f ? o.w_draft / o.W2 : 0.f;
@@ -585,8 +607,17 @@ extern "C" void lia_sample_launch(const bf16_t* logits, long ld, int B, int voca
                                   const float* uniforms, int64_t* out, float* stats, hipStream_t st) {
   if (B <= 0) return;
   const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
-  hipLaunchKernelGGL(lia_sample_kernel, dim3(B), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, tau, top_k, top_p, suppress,
-                     uniforms, out, stats);
+  hipLaunchKernelGGL(lia_sample_kernel<0>, dim3(B), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, tau, top_k, top_p, suppress,
+                     uniforms, out, stats, (const uint32_t*)nullptr, 0L);
+}
+
+// mask: device, row r at mask + r * ldm words (ldm >= ceil(vocab / 32), or 0: one row for every row)
+extern "C" void lia_sample_masked_launch(const bf16_t* logits, long ld, int B, int vocab, float tau, int top_k, float top_p, int suppress,
+                                         const float* uniforms, int64_t* out, float* stats, const uint32_t* mask, long ldm, hipStream_t st) {
+  if (B <= 0) return;
+  const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
+  hipLaunchKernelGGL(lia_sample_kernel<1>, dim3(B), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, tau, top_k, top_p, suppress,
+                     uniforms, out, stats, mask, ldm);
 }
 
 extern "C" void lia_verify_sample_launch(const bf16_t* logits, long ld, int n, int vocab, float tau, int top_k, float top_p, int suppress,
@@ -595,8 +626,21 @@ extern "C" void lia_verify_sample_launch(const bf16_t* logits, long ld, int n, i
                                          float* p_draft, hipStream_t st) {
   if (n <= 0) return;
   const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
-  hipLaunchKernelGGL(lia_verify_sample_kernel, dim3(n), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, tau, top_k, top_p, suppress,
-                     n_suppress, n_suppress_rows, T, r0, uniforms, ldu, n_steps, step0, step_rows, block_ids, sampled, p_draft);
+  hipLaunchKernelGGL(lia_verify_sample_kernel<0>, dim3(n), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, tau, top_k, top_p, suppress,
+                     n_suppress, n_suppress_rows, T, r0, uniforms, ldu, n_steps, step0, step_rows, block_ids, sampled, p_draft,
+                     (const uint32_t*)nullptr, 0L);
+}
+
+// mask: device, block row r0 + i of the chunk at mask + (r0 + i) * ldm words (ldm >= ceil(vocab / 32), or 0: one row for every row)
+extern "C" void lia_verify_sample_masked_launch(const bf16_t* logits, long ld, int n, int vocab, float tau, int top_k, float top_p,
+                                                int suppress, int n_suppress, const int* n_suppress_rows, int T, int r0,
+                                                const float* uniforms, long ldu, int n_steps, int step0, const int* step_rows,
+                                                const int64_t* block_ids, int64_t* sampled, float* p_draft, const uint32_t* mask, long ldm,
+                                                hipStream_t st) {
+  if (n <= 0) return;
+  const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
+  hipLaunchKernelGGL(lia_verify_sample_kernel<1>, dim3(n), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, tau, top_k, top_p, suppress,
+                     n_suppress, n_suppress_rows, T, r0, uniforms, ldu, n_steps, step0, step_rows, block_ids, sampled, p_draft, mask, ldm);
 }
 
 extern "C" void lia_verify_reject_launch(const bf16_t* logits, long ld, int n, int vocab, const bf16_t* draft_logits, long ldd_row,

@@ -95,15 +95,20 @@ extern "C" void lia_token_logprobs_launch(const bf16_t* logits, long ld, int M, 
 // ------------------------------------------------------------------------------------------------
 // lia_argmax_kernel's scan and tie rule over row r0 + blockIdx.x of the block; `suppress` counts as -inf where the row's block
 // position (r0 + blockIdx.x) % T is below n_suppress -- or, with n_suppress_rows (int32 per block row b = (r0 + blockIdx.x) / T, or
-// NULL), below n_suppress_rows[b]
+// NULL), below n_suppress_rows[b].  MASKED (lia_ctx_set_token_mask): a token whose bit in the BLOCK row's mask row,
+// mask + (r0 + blockIdx.x) * ldm words, is clear counts as -inf too; the lane's 8 tokens start at a multiple of 8, so one mask byte
+// covers them on both load paths (bits at or beyond vocab are never looked at).
+template <int MASKED>
 __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_verify_argmax_kernel(const bf16_t* __restrict__ logits, long ld, int vocab, int vec,
                                                                             int suppress, int n_suppress, int T, int r0,
                                                                             int64_t* __restrict__ greedy,
-                                                                            const int* __restrict__ n_suppress_rows) {
+                                                                            const int* __restrict__ n_suppress_rows,
+                                                                            const uint32_t* __restrict__ mask, long ldm) {
   __shared__ float sv[LIA_ROW_WAVES];
   __shared__ int si[LIA_ROW_WAVES];
   const int tid = threadIdx.x, lane = tid & 63;
   const bf16_t* row = logits + (long)blockIdx.x * ld;
+  const uint8_t* mrow = MASKED ? (const uint8_t*)(mask + (long)(r0 + (int)blockIdx.x) * ldm) : nullptr;
   const int brow = (r0 + (int)blockIdx.x) / T;
   const int sup = (r0 + (int)blockIdx.x) % T < (n_suppress_rows ? n_suppress_rows[brow] : n_suppress) ? suppress : -1;
   float best = -INFINITY;
@@ -111,9 +116,12 @@ __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_verify_argmax_kernel(cons
   for (int i = tid * 8; i < vocab; i += LIA_ROW_THREADS * 8) {
     float f[8];
     load_logits8(row, i, vocab, vec, f);
+    uint32_t allow = 0xffu;
+    if constexpr (MASKED) allow = mrow[i >> 3];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float v = i + e == sup ? -INFINITY : f[e];
+      float v = i + e == sup ? -INFINITY : f[e];
+      if constexpr (MASKED) v = (allow >> e) & 1u ? v : -INFINITY;
       if (i + e < vocab && (v > best || (v == best && i + e < bi))) { best = v; bi = i + e; }
     }
   }
@@ -161,8 +169,18 @@ extern "C" void lia_verify_argmax_rows_launch(const bf16_t* logits, long ld, int
                                               const int* n_suppress_rows, int T, int r0, int64_t* greedy, hipStream_t st) {
   if (n <= 0) return;
   const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
-  hipLaunchKernelGGL(lia_verify_argmax_kernel, dim3(n), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, suppress, n_suppress, T, r0, greedy,
-                     n_suppress_rows);
+  hipLaunchKernelGGL(lia_verify_argmax_kernel<0>, dim3(n), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, suppress, n_suppress, T, r0, greedy,
+                     n_suppress_rows, (const uint32_t*)nullptr, 0L);
+}
+
+// mask: device, block row r0 + i of the chunk at mask + (r0 + i) * ldm words (ldm >= ceil(vocab / 32), or 0: one row for every row)
+extern "C" void lia_verify_argmax_masked_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress,
+                                                const int* n_suppress_rows, int T, int r0, int64_t* greedy, const uint32_t* mask, long ldm,
+                                                hipStream_t st) {
+  if (n <= 0) return;
+  const int vec = (ld % 8 == 0) && (vocab % 8 == 0) && (((uintptr_t)logits & 15) == 0);
+  hipLaunchKernelGGL(lia_verify_argmax_kernel<1>, dim3(n), dim3(LIA_ROW_THREADS), 0, st, logits, ld, vocab, vec, suppress, n_suppress, T, r0, greedy,
+                     n_suppress_rows, mask, ldm);
 }
 
 extern "C" void lia_verify_argmax_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress, int T, int r0,

@@ -134,6 +134,7 @@ SIGNATURES = {
                                         c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "lia_ctx_set_key_starts": (c_int, [c_void_p, c_void_p, c_int]),
     "lia_ctx_set_row_lens": (c_int, [c_void_p, c_void_p, c_int]),
+    "lia_ctx_set_token_mask": (c_int, [c_void_p, c_void_p, c_long, c_int]),
     "lia_attn_block_takes": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "lia_embed_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "lia_lm_verify_rows": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p,

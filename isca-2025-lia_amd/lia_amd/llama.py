@@ -214,8 +214,10 @@ class LlamaScheduler:
         return self.hidden.get(B, T)
 
     def forward(self, input_ids, kv_state, gpu_percentage=100, num_minibatch=1, pin_weight=True, enable_cxl=False,
-                suppress_token=-1, sampler=None, **_ignored):
-        """sampler (sampling.Sampler, generate(do_sample=True)): the returned ids are its draw from the logits instead of their argmax"""
+                suppress_token=-1, sampler=None, token_mask=None, **_ignored):
+        """sampler (sampling.Sampler, generate(do_sample=True)): the returned ids are its draw from the logits instead of their argmax.
+        token_mask (int32 CUDA [B, W] or one broadcast row, constraints.Constraint): the allowed-token table of this call's head,
+        set on the context around lm_head and the sampler only (lia_ctx_set_token_mask)."""
         m, sh = self.model, self.model.shape
         lib = N.lib()
         B, T = input_ids.shape
@@ -225,11 +227,18 @@ class LlamaScheduler:
         logits = torch.empty((B, sh.vocab), dtype=torch.bfloat16, device="cuda")
         nxt_ids = torch.empty((B,), dtype=torch.int64, device="cuda")
         x_lm, T_lm = (x, T) if xlast is None else (xlast, 1)     # (the last layer already reduced the block to its last position)
-        N.check(lib.lia_llama_lm_head(ctx.handle, ctypes.c_void_p(x_lm.data_ptr()), B, T_lm, sh.hidden, ctypes.c_void_p(m.final_norm_w.data_ptr()),
-                                      ctypes.c_void_p(m.lm_head.data_ptr()), sh.vocab, sh.rms_eps, suppress_token,
-                                      ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(nxt_ids.data_ptr()), st), "lia_llama_lm_head")
-        if sampler is not None:
-            nxt_ids = sampler(ctx, logits, suppress_token)
+        if token_mask is not None:
+            ctx.set_token_mask(token_mask)
+        try:
+            ctx.token_mask_fits(sh.vocab)
+            N.check(lib.lia_llama_lm_head(ctx.handle, ctypes.c_void_p(x_lm.data_ptr()), B, T_lm, sh.hidden, ctypes.c_void_p(m.final_norm_w.data_ptr()),
+                                          ctypes.c_void_p(m.lm_head.data_ptr()), sh.vocab, sh.rms_eps, suppress_token,
+                                          ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(nxt_ids.data_ptr()), st), "lia_llama_lm_head")
+            if sampler is not None:
+                nxt_ids = sampler(ctx, logits, suppress_token)
+        finally:
+            if token_mask is not None:
+                ctx.set_token_mask(None)
         ctx.synchronize()
         kv_state.len += T
         return logits, nxt_ids
@@ -257,11 +266,11 @@ class LlamaScheduler:
         return lp.view(B, T), greedy.view(B, T)
 
     def verify(self, block_ids, kv_state, suppress_token=-1, n_suppress=0, active=None, gpu_percentage=100, num_minibatch=1,
-               pin_weight=True, enable_cxl=False, sampler=None, return_logits=False, rejector=None, **_ignored):
+               pin_weight=True, enable_cxl=False, sampler=None, return_logits=False, rejector=None, token_mask=None, **_ignored):
         """Speculative verification: OffloadScheduler.verify for a Llama -- the block [pending | draft] appended at kv_state.len,
         every position through the last layer with the block attention kernel, lia_llama_lm_verify; -> (ops.VerifyResult, common),
         kv_state.len = pos0 + common + 1.  sampler / return_logits / rejector: sampled and rejection verification, as
-        OffloadScheduler.verify."""
+        OffloadScheduler.verify.  token_mask (int32 CUDA [B, T, W] or one broadcast row): the verify head's allowed-token table."""
         check_verify_block(block_ids, kv_state)
         m, sh = self.model, self.model.shape
         pos0 = kv_state.len
@@ -273,14 +282,20 @@ class LlamaScheduler:
                 self.ctx.set_option(N.LIA_OPT_BLOCK_ATTENTION, 0)
         ids_dev = block_ids.to(device="cuda", dtype=torch.int64).contiguous()
         act_dev = None if active is None else torch.as_tensor(active).to(device="cuda", dtype=torch.int32).contiguous()
-        if rejector is not None:
-            res = self.ctx.llama_lm_verify_reject(x, m.final_norm_w, m.lm_head, ids_dev, rejector, sh.rms_eps, suppress_token, n_suppress,
-                                                  active=act_dev, return_logits=return_logits, return_probs=True)
-        elif sampler is None:
-            res = self.ctx.llama_lm_verify(x, m.final_norm_w, m.lm_head, ids_dev, sh.rms_eps, suppress_token, n_suppress, act_dev)
-        else:
-            res = self.ctx.llama_lm_verify_sample(x, m.final_norm_w, m.lm_head, ids_dev, sampler, sh.rms_eps, suppress_token, n_suppress,
-                                                  active=act_dev, return_logits=return_logits, return_p_draft=True)
+        if token_mask is not None:
+            self.ctx.set_token_mask(token_mask)
+        try:
+            if rejector is not None:
+                res = self.ctx.llama_lm_verify_reject(x, m.final_norm_w, m.lm_head, ids_dev, rejector, sh.rms_eps, suppress_token, n_suppress,
+                                                      active=act_dev, return_logits=return_logits, return_probs=True)
+            elif sampler is None:
+                res = self.ctx.llama_lm_verify(x, m.final_norm_w, m.lm_head, ids_dev, sh.rms_eps, suppress_token, n_suppress, act_dev)
+            else:
+                res = self.ctx.llama_lm_verify_sample(x, m.final_norm_w, m.lm_head, ids_dev, sampler, sh.rms_eps, suppress_token, n_suppress,
+                                                      active=act_dev, return_logits=return_logits, return_p_draft=True)
+        finally:
+            if token_mask is not None:
+                self.ctx.set_token_mask(None)
         self.ctx.synchronize()
         common = int(res.common.item())
         kv_state.len = pos0 + common + 1
@@ -347,6 +362,14 @@ class LlamaScheduler:
                 pipe.release(idx)
             x, y = y, x
         return x, xlast
+
+    def set_token_mask(self, mask):
+        """None only (generate() when a constrained generation ends): no allowed-token table on the library context; as
+        OffloadScheduler.set_token_mask"""
+        if mask is not None:
+            raise ValueError("set_token_mask takes None only: a table is passed per call, forward(token_mask=) / verify(token_mask=)")
+        if self.ctx is not None:
+            self.ctx.set_token_mask(None)
 
     def stream_stats(self, reset=False):
         return self.pipe.stats(reset) if self.pipe else (0.0, 0.0)

@@ -48,6 +48,7 @@ class Context:
         self.device = device
         self.workspace_alloc_bytes = workspace_bytes
         self.stream = self.lib.lia_ctx_compute_stream(h)
+        self._token_mask = None          # (tensor [rows, W], ldm in words): the table lia_ctx_set_token_mask points at
 
     @property
     def workspace_bytes(self):
@@ -183,22 +184,66 @@ class Context:
         else:
             N.check(self.lib.lia_ctx_set_row_lens(self.handle, ctypes.c_void_p(lens.ctypes.data), lens.shape[0]), "lia_ctx_set_row_lens")
 
+    def set_token_mask(self, mask):
+        """lia_ctx_set_token_mask: mask (int32 CUDA tensor [..., W], W >= ceil(vocab / 32) words per row, rows contiguous; the leading
+        dimensions are flattened -- [B, W] for lm_head / sample, [B, T, W] for the verify heads; or None to clear).  Token i of row r is
+        allowed iff bit i & 31 of mask[r, i >> 5] is set; a token that is not counts as -inf in every head call on this context
+        until the table is cleared.  ONE row ([W] or [1, W]) serves every row of every call (ldm = 0).  The library keeps the pointer
+        only: this object keeps the tensor alive, the caller leaves it unchanged until the head call has run."""
+        if mask is None:
+            self._token_mask = None
+            N.check(self.lib.lia_ctx_set_token_mask(self.handle, None, 0, 0), "lia_ctx_set_token_mask")
+            return
+        if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype != torch.int32 or mask.dim() < 1 or not mask.is_contiguous():
+            raise ValueError("token mask: expected a contiguous int32 CUDA tensor [..., W], got "
+                             + (f"{mask.dtype} {mask.device} shape {tuple(mask.shape)}" if isinstance(mask, torch.Tensor) else type(mask).__name__))
+        m = mask.reshape(-1, mask.shape[-1])
+        if m.numel() == 0:
+            raise ValueError(f"token mask: an empty tensor of shape {tuple(mask.shape)}")
+        torch.cuda.current_stream().synchronize()              # (the library's stream reads what torch's wrote)
+        self._point_token_mask(m, 0)
+        self._token_mask = m
+
+    def token_mask_fits(self, vocab):
+        """the table's rows hold ceil(vocab / 32) words (the library checks the pitch of a table, not the width of a broadcast row)"""
+        m = self._token_mask
+        if m is not None and m.shape[1] < (vocab + 31) // 32:
+            raise ValueError(f"token mask: rows of {m.shape[1]} words, a vocabulary of {vocab} tokens needs {(vocab + 31) // 32}")
+
+    def _point_token_mask(self, m, r0):
+        """the table from row r0 of m on (one row: broadcast)"""
+        rows, W = m.shape
+        ldm = 0 if rows == 1 else W
+        N.check(self.lib.lia_ctx_set_token_mask(self.handle, ctypes.c_void_p(m.data_ptr() + 4 * r0 * ldm), ldm, rows - r0 if ldm else 1),
+                "lia_ctx_set_token_mask")
+
     LM_HEAD_ROWS = 256       # rows per lia_lm_head call (its argmax scratch is sized for that many)
 
     def lm_head(self, hidden, lnw, lnb, emb, eps=1e-5, suppress_token=-1, stream=None):
         """final LN + tied lm_head on the LAST position + argmax (models.py:424-431, greedy_search.py:367).  A batch beyond 256 rows
         (the reference's --batch-size 900 ... 1580 lines, llm/scripts/cxl_offloading.sh:13-39) goes through in chunks of 256 rows:
-        rows are independent, the results are those of one call."""
+        rows are independent, the results are those of one call.  With a token mask set (set_token_mask) chunk b0 reads the table
+        from its row b0 on; the table is pointed back at row 0 afterwards."""
         for t in (hidden, lnw, lnb, emb):
             _chk(t)
         B, T, H = hidden.shape
         vocab = emb.shape[0]
         logits = torch.empty((B, vocab), dtype=torch.bfloat16, device=hidden.device)
+        self.token_mask_fits(vocab)
         nxt = torch.empty((B,), dtype=torch.int64, device=hidden.device)
-        for b0 in range(0, B, self.LM_HEAD_ROWS):
-            nb = min(self.LM_HEAD_ROWS, B - b0)
-            N.check(self.lib.lia_lm_head(self.handle, _ptr(hidden[b0:b0 + nb]), nb, T, H, _ptr(lnw), _ptr(lnb), _ptr(emb), vocab, eps, suppress_token,
-                                         _ptr(logits[b0:b0 + nb]), _ptr(nxt[b0:b0 + nb]), self._st(stream)), "lia_lm_head")
+        tm = self._token_mask if B > self.LM_HEAD_ROWS else None
+        if tm is not None and 1 < tm.shape[0] < B:
+            raise ValueError(f"lia_lm_head: the call has {B} rows, the token mask table {tm.shape[0]}")
+        try:
+            for b0 in range(0, B, self.LM_HEAD_ROWS):
+                nb = min(self.LM_HEAD_ROWS, B - b0)
+                if tm is not None and b0:
+                    self._point_token_mask(tm, b0)
+                N.check(self.lib.lia_lm_head(self.handle, _ptr(hidden[b0:b0 + nb]), nb, T, H, _ptr(lnw), _ptr(lnb), _ptr(emb), vocab, eps, suppress_token,
+                                             _ptr(logits[b0:b0 + nb]), _ptr(nxt[b0:b0 + nb]), self._st(stream)), "lia_lm_head")
+        finally:
+            if tm is not None:
+                self._point_token_mask(tm, 0)
         return logits, nxt
 
     def sample(self, logits, temperature, top_k, top_p, uniforms, suppress_token=-1, stats=None, stream=None):
@@ -210,6 +255,7 @@ class Context:
                              f"shape {tuple(logits.shape)} strides {logits.stride()}")
         B, vocab = logits.shape
         _chk(uniforms, torch.float32)
+        self.token_mask_fits(vocab)
         if uniforms.numel() != B:
             raise ValueError(f"uniforms has {uniforms.numel()} entries, logits {B} rows")
         if stats is not None:
@@ -293,6 +339,7 @@ class Context:
         for t in (lnw, lnb, emb):
             _chk(t)
         B, T, H, out = self._verify_args(hidden, block_ids, active)
+        self.token_mask_fits(emb.shape[0])
         N.check(self.lib.lia_lm_verify(self.handle, _ptr(hidden), H, B, T, H, _ptr(lnw), _ptr(lnb), _ptr(emb), emb.shape[0], eps,
                                        int(suppress_token), int(n_suppress), _ptr(block_ids), _ptr(active), _ptr(out.greedy),
                                        _ptr(out.accepted), _ptr(out.common), _ptr(out.next), self._st(stream)), "lia_lm_verify")
@@ -307,6 +354,7 @@ class Context:
         B, T, H, out = self._verify_args(hidden, block_ids, active)
         if n_suppress_rows.numel() != B:
             raise ValueError(f"n_suppress_rows has {n_suppress_rows.numel()} entries, block_ids {B} rows")
+        self.token_mask_fits(emb.shape[0])
         N.check(self.lib.lia_lm_verify_rows(self.handle, _ptr(hidden), H, B, T, H, _ptr(lnw), _ptr(lnb), _ptr(emb), emb.shape[0], eps,
                                             int(suppress_token), _ptr(n_suppress_rows), _ptr(block_ids), _ptr(active), _ptr(out.greedy),
                                             _ptr(out.accepted), _ptr(out.common), _ptr(out.next), self._st(stream)), "lia_lm_verify_rows")
@@ -317,6 +365,7 @@ class Context:
         for t in (normw, lm):
             _chk(t)
         B, T, H, out = self._verify_args(hidden, block_ids, active)
+        self.token_mask_fits(lm.shape[0])
         N.check(self.lib.lia_llama_lm_verify(self.handle, _ptr(hidden), H, B, T, H, _ptr(normw), _ptr(lm), lm.shape[0], eps,
                                              int(suppress_token), int(n_suppress), _ptr(block_ids), _ptr(active), _ptr(out.greedy),
                                              _ptr(out.accepted), _ptr(out.common), _ptr(out.next), self._st(stream)), "lia_llama_lm_verify")
@@ -347,6 +396,7 @@ class Context:
         args = N.BlockSampler(float(block.temperature), int(block.top_k), float(block.top_p), U.data_ptr(), U.stride(0), U.shape[0],
                               int(block.step0), None if step_rows is None else step_rows.data_ptr())
         vocab = head.shape[0]
+        self.token_mask_fits(vocab)
         logits = torch.empty((B, T, vocab), dtype=torch.bfloat16, device=dev) if return_logits else None
         p_draft = torch.empty((B, T), dtype=torch.float32, device=dev) if return_p_draft else None
         N.check(getattr(self.lib, name)(self.handle, _ptr(hidden), H, B, T, H, *[_ptr(t) for t in norm], _ptr(head), vocab, eps,

@@ -142,8 +142,40 @@ def build_parser():
                    help="with --sampled-verify: draw = accept a draft token iff it equals the sampler's own draw; rejection = the draft model "
                         "samples its own logits and a token is accepted with probability min(1, p / q), else a draw of the residual "
                         "(an exact sample, but not the ids of plain --do-sample; common acceptance only, not with --draft-coupled)")
+    p.add_argument("--suppress-tokens", default=None, type=str,
+                   help="constrained decoding: token ids no row may emit, e.g. 5,6,7 (generate(suppress_tokens=): they count as -inf in "
+                        "the argmax and in the sampler)")
+    p.add_argument("--allowed-tokens-file", default=None, type=str,
+                   help="constrained decoding: ONE allow-list for every row and step -- a .npy of token ids, or text with one id per "
+                        "line; every other token counts as -inf (not with --acceptance row or --verify-rule rejection)")
     add_init_args(p)
     return p
+
+
+def constraint_kwargs(args, vocab):
+    """generate()'s constraint kwargs of the command line: none without --suppress-tokens / --allowed-tokens-file.  The allow-list is
+    turned into its complement, a suppress list: one static row, packed and uploaded once."""
+    import numpy as np
+    banned = set()
+    if getattr(args, "suppress_tokens", None):
+        try:
+            banned |= {int(v) for v in args.suppress_tokens.split(",") if v.strip()}
+        except ValueError:
+            raise SystemExit(f"[ERROR] --suppress-tokens takes comma-separated token ids, got {args.suppress_tokens!r}") from None
+    if getattr(args, "allowed_tokens_file", None):
+        path = args.allowed_tokens_file
+        try:
+            ids = np.load(path) if path.endswith(".npy") else np.loadtxt(path, dtype=np.int64, ndmin=1)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"[ERROR] --allowed-tokens-file {path}: {e}") from None
+        ids = np.asarray(ids).reshape(-1)
+        if ids.size == 0 or not np.issubdtype(ids.dtype, np.integer):
+            raise SystemExit(f"[ERROR] --allowed-tokens-file {path}: expected a non-empty list of integer token ids, got {ids.dtype} x {ids.size}")
+        if ids.min() < 0 or ids.max() >= vocab:
+            raise SystemExit(f"[ERROR] --allowed-tokens-file {path}: token id {int(ids.min() if ids.min() < 0 else ids.max())} is outside "
+                             f"the vocabulary [0, {vocab})")
+        banned |= set(range(vocab)) - set(ids.tolist())
+    return {"suppress_tokens": sorted(banned)} if banned else {}
 
 
 def check_spec_sample_flags(args):
@@ -678,6 +710,7 @@ def _main(args, rec=None):
         generate_kwargs["cpu_layers"] = args.cpu_layers
         if args.cpu_layers < 0 and args.cpu_layers_start is not None:
             generate_kwargs["cpu_layers_start"] = args.cpu_layers_start
+    generate_kwargs.update(constraint_kwargs(args, model.shape.vocab))
     spec_log = None
     if args.draft_model:
         spec_log = []

@@ -271,7 +271,7 @@ class OffloadScheduler:
     # the step record `s`; none reaches back.
     def forward(self, input_ids, kv_state, prefill_policy=1, decoding_policy=1, no_overlap=False, pin_weight=False,
                 gpu_percentage=0, num_minibatch=1, enable_cxl=False, max_new_tokens=None, suppress_token=-1, cpu_layers=0,
-                cpu_layers_start=None, sampler=None, append_policy=None):
+                cpu_layers_start=None, sampler=None, append_policy=None, token_mask=None):
         """cpu_layers (build-defined): with decoding policy 2, that many of the streamed layers run
         their decode step entirely on the host cores (policy 1, weights read in place) instead of crossing the link --
         the cooperative split of the reference taken per layer.  Prefill is unaffected (policy 0 for every layer).
@@ -280,7 +280,9 @@ class OffloadScheduler:
         sampler (sampling.Sampler, generate(do_sample=True)): the returned ids are its draw from the logits instead of their argmax.
         A multi-token call on a NON-EMPTY cache appends its block at positions kv_state.len .. (generate(past=)): it goes by the
         prefill policy like every multi-token call, or by append_policy = 2 where the caches live on the host -- q, k, v of the
-        block travel to the host attention instead of the cached prefix to the GPU (the one multi-token policy 2)."""
+        block travel to the host attention instead of the cached prefix to the GPU (the one multi-token policy 2).
+        token_mask (int32 CUDA [B, W] or one broadcast row [1, W], constraints.Constraint): the allowed-token table of this call's
+        head -- set on the context around lm_head and the sampler, cleared behind them (lia_ctx_set_token_mask)."""
         s = self._validate(input_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch, append_policy)
         self._place(s, kv_state, pin_weight, enable_cxl, max_new_tokens, cpu_layers, cpu_layers_start)
         m, sh, ctx = self.model, self.model.shape, self.ctx
@@ -291,9 +293,15 @@ class OffloadScheduler:
             hidden = self._host_layers(s.x, kv_state, s.n_gpu, s.B, s.T, s.pos0)  # resident prefix on the GPU, the rest on the CPU
         else:
             hidden = self._run_layers(s, kv_state)
-        logits, nxt = ctx.lm_head(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, sh.ln_eps, suppress_token)
-        if sampler is not None:
-            nxt = sampler(ctx, logits, suppress_token)
+        if token_mask is not None:
+            ctx.set_token_mask(token_mask)
+        try:
+            logits, nxt = ctx.lm_head(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, sh.ln_eps, suppress_token)
+            if sampler is not None:
+                nxt = sampler(ctx, logits, suppress_token)
+        finally:
+            if token_mask is not None:
+                ctx.set_token_mask(None)
         self._deliver(s, kv_state)
         return logits, nxt
 
@@ -338,7 +346,7 @@ class OffloadScheduler:
 
     def verify(self, block_ids, kv_state, suppress_token=-1, n_suppress=0, active=None, prefill_policy=1, decoding_policy=1,
                no_overlap=False, pin_weight=False, gpu_percentage=0, num_minibatch=1, enable_cxl=False, append_policy=None,
-               sampler=None, return_logits=False, rejector=None, **_decode_only):
+               sampler=None, return_logits=False, rejector=None, token_mask=None, **_decode_only):
         """Speculative verification: one pass of the weights over block_ids [B, T] = [pending | d_1 .. d_{T-1}]
         appended at kv_state.len on a NON-EMPTY cache.  forward()'s phases with the last layer on every position, lm_verify in
         place of lm_head and LIA_OPT_BLOCK_ATTENTION set around the layers; the K/V rows are delivered as in forward().  Returns
@@ -350,7 +358,8 @@ class OffloadScheduler:
         draws of U[step + t, b], res.p_draft the chance of each to confirm the draft; return_logits (with a sampler, for tests and
         measurements) also returns the block's logits.  rejector (sampling.RejectorBlock, rejection verification of a stochastic
         drafter's block): the head is lm_verify_reject -- res.greedy holds `token`, res.ok / p_tok / q_tok / resid_mass the accept
-        test.  Everything else is the same pass."""
+        test.  Everything else is the same pass.  token_mask (int32 CUDA [B, T, W] or one broadcast row): the allowed-token table of
+        the verify head, row (b, t) for block position t of row b; set around the head call only.  Not with a rejector."""
         from . import speculative
         check_verify_block(block_ids, kv_state)
         B, T = block_ids.shape
@@ -372,6 +381,20 @@ class OffloadScheduler:
                 hidden = self._run_layers(s, kv_state)
         finally:
             ctx.set_option(N.LIA_OPT_BLOCK_ATTENTION, 0)
+        if token_mask is not None:
+            ctx.set_token_mask(token_mask)
+        try:
+            res = self._verify_head(ctx, hidden, ids_dev, act_dev, suppress_token, n_suppress, sampler, rejector, return_logits)
+        finally:
+            if token_mask is not None:
+                ctx.set_token_mask(None)
+        self._deliver(s, kv_state)
+        common = int(res.common.item())
+        kv_state.len = pos0 + common + 1
+        return res, common
+
+    def _verify_head(self, ctx, hidden, ids_dev, act_dev, suppress_token, n_suppress, sampler, rejector, return_logits):
+        m, sh = self.model, self.model.shape
         if rejector is not None:
             res = ctx.lm_verify_reject(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, rejector, sh.ln_eps, suppress_token,
                                        n_suppress, active=act_dev, return_logits=return_logits, return_probs=True)
@@ -380,10 +403,7 @@ class OffloadScheduler:
         else:
             res = ctx.lm_verify_sample(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, sampler, sh.ln_eps, suppress_token,
                                        n_suppress, active=act_dev, return_logits=return_logits, return_p_draft=True)
-        self._deliver(s, kv_state)
-        common = int(res.common.item())
-        kv_state.len = pos0 + common + 1
-        return res, common
+        return res
 
     def verify_rows(self, block_ids, kv_state, row_lens, suppress_token=-1, n_suppress_rows=None, active=None, prefill_policy=1,
                     decoding_policy=1, no_overlap=False, pin_weight=False, gpu_percentage=0, num_minibatch=1, enable_cxl=False,
@@ -430,6 +450,15 @@ class OffloadScheduler:
         finally:
             kv_state.len = len0
         return res
+
+    def set_token_mask(self, mask):
+        """None (what generate() calls when a constrained generation ends, also after an exception): no allowed-token table on the
+        library context -- every later head call is the unmasked one.  forward(token_mask=) / verify(token_mask=) set a table
+        themselves, around their head call."""
+        if mask is not None:
+            raise ValueError("set_token_mask takes None only: a table is passed per call, forward(token_mask=) / verify(token_mask=)")
+        if self.ctx is not None:
+            self.ctx.set_token_mask(None)
 
     # -- left-padded batches (generation.generate(..., attention_mask=)) -----------------------------------------------------
     def set_key_starts(self, starts):

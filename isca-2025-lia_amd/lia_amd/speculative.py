@@ -435,7 +435,7 @@ def speculative_search_rows(model, sched, input_ids, max_new_tokens, min_new_tok
 
 def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, eos_token_id, pad_token_id, token_latency, lia,
                        draft, draft_tokens, spec_log=None, step_hook=None, max_steps=None, past=None, return_state=False,
-                       reserve_tokens=0, starts=None, sampler=None, rejector=None):
+                       reserve_tokens=0, starts=None, sampler=None, rejector=None, constraint=None):
     """_greedy_search with a drafter: the ordinary prefill, then rounds of propose -> verify -> append.  The EOS / pad / unfinished
     bookkeeping is applied token by token as the greedy loop applies it; a finished row is inactive (it never limits `common`, its
     block is pad tokens, as the greedy loop feeds them); a round ends behind the token at which a row finishes, so the cache holds
@@ -445,7 +445,10 @@ def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, 
     lia_sample(logits(prefix), U[s]) on either loop; the sampled ids stand where `greedy` stood.
     rejector (the generation's sampling.Rejector, in place of sampler: rejection verification): the first forward draws with U[0]; a
     round hands the drafter and the verify pass the view of step origin g, gives the view the drafter's draft_logits, and emits the
-    `common` draft tokens every active row accepted and then res.next -- per row its own accepted draft token or the head's token."""
+    `common` draft tokens every active row accepted and then res.next -- per row its own accepted draft token or the head's token.
+    constraint (constraints.Constraint; greedy and the draw rule): the first forward takes step 0's token mask, a verify pass one row
+    per (row, position) -- position t's built from ids + draft[:t].  The drafter is not told: a proposal the mask forbids is simply
+    not accepted, and the ids are those of the plain constrained run."""
     from .generation import GenerationState, turn_positions
     if rejector is not None:
         sampler = None
@@ -502,8 +505,9 @@ def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, 
         step_hook(0)
     tic = time.time()
     suppress = eos_token_id if (eos_token_id is not None and 0 < min_new_tokens) else -1
+    first_mask = {} if constraint is None else {"token_mask": constraint.step_mask(0, ids, unfinished, suppress)}
     _, nxt = sched.forward(first, kv, max_new_tokens=max_new_tokens, suppress_token=suppress,
-                           **_first_kw(sampler if rejector is None else rejector.sampler), **lia)
+                           **_first_kw(sampler if rejector is None else rejector.sampler), **first_mask, **lia)
     over, _ = append(nxt.cpu())
     latency_list.append(time.time() - tic)
     rnd = 0
@@ -528,8 +532,9 @@ def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, 
         block = torch.cat([ids_buf[:, T + g - 1:T + g], prop], dim=1)
         if rview is not None:
             rview.draft_logits = draft.draft_logits        # [B, k, vocab]: the Q behind prop (a finished row's is never looked at)
+        mask_kw = {} if constraint is None else {"token_mask": constraint.block_mask(g, ids_buf[:, :T + g], prop, active, sup_tok, n_sup)}
         res, common = sched.verify(block, kv, suppress_token=sup_tok, n_suppress=n_sup, active=active.to(torch.int32), **_verify_kw(view),
-                                   **_reject_kw(rview), **lia)
+                                   **_reject_kw(rview), **mask_kw, **lia)
         if rview is None:
             greedy = res.greedy.cpu()
         else:                                              # the accepted draft tokens, then each row's token behind them
