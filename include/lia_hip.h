@@ -439,11 +439,27 @@ int lia_llama_decode_layers(lia_ctx* ctx, const lia_llama_desc* d, int n_layers,
  *     attention kernel where (heads / kv_heads) * T <= 16 and its scores fit the LDS, the append kernels otherwise; row t is then
  *     bit for bit the decode attention over pos0 + t + 1 keys.  The speculative verify pass sets it around its layer calls, for
  *     the shapes where the kernel was measured faster (speculative.block_attention_pays).
- *   lia_ctx_get_counter(ctx, LIA_CNT_BLOCK_ATTENTION): block attention launches through this context. */
-enum { LIA_OPT_FUSE_COMBINE = 1, LIA_OPT_BLOCK_ATTENTION = 2 };
-enum { LIA_CNT_FUSED_COMBINE = 100, LIA_CNT_BLOCK_ATTENTION = 200 };
+ *   lia_ctx_get_counter(ctx, LIA_CNT_BLOCK_ATTENTION): block attention launches through this context.
+ *   LIA_OPT_SPLIT_DECODE (default 0): 1 = a decode-shaped attention (one query per row: T == 1, or the _last operators) over
+ *     S > lia_attn_split_chunk(head_dim) keys takes the split-key route -- the row's keys cut into chunks of that many keys, one
+ *     workgroup per (chunk, KV head, row), fp32 partial outputs added in chunk order; scores, softmax and every rounding point are
+ *     the one-workgroup kernel's, only the fp32 order of the P.V sum differs.  Whatever the option says, a layer call takes that
+ *     route where the one-workgroup kernel cannot hold the row's scores in LDS (S beyond ~4.6k keys at 8 query heads per KV head,
+ *     ~9.7k at 4, ~39k at 1), so a decode step has no limit on S.  The route's scratch, lia_attn_split_scratch_bytes(B, S, heads,
+ *     kv_heads, head_dim) bytes, lies in the context's workspace behind the layer call's own layout (lia_layer_workspace_bytes /
+ *     lia_llama_workspace_bytes of the call's rows): where it does not fit, a call sent there by the option alone takes the
+ *     one-workgroup kernel, and a call beyond that kernel returns LIA_ERR_MEMORY, naming the bytes, before anything is launched.
+ *   lia_ctx_get_counter(ctx, LIA_CNT_SPLIT_DECODE): split-key launches through this context. */
+enum { LIA_OPT_FUSE_COMBINE = 1, LIA_OPT_BLOCK_ATTENTION = 2, LIA_OPT_SPLIT_DECODE = 3 };
+enum { LIA_CNT_FUSED_COMBINE = 100, LIA_CNT_BLOCK_ATTENTION = 200, LIA_CNT_SPLIT_DECODE = 300 };
 int lia_ctx_set_option(lia_ctx* ctx, int key, long value);
 long lia_ctx_get_counter(lia_ctx* ctx, int key);
+/* Pure host arithmetic (no GPU is touched).  lia_attn_split_chunk: the keys per chunk of the split-key route, one constant per
+ * head_dim (32 / 64 / 128; 0 for any other).  lia_attn_split_scratch_bytes: the scratch of one split-key attention over B rows of
+ * S keys, a multiple of 256: bf16 scores [B][heads][chunks * chunk], fp32 chunk maxima [B][heads][chunks] and fp32 partial outputs
+ * [chunks][B][heads][head_dim], each rounded up to 256 bytes; 0 for a shape the route does not take. */
+int lia_attn_split_chunk(int head_dim);
+size_t lia_attn_split_scratch_bytes(int B, int S, int heads, int kv_heads, int head_dim);
 
 /* ---- host side of the cooperative policies -------------------------------------------------------
  * Indirect-access-KV masked MHA, csrc/cpu/aten/kernels/MaskedMultiHeadAttentionKrnl.cpp:513-842: fp32

@@ -840,6 +840,23 @@ template <int CTRL> __device__ __forceinline__ float dpp_f32(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
 }
 
+// The softmax of a decode-shaped row, shared by the one-workgroup kernel and the split-key route (lia_attn_split_softmax_kernel) so
+// that m, l and P are the same bits on both: e = exp(s - m) with the row maximum m; l summed by thread j % 256 over its keys in
+// order, then over the wave, then over the four waves left to right; P = bf16(e / l).
+//   load(j): the bf16-rounded score of key j;  store(j, e): where the caller keeps e (the split route recomputes it instead)
+template <typename Load, typename Store>
+__device__ __forceinline__ float lia_attn_exp_sum(int tid, int S, float m, Load load, Store store) {
+  float ls = 0.f;
+  for (int j = tid; j < S; j += 256) {
+    float e = __expf(load(j) - m);
+    store(j, e);
+    ls += e;
+  }
+  return wave_sum(ls);
+}
+__device__ __forceinline__ float lia_attn_fold_waves(const float* w) { return w[0] + w[1] + w[2] + w[3]; }
+__device__ __forceinline__ float lia_attn_prob(float e, float l) { return rbf(e / l); }
+
 // PADDED: the row's keys are kstart .. Sp - 1 (kstart = starts[b] <= the query's position Sp - 1): the keys of a sequence of Sp - kstart
 // tokens starting at kstart, as in the prefill kernels -- the key loop starts at kstart, no key below it is read.
 // starts: per served row b (the caller passes its table + b0); PADDED = 0 never reads it
@@ -944,23 +961,17 @@ __global__ __launch_bounds__(256) void lia_attn_decode_kernel(const bf16_t* __re
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     mrow[g] = fmaxf(fmaxf(scratch[g * 8], scratch[g * 8 + 1]), fmaxf(scratch[g * 8 + 2], scratch[g * 8 + 3]));
-    float ls = 0.f;
-    for (int j = tid; j < S; j += 256) {
-      float e = __expf(sc[g * Spad + j] - mrow[g]);
-      sc[g * Spad + j] = e;
-      ls += e;
-    }
-    ls = wave_sum(ls);
+    const float ls = lia_attn_exp_sum(tid, S, mrow[g], [&](int j) { return sc[g * Spad + j]; }, [&](int j, float e) { sc[g * Spad + j] = e; });
     if (lane == 0) scratch[g * 8 + 4 + wave] = ls;
   }
   __syncthreads();
 #pragma unroll
-  for (int g = 0; g < G; ++g) lrow[g] = scratch[g * 8 + 4] + scratch[g * 8 + 5] + scratch[g * 8 + 6] + scratch[g * 8 + 7];
+  for (int g = 0; g < G; ++g) lrow[g] = lia_attn_fold_waves(scratch + g * 8 + 4);
   // probabilities once per (head, key) -- bf16(e / l), the reference's rounding point -- instead of once per lane of the
   // key in the P.V loop below (LPK lanes would each repeat the division)
 #pragma unroll
   for (int g = 0; g < G; ++g)
-    for (int j = tid; j < S; j += 256) sc[g * Spad + j] = rbf(sc[g * Spad + j] / lrow[g]);
+    for (int j = tid; j < S; j += 256) sc[g * Spad + j] = lia_attn_prob(sc[g * Spad + j], lrow[g]);
   __syncthreads();
 
   float o[G][8];
@@ -1179,6 +1190,355 @@ extern "C" int lia_attn_decode_padded_launch(const bf16_t* q, long ldq, const bf
                                              int S, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, hipStream_t st) {
   if (!starts) return -1;
   return decode_launch(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
+}
+
+// ---------------------------------------------------------------------------------------------
+// split-key decode (T == 1): the decode kernel's arithmetic with a row's keys cut into chunks of C keys, counted from the row's own
+// first key, and one workgroup per (chunk, KV head, batch row) -- no LDS that grows with S, and a grid that fills the chip at small
+// batches.  Four launches, every cross-workgroup dependency a kernel boundary (the per-XCD L2s are not coherent inside a launch):
+//   scores   (chunks, kv_heads, B)  s = bf16(q . k) [bf16(. scaling)] with the decode kernel's key pass -> scratch, bf16
+//                                   [row][head][Spad], and the chunk's maximum [row][head][chunk]
+//   softmax  (heads, B)             m over the chunk maxima, l in the decode kernel's order (lia_attn_exp_sum), the scores rewritten
+//                                   in place as P = bf16(exp(s - m) / l): 2 S bytes per head, served from L2
+//   pv       (chunks, kv_heads, B)  the chunk's P staged in LDS, the decode kernel's V pass and folds -> fp32 partial
+//                                   [chunk][row][head][D]
+//   combine                         the partials added in chunk order, bf16 through ldo.  No floating-point atomics anywhere.
+// Scores, m, l and P are bit for bit the one-workgroup kernel's; only the fp32 order of the P.V sum differs, and within a chunk the
+// keys keep that kernel's thread assignment and fold order (C is a multiple of its pass of U * KPP keys), so a row of S <= C keys
+// is the one-workgroup launch bit for bit.  A row's result depends on its own q, keys, S and C alone: not on B, b0, Bc or the other
+// rows; a padded row (keys from kstart = starts[b]) is the unpadded launch of its shifted sequence.
+// ---------------------------------------------------------------------------------------------
+// C per head_dim: a multiple of the pass (128 / 256 / 512 keys at d = 128 / 64 / 32), the smallest candidate of tools/attn_split_bench's
+// sweep over 256 / 512 / 1024 at every d: the route serves launches of few workgroups, where more chunks win up to S ~ 8k at B = 1
+// (Llama-3-8B heads, B 1, S 4096: 33.9 / 39.2 / 53.2 us); a larger C wins by 5 - 15 % from B x S ~ 32k on (results/attn_split_bench.txt).
+extern "C" int lia_attn_split_chunk(int d) {
+  switch (d) {
+    case 128: return 256;
+    case 64: return 256;
+    case 32: return 512;
+    default: return 0;
+  }
+}
+
+static int split_pass(int d) { return 8 * (256 / (d / 8)); }
+
+struct LiaSplitPlan { int nch, Spad; size_t scores, cmax, part, total; };   // byte offsets into the scratch, each 256-aligned
+static LiaSplitPlan split_plan(int B, int S, int heads, int d, int chunk) {
+  LiaSplitPlan p;
+  p.nch = (S + chunk - 1) / chunk;
+  p.Spad = p.nch * chunk;
+  size_t at = 0;
+  auto take = [&](size_t bytes) { size_t o = at; at = align_up(at + bytes, 256); return o; };
+  p.scores = take((size_t)B * heads * p.Spad * 2);
+  p.cmax = take((size_t)B * heads * p.nch * 4);
+  p.part = take((size_t)p.nch * B * heads * d * 4);
+  p.total = at;
+  return p;
+}
+
+static size_t split_scratch_bytes(int B, int S, int heads, int kv_heads, int d, int chunk) {
+  if (B <= 0 || S <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads || !(d == 32 || d == 64 || d == 128)) return 0;
+  if (chunk <= 0 || chunk % split_pass(d)) return 0;
+  return split_plan(B, S, heads, d, chunk).total;
+}
+
+// pure host arithmetic: the scratch lia_attn_decode_split_launch needs for B rows of S keys (0: a shape it refuses)
+extern "C" size_t lia_attn_split_scratch_bytes(int B, int S, int heads, int kv_heads, int d) {
+  return split_scratch_bytes(B, S, heads, kv_heads, d, lia_attn_split_chunk(d));
+}
+extern "C" size_t lia_attn_split_scratch_bytes_chunk(int B, int S, int heads, int kv_heads, int d, int chunk) {
+  return split_scratch_bytes(B, S, heads, kv_heads, d, chunk);
+}
+
+// sc: [B][heads][Spad] bf16 scores; cmax: [B][heads][nch].  C: keys per chunk
+template <int D, int G, int PADDED>
+__global__ __launch_bounds__(256) void lia_attn_split_scores_kernel(const bf16_t* __restrict__ q, long ldq, const bf16_t* __restrict__ kc,
+                                                                     bf16_t* __restrict__ sc, float* __restrict__ cmax, int Sp, int heads,
+                                                                     int kv_heads, int Bc, int b0, float scaling, int post_scale,
+                                                                     const int* __restrict__ starts, int C, int nch, int Spad) {
+  constexpr int LPK = D / 8;          // lanes per key
+  constexpr int KPP = 256 / LPK;      // keys per pass of the workgroup
+  constexpr int U = 8;
+  __shared__ float wmax[G * 4];
+  const int c = blockIdx.x, kh = blockIdx.y, b = blockIdx.z;
+  const int kstart = PADDED ? __builtin_amdgcn_readfirstlane(starts[b]) : 0;
+  const int c0 = c * C;
+  if (c0 >= Sp - kstart) return;     // a padded row of fewer chunks than the longest row (uniform over the workgroup)
+  const int S = min(C, Sp - kstart - c0);   // the keys of this chunk: c0 .. c0 + S - 1 of the row
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long kv_row = (long)Bc * kv_heads * D;
+  const bf16_t* kbase = kc + ((long)(b0 + b) * kv_heads + kh) * D + (long)(kstart + c0) * kv_row;
+  bf16_t* srow = sc + ((long)b * heads + (long)kh * G) * Spad + c0;
+  const float qscale = post_scale ? 1.0f : scaling;
+  const int sub = tid % LPK, kslot = tid / LPK;
+
+  typedef __attribute__((ext_vector_type(2))) __bf16 lia_bf16x2;
+  uint32_t qp[G][4];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    uint4 v = *(const uint4*)(q + (long)b * ldq + (long)(kh * G + g) * D + 8 * sub);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) qp[g][j] = pack_bf16x2(bf2f(w[j] & 0xffff) * qscale, bf2f(w[j] >> 16) * qscale);
+  }
+  float lmax[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) lmax[g] = -INFINITY;
+  // the decode kernel's key pass (U * KPP keys, every row requested before the first is used; the tail requests only rows that exist)
+  auto k_pass = [&](const int j0, auto tail) {
+    constexpr bool TAIL = decltype(tail)::value;
+    uint4 kv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int j = j0 + u * KPP + kslot;
+      if constexpr (TAIL) {
+        kv[u] = uint4{0u, 0u, 0u, 0u};
+        if (j < S) kv[u] = lia_ldg_stream(kbase + (long)j * kv_row + 8 * sub);
+      } else {
+        kv[u] = lia_ldg_stream(kbase + (long)j * kv_row + 8 * sub);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int j = j0 + u * KPP + kslot;
+      const uint32_t w[4] = {kv[u].x, kv[u].y, kv[u].z, kv[u].w};
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        float a = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          a = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(lia_bf16x2, qp[g][e]), __builtin_bit_cast(lia_bf16x2, w[e]), a, false);
+        if constexpr (LPK == 16) {
+          a += dpp_f32<0x128>(a);     // row_ror:8   (the decode kernel's butterfly)
+          a += dpp_f32<0x124>(a);     // row_ror:4
+          a += dpp_f32<0x4E>(a);      // quad_perm:[2,3,0,1]  (xor 2)
+          a += dpp_f32<0xB1>(a);      // quad_perm:[1,0,3,2]  (xor 1)
+        } else {
+#pragma unroll
+          for (int o = LPK / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+        }
+        if (!TAIL || j < S) {
+          float sv = rbf(a);
+          if (post_scale) sv = rbf(sv * scaling);
+          if (sub == 0) srow[(long)g * Spad + j] = f2bf(sv);   // (exact: sv is a bf16 value)
+          lmax[g] = fmaxf(lmax[g], sv);
+        }
+      }
+    }
+  };
+  const int s_full = S - S % (U * KPP);
+  for (int j0 = 0; j0 < s_full; j0 += U * KPP) k_pass(j0, std::false_type{});
+  if (s_full < S) k_pass(s_full, std::true_type{});
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    float m = wave_max(lmax[g]);
+    if (lane == 0) wmax[g * 4 + wave] = m;
+  }
+  __syncthreads();
+  if (tid < G)
+    cmax[((long)b * heads + (long)kh * G + tid) * nch + c] = fmaxf(fmaxf(wmax[tid * 4], wmax[tid * 4 + 1]), fmaxf(wmax[tid * 4 + 2], wmax[tid * 4 + 3]));
+}
+
+// one workgroup per (head, row): the head group's G rows are independent here, so each gets a workgroup of its own
+template <int PADDED>
+__global__ __launch_bounds__(256) void lia_attn_split_softmax_kernel(bf16_t* __restrict__ sc, const float* __restrict__ cmax, int Sp, int heads,
+                                                                      const int* __restrict__ starts, int C, int nch, int Spad) {
+  __shared__ float red[8];
+  const int h = blockIdx.x, b = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int kstart = PADDED ? __builtin_amdgcn_readfirstlane(starts[b]) : 0;
+  const int S = Sp - kstart;
+  const int n = (S + C - 1) / C;     // the row's own chunks
+  bf16_t* s = sc + ((long)b * heads + h) * Spad;
+  const float* cm = cmax + ((long)b * heads + h) * nch;
+  float m = -INFINITY;
+  for (int c = tid; c < n; c += 256) m = fmaxf(m, cm[c]);
+  m = wave_max(m);
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  const float ls = lia_attn_exp_sum(tid, S, m, [&](int j) { return bf2f(s[j]); }, [](int, float) {});
+  if (lane == 0) red[4 + wave] = ls;
+  __syncthreads();
+  const float l = lia_attn_fold_waves(red + 4);
+  // (e is computed again rather than kept: the same operation on the same bits, and the scratch stays 2 bytes per score)
+  for (int j = tid; j < S; j += 256) s[j] = f2bf(lia_attn_prob(__expf(bf2f(s[j]) - m), l));
+}
+
+// part: [nch][B][heads][D] fp32, part_stride = B * heads * D
+template <int D, int G, int PADDED>
+__global__ __launch_bounds__(256) void lia_attn_split_pv_kernel(const bf16_t* __restrict__ sc, const bf16_t* __restrict__ vc,
+                                                                 float* __restrict__ part, int Sp, int heads, int kv_heads, int Bc, int b0,
+                                                                 const int* __restrict__ starts, int C, int Spad, long part_stride) {
+  constexpr int LPK = D / 8;
+  constexpr int KPP = 256 / LPK;
+  constexpr int U = 8;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* p = (float*)smem;                    // [G][C] the chunk's probabilities
+  float* red = p + (size_t)G * C;             // [4 waves][G][D] partial outputs
+  const int c = blockIdx.x, kh = blockIdx.y, b = blockIdx.z;
+  const int kstart = PADDED ? __builtin_amdgcn_readfirstlane(starts[b]) : 0;
+  const int c0 = c * C;
+  if (c0 >= Sp - kstart) return;
+  const int S = min(C, Sp - kstart - c0);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long kv_row = (long)Bc * kv_heads * D;
+  const bf16_t* vbase = vc + ((long)(b0 + b) * kv_heads + kh) * D + (long)(kstart + c0) * kv_row;
+  const bf16_t* srow = sc + ((long)b * heads + (long)kh * G) * Spad + c0;
+  const int sub = tid % LPK, kslot = tid / LPK;
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+    for (int j = tid; j < S; j += 256) p[g * C + j] = bf2f(srow[(long)g * Spad + j]);
+  __syncthreads();
+
+  float o[G][8];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
+  // the decode kernel's V pass and folds on the chunk
+  auto v_pass = [&](const int j0, auto tail) {
+    constexpr bool TAIL = decltype(tail)::value;
+    uint4 vv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if constexpr (TAIL) {
+        vv[u] = uint4{0u, 0u, 0u, 0u};
+        if (j0 + u * KPP < S) vv[u] = lia_ldg_stream(vbase + (long)(j0 + u * KPP) * kv_row + 8 * sub);
+      } else {
+        vv[u] = lia_ldg_stream(vbase + (long)(j0 + u * KPP) * kv_row + 8 * sub);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int j = j0 + u * KPP;
+      if (!TAIL || j < S) {
+        const uint32_t w[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const float pj = p[g * C + j];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { o[g][2 * e] += pj * bf2f(w[e] & 0xffff); o[g][2 * e + 1] += pj * bf2f(w[e] >> 16); }
+        }
+      }
+    }
+  };
+  const int s_full = S - S % (U * KPP);
+  for (int j0 = 0; j0 < s_full; j0 += U * KPP) v_pass(j0 + kslot, std::false_type{});
+  if (s_full < S) v_pass(s_full + kslot, std::true_type{});
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float v = o[g][e];
+#pragma unroll
+      for (int off = LPK; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+      o[g][e] = v;
+    }
+  if (lane < LPK) {
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) red[((size_t)wave * G + g) * D + 8 * sub + e] = o[g][e];
+  }
+  __syncthreads();
+  float* prow = part + (long)c * part_stride + ((long)b * heads + (long)kh * G) * D;
+  for (int idx = tid; idx < G * D; idx += 256) {
+    const int g = idx / D, dd = idx - g * D;
+    prow[idx] = (red[(size_t)g * D + dd] + red[((size_t)G + g) * D + dd]) + (red[((size_t)2 * G + g) * D + dd] + red[((size_t)3 * G + g) * D + dd]);
+  }
+}
+
+// hd = heads * D values per row; a thread per output value adds its partials in chunk order
+template <int PADDED>
+__global__ __launch_bounds__(256) void lia_attn_split_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ out, long ldo, int Sp,
+                                                                      int hd, const int* __restrict__ starts, int C, long part_stride) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= part_stride) return;
+  const int b = (int)(idx / hd);
+  const int r = (int)(idx - (long)b * hd);
+  const int kstart = PADDED ? starts[b] : 0;
+  const int n = (Sp - kstart + C - 1) / C;
+  float acc = part[idx];
+  for (int c = 1; c < n; ++c) acc += part[(long)c * part_stride + idx];
+  out[(long)b * ldo + r] = f2bf(acc);
+}
+
+template <int D>
+static int launch_split(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int S, int heads,
+                        int kv_heads, int Bc, int b0, float scaling, int post_scale, const int* starts, int C, char* scratch, hipStream_t st) {
+  const int G = heads / kv_heads;
+  const LiaSplitPlan p = split_plan(B, S, heads, D, C);
+  bf16_t* sc = (bf16_t*)(scratch + p.scores);
+  float* cmax = (float*)(scratch + p.cmax);
+  float* part = (float*)(scratch + p.part);
+  const long part_stride = (long)B * heads * D;
+  const size_t lds = ((size_t)G * C + (size_t)4 * G * D) * sizeof(float);
+  if (lds > 64 * 1024) return -1;
+  const dim3 grid(p.nch, kv_heads, B);
+#define LIA_SPLIT_PD(GV, PD)                                                                                                                       \
+  hipLaunchKernelGGL((lia_attn_split_scores_kernel<D, GV, PD>), grid, dim3(256), 0, st, q, ldq, kc, sc, cmax, S, heads, kv_heads, Bc, b0, scaling, \
+                     post_scale, starts, C, p.nch, p.Spad);                                                                                        \
+  hipLaunchKernelGGL((lia_attn_split_softmax_kernel<PD>), dim3(heads, B), dim3(256), 0, st, sc, cmax, S, heads, starts, C, p.nch, p.Spad);         \
+  hipLaunchKernelGGL((lia_attn_split_pv_kernel<D, GV, PD>), grid, dim3(256), lds, st, sc, vc, part, S, heads, kv_heads, Bc, b0, starts, C, p.Spad, \
+                     part_stride);                                                                                                                 \
+  hipLaunchKernelGGL((lia_attn_split_combine_kernel<PD>), dim3((unsigned)((part_stride + 255) / 256)), dim3(256), 0, st, part, out, ldo, S,        \
+                     heads * D, starts, C, part_stride);
+#define LIA_SPLIT(GV) if (starts) { LIA_SPLIT_PD(GV, 1) } else { LIA_SPLIT_PD(GV, 0) }
+  switch (G) {
+    case 1: LIA_SPLIT(1) break;
+    case 2: LIA_SPLIT(2) break;
+    case 4: LIA_SPLIT(4) break;
+    case 8: LIA_SPLIT(8) break;
+    default: return -1;
+  }
+#undef LIA_SPLIT
+#undef LIA_SPLIT_PD
+  return 0;
+}
+
+static int split_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int S, int heads,
+                        int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, int chunk, void* scratch,
+                        size_t scratch_bytes, hipStream_t st) {
+  if (S < 1 || kv_heads <= 0 || heads <= 0 || heads % kv_heads) return -1;
+  const int G = heads / kv_heads;
+  if (!(G == 1 || G == 2 || G == 4 || G == 8)) return -1;
+  if (B <= 0) return 0;
+  const size_t need = split_scratch_bytes(B, S, heads, kv_heads, d, chunk);
+  if (!need || !scratch || scratch_bytes < need || B > 65535 || kv_heads > 65535) return -1;
+  const float scaling = 1.0f / sqrtf((float)d);
+  switch (d) {
+    case 128: return launch_split<128>(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, Bc, b0, scaling, post_scale, starts, chunk, (char*)scratch, st);
+    case 64: return launch_split<64>(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, Bc, b0, scaling, post_scale, starts, chunk, (char*)scratch, st);
+    case 32: return launch_split<32>(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, Bc, b0, scaling, post_scale, starts, chunk, (char*)scratch, st);
+    default: return -1;
+  }
+}
+
+// lia_attn_decode_launch's arguments and meaning (starts: lia_attn_decode_padded_launch's, or NULL = unpadded) through the four
+// launches above, for any S >= 1.  scratch: device memory of lia_attn_split_scratch_bytes(B, S, heads, kv_heads, d), owned by the
+// call until the stream has passed it.  -1, nothing launched: d or heads / kv_heads not instantiated, scratch too small, S < 1.
+extern "C" int lia_attn_decode_split_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int S,
+                                            int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, void* scratch,
+                                            size_t scratch_bytes, hipStream_t st) {
+  return split_launch(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, d, Bc, b0, post_scale, starts, lia_attn_split_chunk(d), scratch, scratch_bytes, st);
+}
+// the same with the chunk as an argument (a multiple of the pass; scratch of lia_attn_split_scratch_bytes_chunk): the bench's sweep
+extern "C" int lia_attn_decode_split_launch_chunk(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B,
+                                                  int S, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts,
+                                                  int chunk, void* scratch, size_t scratch_bytes, hipStream_t st) {
+  return split_launch(q, ldq, kc, vc, out, ldo, B, S, heads, kv_heads, d, Bc, b0, post_scale, starts, chunk, scratch, scratch_bytes, st);
+}
+
+// The route of a decode-shaped dispatch over S keys: 0 = the one-workgroup launch, 1 = split by LIA_OPT_SPLIT_DECODE (S > C),
+// 2 = split because the one-workgroup launcher refuses the shape for LDS.  0 for shapes the split launch does not take either.
+int lia_attn_split_route(int option, int S, int heads, int kv_heads, int d) {
+  if (S < 1 || kv_heads <= 0 || heads <= 0 || heads % kv_heads || !(d == 32 || d == 64 || d == 128)) return 0;
+  const int G = heads / kv_heads;
+  if (!(G == 1 || G == 2 || G == 4 || G == 8)) return 0;
+  const int Spad = (S + 3) & ~3;
+  if (((size_t)G * Spad + (size_t)4 * G * d + (size_t)G * 8) * sizeof(float) > 160 * 1024) return 2;
+  return option && S > lia_attn_split_chunk(d) ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1481,6 +1841,15 @@ int lia_attn_dispatch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t*
   }
   if (T > 1 && pos0 > 0 && !tail) return lia_attn_append_launch(q, ldq, kc, vc, out, ldo, B, T, pos0, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
   const LiaTail t = lia_tail(tail, B, T, ldq);
+  // the split-key route: by LIA_OPT_SPLIT_DECODE, and always where the one-workgroup launcher would refuse for LDS -- when the caller
+  // placed the scratch (a layer call does, behind its workspace layout); otherwise today's launch with today's arguments
+  if ((T == 1 || tail) && opts && opts->split_scratch && lia_attn_split_route(opts->split_decode, pos0 + T, heads, kv_heads, d)) {
+    if (lia_attn_decode_split_launch(q + t.off, t.ld, kc, vc, out, ldo, B, pos0 + T, heads, kv_heads, d, Bc, b0, post_scale, starts,
+                                     opts->split_scratch, opts->split_scratch_bytes, st))
+      return -1;
+    ++opts->split_launches;
+    return 0;
+  }
   if (T == 1 || tail) return decode_launch(q + t.off, t.ld, kc, vc, out, ldo, B, pos0 + T, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
   return prefill_launch(q, ldq, kc, vc, out, ldo, B, T, heads, kv_heads, d, Bc, b0, post_scale, starts, st);
 }

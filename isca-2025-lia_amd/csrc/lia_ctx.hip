@@ -216,6 +216,7 @@ extern "C" int lia_ctx_set_option(lia_ctx* c, int key, long value) {
   switch (key) {
     case LIA_OPT_FUSE_COMBINE: c->gemm_opts.fuse_combine = value ? 1 : 0; return LIA_OK;
     case LIA_OPT_BLOCK_ATTENTION: c->attn_opts.block_attention = value ? 1 : 0; return LIA_OK;
+    case LIA_OPT_SPLIT_DECODE: c->attn_opts.split_decode = value ? 1 : 0; return LIA_OK;
     default: lia_set_error("lia_ctx_set_option: unknown key %d", key); return LIA_ERR_INVALID;
   }
 }
@@ -223,6 +224,7 @@ extern "C" long lia_ctx_get_counter(lia_ctx* c, int key) {
   if (!c) return -1;
   if (key > LIA_CNT_FUSED_COMBINE && key <= LIA_CNT_FUSED_COMBINE + 4) return c->gemm_opts.fused_combines[key - LIA_CNT_FUSED_COMBINE];
   if (key == LIA_CNT_BLOCK_ATTENTION) return c->attn_opts.block_launches;
+  if (key == LIA_CNT_SPLIT_DECODE) return c->attn_opts.split_launches;
   return -1;
 }
 

@@ -104,6 +104,17 @@ extern "C" int lia_attn_block_launch(const bf16_t* q, long ldq, const bf16_t* kc
 extern "C" int lia_attn_block_ragged_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B,
                                             int T, int max_len, int heads, int kv_heads, int d, int Bc, int b0, int post_scale,
                                             const int* starts, const int* lens, hipStream_t st);
+// the split-key decode route (lia_attention.hip): lia_attn_decode_launch's arguments, starts or NULL, and the call's scratch of
+// lia_attn_split_scratch_bytes; -1 (nothing launched): d or heads / kv_heads not instantiated, scratch too small, S < 1.
+// lia_attn_split_chunk and lia_attn_split_scratch_bytes (include/lia_hip.h) are pure host arithmetic.
+extern "C" int lia_attn_decode_split_launch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int S,
+                                            int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, void* scratch,
+                                            size_t scratch_bytes, hipStream_t st);
+// ... with the chunk as an argument (a multiple of the kernel's pass), for tools/attn_split_bench's sweep
+extern "C" size_t lia_attn_split_scratch_bytes_chunk(int B, int S, int heads, int kv_heads, int d, int chunk);
+extern "C" int lia_attn_decode_split_launch_chunk(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B,
+                                                  int S, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts,
+                                                  int chunk, void* scratch, size_t scratch_bytes, hipStream_t st);
 
 // ---- helpers shared by the API files: C++ linkage, kept out of the dynamic symbol table
 #define LIA_HIDDEN __attribute__((visibility("hidden")))
@@ -130,10 +141,17 @@ static inline LiaTail lia_tail(int tail, int B, int T, long H) {
 //   T > 1 && pos0 > 0 && !tail -> append;  T == 1 || tail -> decode over S = pos0 + T keys (tail: the last query of each row);
 //   otherwise -> prefill;  starts != NULL: the padded instantiations.  Returns the launcher's 0 / -1.
 //   opts (nullable = defaults), LIA_OPT_BLOCK_ATTENTION set: the append case goes to the block launch where that takes the shape
+//   the decode case, when the caller placed split_scratch: the split-key launch where lia_attn_split_route says so
 struct LiaAttnOpts {
   int block_attention;      // 0 (default): append launch; 1: lia_attn_block_launch first (the speculative verify pass sets it)
   long block_launches;      // LIA_CNT_BLOCK_ATTENTION
+  int split_decode;         // LIA_OPT_SPLIT_DECODE: 0 (default): split only past the one-workgroup kernel's LDS bound; 1: whenever S > C
+  long split_launches;      // LIA_CNT_SPLIT_DECODE
+  void* split_scratch;      // the scratch of THIS call (a layer call places it behind its workspace layout), or NULL: never split
+  size_t split_scratch_bytes;
 };
+// 0: the one-workgroup launch; 1: split by the option (S > lia_attn_split_chunk); 2: split because that launch refuses S for LDS
+LIA_HIDDEN int lia_attn_split_route(int option, int S, int heads, int kv_heads, int d);
 LIA_HIDDEN int lia_attn_dispatch(const bf16_t* q, long ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, long ldo, int B, int T,
                                  int pos0, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, int tail,
                                  hipStream_t st, LiaAttnOpts* opts = nullptr);

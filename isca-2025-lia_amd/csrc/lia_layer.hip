@@ -89,6 +89,28 @@ static int ensure_host_stage(lia_ctx* c, size_t bytes) {
   return LIA_OK;
 }
 
+// The split-key route's scratch for the GPU attention of one layer call over S keys (decode_shaped: one query per row), placed behind
+// the call's own workspace layout.  A call that does not take the route needs exactly the workspace it needed before; one sent there
+// by LIA_OPT_SPLIT_DECODE alone falls back to the one-workgroup kernel when the scratch does not fit; one beyond that kernel's LDS
+// bound is refused here, before anything is launched.
+static int split_scratch_place(lia_ctx* ctx, const char* who, bool decode_shaped, int B, int S, int heads, int kv_heads, int hd, size_t layout) {
+  LiaAttnOpts& o = ctx->attn_opts;
+  o.split_scratch = nullptr;
+  o.split_scratch_bytes = 0;
+  const int route = decode_shaped ? lia_attn_split_route(o.split_decode, S, heads, kv_heads, hd) : 0;
+  if (!route) return LIA_OK;
+  const size_t need = lia_attn_split_scratch_bytes(B, S, heads, kv_heads, hd);
+  if (layout + need > ctx->ws_bytes) {
+    if (route == 1) return LIA_OK;
+    lia_set_error("%s: workspace %zu < %zu + %zu bytes of split-key attention scratch (%d keys are beyond the one-workgroup decode kernel)",
+                  who, ctx->ws_bytes, layout, need, S);
+    return LIA_ERR_MEMORY;
+  }
+  o.split_scratch = ctx->ws + layout;
+  o.split_scratch_bytes = need;
+  return LIA_OK;
+}
+
 // tail = 1 (lia_layer_forward_last): LN1 and the q | k | v projection run on all B x T rows (the cache needs every K/V row), everything
 // behind them -- attention, out-proj, LN2, fc1, fc2 -- only on the LAST position of each row; y is then [B, 1, H].
 static int layer_forward_impl(lia_ctx* ctx, const lia_layer_desc* d, int policy, const void* const weights[16], const lia_bf16* x,
@@ -181,6 +203,8 @@ static int layer_forward_impl(lia_ctx* ctx, const lia_layer_desc* d, int policy,
     lia_set_error("lia_layer_forward: workspace %zu < %zu needed for %ld rows", ctx->ws_bytes, w.total, M);
     return LIA_ERR_MEMORY;
   }
+  rc = split_scratch_place(ctx, "lia_layer_forward", (T == 1 || tail) && policy != 2 && !ragged, B, pos0 + T, d->heads, d->heads, hd, w.total);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   {
     // a K/V delivery still draining from a slab of a DIFFERENT layout could overlap this call's buffers
@@ -424,6 +448,8 @@ static int llama_layer_forward_impl(lia_ctx* ctx, const lia_llama_desc* d, const
   const long Mt = tl.rows;
   const LlamaWs w = llama_ws(d, M);
   if (w.total > ctx->ws_bytes) { lia_set_error("lia_llama_layer_forward: workspace %zu < %zu", ctx->ws_bytes, w.total); return LIA_ERR_MEMORY; }
+  rc = split_scratch_place(ctx, "lia_llama_layer_forward", T == 1 || tail, B, pos0 + T, d->heads, d->kv_heads, hd, w.total);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   char* ws = ctx->ws;
   bf16_t *ln = (bf16_t*)(ws + w.ln), *qb = (bf16_t*)(ws + w.q), *ao = (bf16_t*)(ws + w.attn), *h1 = (bf16_t*)(ws + w.h1);

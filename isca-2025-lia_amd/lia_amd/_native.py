@@ -18,6 +18,8 @@ LIA_OK, LIA_ERR_INVALID, LIA_ERR_MEMORY, LIA_ERR_HIP, LIA_ERR_MISSING = 0, -1, -
 LIA_OPT_FUSE_COMBINE = 1           # lia_ctx_set_option keys (include/lia_hip.h)
 LIA_OPT_BLOCK_ATTENTION = 2        # the decode-shaped block attention kernel for a few queries behind a non-empty cache (verify)
 LIA_CNT_BLOCK_ATTENTION = 200      # block attention launches through the context
+LIA_OPT_SPLIT_DECODE = 3           # the split-key decode attention for every decode-shaped attention over more keys than one chunk
+LIA_CNT_SPLIT_DECODE = 300         # split-key decode launches through the context
 LIA_CNT_FUSED_COMBINE = 100        # lia_ctx_get_counter(ctx, LIA_CNT_FUSED_COMBINE + kind), kind = 1 LayerNorm, 2 RMSNorm, 3 SiLU*up, 4 RoPE
 
 c_void_p, c_int, c_long, c_size_t, c_float, c_double = (ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_size_t,
@@ -136,6 +138,8 @@ SIGNATURES = {
     "lia_ctx_set_row_lens": (c_int, [c_void_p, c_void_p, c_int]),
     "lia_ctx_set_token_mask": (c_int, [c_void_p, c_void_p, c_long, c_int]),
     "lia_attn_block_takes": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "lia_attn_split_chunk": (c_int, [c_int]),
+    "lia_attn_split_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "lia_embed_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "lia_lm_verify_rows": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

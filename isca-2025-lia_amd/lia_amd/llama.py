@@ -7,6 +7,7 @@ weights through the same WeightPipeline; the KV cache of every layer lives in HB
 OPT-only), i.e. every layer runs "policy 3" arithmetic.  Arithmetic = HF transformers' eager bf16 Llama.
 """
 import ctypes
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -184,8 +185,11 @@ class LlamaKVState:
 class LlamaScheduler:
     """forward(ids, kv, gpu_percentage=..., num_minibatch=...) -> (logits, next ids) on the device."""
 
-    def __init__(self, model, device=0, n_slots=4, pack=None):
+    def __init__(self, model, device=0, n_slots=4, pack=None, split_decode=None):
         self.model, self.device, self.n_slots = model, device, n_slots
+        # a decode step's attention: OffloadScheduler.split_decode ("measured" / True / False; LIA_SPLIT_DECODE)
+        self.split_decode = ops.split_decode_mode(os.environ.get("LIA_SPLIT_DECODE") if split_decode is None else split_decode,
+                                                  "LIA_SPLIT_DECODE" if split_decode is None else "split_decode")
         fmt = default_stream_format() if pack is None else pack
         self.pack = wire_format_code(fmt)
         self.ctx = self.pipe = None
@@ -193,10 +197,11 @@ class LlamaScheduler:
         self.prefill_tail = True      # last layer of a prefill: last position only behind q|k|v (False: every position)
         self.block_attention = "measured"     # a verify pass's attention: OffloadScheduler.block_attention
 
-    def _ensure(self, rows, B, T, n_gpu, smax, score_rows=0):
+    def _ensure(self, rows, B, T, n_gpu, smax, score_rows=0, split_bytes=0):
+        """split_bytes: the split-key attention scratch of a forward that takes that route, behind the layer call's own layout"""
         sh, lib = self.model.shape, N.lib()
         lm_bytes = 2 * 256 * sh.hidden + 8 * min(B, 256) * sh.vocab * 4 + (1 << 20)
-        need = max(lib.lia_llama_workspace_bytes(ctypes.byref(self.model.desc), rows), lm_bytes)
+        need = max(lib.lia_llama_workspace_bytes(ctypes.byref(self.model.desc), rows) + split_bytes, lm_bytes)
         if score_rows:       # a scoring pass: room for one chunk of lia_llama_lm_score (normed rows + bf16 logits)
             need = max(need, lib.lia_lm_score_workspace_bytes(score_rows, sh.hidden, sh.vocab))
         if self.ctx is None or need > self.ctx.workspace_bytes:
@@ -315,7 +320,32 @@ class LlamaScheduler:
         if m.placed_for != (n_gpu, bool(pin_weight), bool(enable_cxl), LayerStore._fmt_of(self.pack)):
             self.resident.replaced(self.pipe)
         m.place(n_gpu, pin_weight, enable_cxl, self.pack)
-        x, y = self._ensure(mini * T, B, T, n_gpu, kv_state.smax, score_rows=B * T if every_pos else 0)
+        pos0 = kv_state.len
+        # the split-key route of a decode-shaped attention (OffloadScheduler._split_decode_plan): a decode step by the rule of
+        # self.split_decode, a prefill's last-position-only last layer where the one-workgroup kernel cannot hold its keys
+        split_opt, split_bytes = 0, 0
+        if T == 1:
+            split_opt, split = ops.split_decode_for(self.split_decode, sh.head_dim, sh.heads, sh.kv_heads, mini, pos0 + 1)
+            split_bytes = ops.split_scratch_bytes(mini, max(pos0 + 1, kv_state.smax), sh.heads, sh.kv_heads, sh.head_dim) if split else 0
+        elif self.prefill_tail and not every_pos and ops.split_decode_forced(sh.head_dim, sh.heads, sh.kv_heads, pos0 + T):
+            split_bytes = ops.split_scratch_bytes(mini, pos0 + T, sh.heads, sh.kv_heads, sh.head_dim)
+        x, y = self._ensure(mini * T, B, T, n_gpu, kv_state.smax, score_rows=B * T if every_pos else 0, split_bytes=split_bytes)
+        ctx, pipe = self.ctx, self.pipe
+        st = ctypes.c_void_p(ctx.stream)
+        if split_opt:
+            ctx.set_option(N.LIA_OPT_SPLIT_DECODE, 1)
+        try:
+            return self._run_layers(input_ids, kv_state, x, y, n_gpu, minis, mini, every_pos, block_attention)
+        finally:
+            if split_opt:
+                ctx.set_option(N.LIA_OPT_SPLIT_DECODE, 0)
+
+    def _run_layers(self, input_ids, kv_state, x, y, n_gpu, minis, mini, every_pos, block_attention):
+        """the embedding and the layer calls of _layers, on the context and buffers it prepared"""
+        m, sh = self.model, self.model.shape
+        lib = N.lib()
+        B, T = input_ids.shape
+        L = sh.layers
         ctx, pipe = self.ctx, self.pipe
         st = ctypes.c_void_p(ctx.stream)
         pos0 = kv_state.len

@@ -88,6 +88,11 @@ class Context:
         """block attention launches through this context (N.LIA_OPT_BLOCK_ATTENTION set: the verify pass of speculative decoding)"""
         return self.lib.lia_ctx_get_counter(self.handle, N.LIA_CNT_BLOCK_ATTENTION)
 
+    def split_decode_launches(self):
+        """split-key decode attention launches through this context (N.LIA_OPT_SPLIT_DECODE set, or a cache beyond the one-workgroup
+        decode kernel's LDS bound)"""
+        return self.lib.lia_ctx_get_counter(self.handle, N.LIA_CNT_SPLIT_DECODE)
+
     def chain_next_norm(self, g_ptr, b_ptr=None):
         """lia_ctx_chain_next_norm: the next layer call also computes the first norm (weights g, b) of the layer after it."""
         N.check(self.lib.lia_ctx_chain_next_norm(self.handle, ctypes.c_void_p(g_ptr), ctypes.c_void_p(b_ptr) if b_ptr else None),
@@ -488,6 +493,76 @@ def block_attention_takes(heads, kv_heads, head_dim, T, S):
     """lia_attn_block_takes: whether the block attention launches (the ragged one included) take T queries per row whose last one
     sees S keys -- the launches' own rule, asked of the library"""
     return bool(N.lib().lia_attn_block_takes(int(heads), int(kv_heads), int(head_dim), int(T), int(S)))
+
+
+def split_chunk(head_dim):
+    """lia_attn_split_chunk: keys per chunk of the split-key decode attention (0: a head_dim it does not serve)"""
+    return N.lib().lia_attn_split_chunk(int(head_dim))
+
+
+def split_scratch_bytes(B, S, heads, kv_heads, head_dim):
+    """lia_attn_split_scratch_bytes: the scratch of one split-key decode attention over B rows of S keys (0: a shape it refuses)"""
+    return N.lib().lia_attn_split_scratch_bytes(int(B), int(S), int(heads), int(kv_heads), int(head_dim))
+
+
+DECODE_LDS_BYTES = 160 * 1024       # what the one-workgroup decode kernel may use (lia_attention.hip, launch_decode)
+
+
+def split_decode_forced(head_dim, heads, kv_heads, S):
+    """whether a decode-shaped attention over S keys is beyond the one-workgroup kernel -- its launcher's own bound,
+    (G Spad + 4 G d + 8 G) 4 bytes of LDS -- so that a layer call takes the split-key route whatever the option says"""
+    G = heads // kv_heads
+    return (G * ((S + 3) & ~3) + 4 * G * head_dim + 8 * G) * 4 > DECODE_LDS_BYTES
+
+
+# Shape classes where tools/attn_split_bench measured the split-key route's median below the one-workgroup launch's by more than the
+# run-to-run spread of the two legs (results/attn_split_bench.txt): (head_dim, heads / kv_heads, the most workgroups B * kv_heads of
+# the one-workgroup launch, the fewest keys S).  A class nobody measured keeps the one-workgroup launch.
+# Measured (MI355X, medians of 30 interleaved launches, split p90 below one-workgroup p10 in every listed class):
+#   d 128, G 1 (OPT-30B heads), 56 workgroups, S 2047: 27.6 us against 35.2 (S 1024: 20.2 against 20.6, inside the spread -> not listed;
+#     224 workgroups: the one-workgroup launch wins at every S)
+#   d 128, G 4 (Llama-3-8B heads), 8 / 32 workgroups from S 1030 (25.4 / 26.0 us against 36.6 / 36.8), 128 workgroups from S 4096
+#     (83.4 against 113.2; S 1030: 36.8 against 38.3, a 4 % margin -> not listed)
+#   d 64 / 32, G 4, 8 / 32 workgroups from S 4096 (30.8 / 37.4 us against 103.0 / 103.4; 29.0 / 32.2 against 56.3 / 60.1)
+SPLIT_DECODE_PAYS = (
+    (128, 1, 56, 2047),
+    (128, 4, 32, 1030),
+    (128, 4, 128, 4096),
+    (64, 4, 32, 4096),
+    (32, 4, 32, 4096),
+)
+SPLIT_DECODE_MAX_WORKGROUPS = 255   # a launch of B * kv_heads >= 256 workgroups fills the chip by itself: never by the table
+
+
+def split_decode_pays(head_dim, heads, kv_heads, B, S):
+    """the "measured" rule of a scheduler's split_decode: the table above"""
+    if kv_heads <= 0 or heads % kv_heads or B * kv_heads > SPLIT_DECODE_MAX_WORKGROUPS or S <= split_chunk(head_dim):
+        return False
+    G = heads // kv_heads
+    return any(d == head_dim and g == G and B * kv_heads <= wgs and S >= s_min for d, g, wgs, s_min in SPLIT_DECODE_PAYS)
+
+
+def split_decode_mode(value, what="split_decode"):
+    """a scheduler's split_decode from an argument, $LIA_SPLIT_DECODE or --split-decode: True / False / "measured"; anything else is
+    refused by name"""
+    if value is None:
+        return "measured"
+    if isinstance(value, bool):
+        return value
+    modes = {"1": True, "on": True, "true": True, "0": False, "off": False, "false": False, "measured": "measured"}
+    key = str(value).strip().lower()
+    if key not in modes:
+        raise ValueError(f"{what}={value!r}: one of 0 / off, 1 / on, measured")
+    return modes[key]
+
+
+def split_decode_for(mode, head_dim, heads, kv_heads, B, S):
+    """(LIA_OPT_SPLIT_DECODE of one decode step, whether the step takes the split-key route and so needs its scratch): mode True =
+    every step over more keys than one chunk, False = only beyond the one-workgroup kernel, "measured" = split_decode_pays"""
+    if split_decode_forced(head_dim, heads, kv_heads, S):
+        return 0, True
+    on = split_decode_pays(head_dim, heads, kv_heads, B, S) if mode == "measured" else bool(mode) and S > split_chunk(head_dim)
+    return int(on), bool(on)
 
 
 def make_desc(hidden, heads, ffn, eps=1e-5):

@@ -43,6 +43,13 @@ def add_stream_format_arg(p):
                         "reference ships); a model directory in the build's packed format defaults to the format on disk")
 
 
+def add_split_decode_arg(p):
+    p.add_argument("--split-decode", default=None, choices=["measured", "on", "off"],
+                   help="a decode step's GPU attention: the split-key route (a row's keys cut into chunks over many workgroups) where it "
+                        "was measured faster (measured: the default, or $LIA_SPLIT_DECODE), at every step over more keys than one chunk "
+                        "(on), or never (off); a cache beyond the one-workgroup kernel's LDS takes it whatever this says")
+
+
 def add_init_args(p):
     p.add_argument("--seed", default=0, type=int)
     p.add_argument("--init", default="normal", choices=["normal", "uniform01", "trained-like"],
@@ -56,14 +63,14 @@ def lia_kwargs_of(args):
                 enable_cxl=args.enable_cxl)
 
 
-def attach_scheduler(model, stream_format):
-    """the scheduler generate() / score() drive, with the wire format the command line names"""
+def attach_scheduler(model, stream_format, split_decode=None):
+    """the scheduler generate() / score() drive, with the wire format and the --split-decode mode the command line names"""
     if getattr(model, "family", "opt") == "llama":
         from .llama import LlamaScheduler
-        model._lia_scheduler = LlamaScheduler(model, pack=stream_format)
+        model._lia_scheduler = LlamaScheduler(model, pack=stream_format, split_decode=split_decode)
     else:
         from .scheduler import OffloadScheduler
-        model._lia_scheduler = OffloadScheduler(model, wire=stream_format)
+        model._lia_scheduler = OffloadScheduler(model, wire=stream_format, split_decode=split_decode)
     return model._lia_scheduler
 
 
@@ -98,6 +105,7 @@ def build_parser():
     add_lia_args(p)
     # build-specific
     add_stream_format_arg(p)
+    add_split_decode_arg(p)
     p.add_argument("--auto-plan", action="store_true",
                    help="measure this box (lia_amd.planner.calibrate, a few seconds) and let the planner choose --gpu-percentage, "
                         "the policies and --cpu-layers instead of the hand-picked values of llm/scripts/lia_*.sh")
@@ -699,7 +707,7 @@ def _main(args, rec=None):
         rec["_mem_samples"].append(_hi.cgroup_memory()["current"])
     if args.stream_format is None:
         args.stream_format = default_stream_format()
-    attach_scheduler(model, args.stream_format)                                     # generate() drives this scheduler
+    attach_scheduler(model, args.stream_format, args.split_decode)                  # generate() drives this scheduler
     if getattr(model, "family", "opt") == "llama":
         print(f"note: {model.shape.name} is a Llama: --prefill-policy / --decoding-policy have no counterpart (decoder.py:121-169); "
               f"gpu% {args.gpu_percentage} of the layers resident, the others streamed, every layer computed on the GPU")

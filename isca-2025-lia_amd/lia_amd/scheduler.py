@@ -129,8 +129,13 @@ def check_verify_rows(block_ids, kv_state, row_lens, flags, n_gpu, L):
 class OffloadScheduler:
     """forward(input_ids, kv_state, **lia flags) -> (logits [B,vocab], next_ids [B]) on the device."""
 
-    def __init__(self, model, device=0, n_slots=None, dp_group=None, wire=None, wire_cache=None, wire_cache_ws=None):
+    def __init__(self, model, device=0, n_slots=None, dp_group=None, wire=None, wire_cache=None, wire_cache_ws=None, split_decode=None):
         self.model, self.device, self.dp = model, device, dp_group
+        # a decode step's GPU attention: "measured" = the split-key route where it was measured faster than the one-workgroup kernel
+        # (ops.split_decode_pays), True = every step over more keys than one chunk (A/B runs, tests), False = never -- and always,
+        # whatever this says, where the cache has outgrown the one-workgroup kernel.  LIA_SPLIT_DECODE=0|1|measured.
+        self.split_decode = ops.split_decode_mode(os.environ.get("LIA_SPLIT_DECODE") if split_decode is None else split_decode,
+                                                  "LIA_SPLIT_DECODE" if split_decode is None else "split_decode")
         self.n_slots = n_slots or 4
         # decode steps and small blocks keep the first streamed layers in HBM in their wire format, in the streamer slots such
         # forwards have no use for (WeightPipeline.set_decode_mode); LIA_WIRE_CACHE=0: every layer crosses the link every step
@@ -179,12 +184,13 @@ class OffloadScheduler:
         self.host.time = value
 
     # -- resources -----------------------------------------------------------------------------------
-    def _ensure(self, rows, B, T, n_gpu, score_rows=0):
+    def _ensure(self, rows, B, T, n_gpu, score_rows=0, split_bytes=0):
         """Context workspace (sized by the largest layer call seen so far), streamer slots, hidden buffers.  score_rows: a scoring
-        pass also needs room for one chunk of lm_score (its normed rows and bf16 logits, lia_lm_score_workspace_bytes)."""
+        pass also needs room for one chunk of lm_score (its normed rows and bf16 logits, lia_lm_score_workspace_bytes).
+        split_bytes: the split-key attention scratch of a forward that takes that route, behind the layer call's own layout."""
         sh = self.model.shape
         lm_bytes = 2 * 256 * sh.hidden + 8 * min(B, 256) * sh.vocab * 4 + (1 << 20)
-        need = max(ops.workspace_bytes(self.model.desc, rows), lm_bytes)
+        need = max(ops.workspace_bytes(self.model.desc, rows) + split_bytes, lm_bytes)
         if score_rows:
             need = max(need, N.lib().lia_lm_score_workspace_bytes(score_rows, sh.hidden, sh.vocab))
         self._ws_need = need
@@ -211,6 +217,25 @@ class OffloadScheduler:
             torch.cuda.empty_cache()
             self.pipe = WeightPipeline(self.ctx, self.model, self.n_slots, self.dp)
         return self.hidden.get(B, T)
+
+    def _split_decode_plan(self, s, kv_state):
+        """(LIA_OPT_SPLIT_DECODE around this forward's layers, bytes of split-key scratch its workspace needs).  Only a forward with
+        a decode-shaped GPU attention has either: a decode step with resident layers or a GPU-attention policy (0 / 3), by the rule of
+        self.split_decode; a prefill whose last layer attends, for its last position only, more keys than the one-workgroup kernel
+        holds.  The scratch is sized for the cache's positions, not the step's, so that a generation sizes its workspace once."""
+        sh = self.model.shape
+        kvh = getattr(sh, "kv_heads", sh.heads)
+        gpu_attn = s.n_gpu > 0 or (s.policy in (0, 3) and not s.on_host)
+        if not gpu_attn:
+            return 0, 0
+        Bc = s.B if s.n_gpu > 0 else s.mini        # rows of the largest attention launch
+        S = s.pos0 + s.T
+        if s.is_prefill:
+            tail = self.prefill_tail and not s.every_pos and s.T > 1
+            forced = tail and ops.split_decode_forced(sh.head_dim, sh.heads, kvh, S)
+            return 0, (ops.split_scratch_bytes(Bc, S, sh.heads, kvh, sh.head_dim) if forced else 0)
+        opt, split = ops.split_decode_for(self.split_decode, sh.head_dim, sh.heads, kvh, Bc, S)
+        return opt, (ops.split_scratch_bytes(Bc, max(S, kv_state.smax), sh.heads, kvh, sh.head_dim) if split else 0)
 
     def _hold_caches(self, B, T, n_gpu):
         """Device holding caches [T, B, h, d] x 2 for every streamed layer (20.7 GB for OPT-30B at B = 64, T = 256), or None when
@@ -288,11 +313,17 @@ class OffloadScheduler:
         m, sh, ctx = self.model, self.model.shape, self.ctx
         ids_dev = input_ids.to("cuda", non_blocking=False).contiguous()
         ctx.embed_into(ids_dev, m.embed_tokens, m.embed_positions, s.x, s.pos0, starts=self._key_starts_for(s.B)[1])
-        if s.on_host:
-            self._await_kv(kv_state)
-            hidden = self._host_layers(s.x, kv_state, s.n_gpu, s.B, s.T, s.pos0)  # resident prefix on the GPU, the rest on the CPU
-        else:
-            hidden = self._run_layers(s, kv_state)
+        if s.split_opt:
+            ctx.set_option(N.LIA_OPT_SPLIT_DECODE, 1)
+        try:
+            if s.on_host:
+                self._await_kv(kv_state)
+                hidden = self._host_layers(s.x, kv_state, s.n_gpu, s.B, s.T, s.pos0)  # resident prefix on the GPU, the rest on the CPU
+            else:
+                hidden = self._run_layers(s, kv_state)
+        finally:
+            if s.split_opt:
+                ctx.set_option(N.LIA_OPT_SPLIT_DECODE, 0)
         if token_mask is not None:
             ctx.set_token_mask(token_mask)
         try:
@@ -582,7 +613,8 @@ class OffloadScheduler:
             # a policy-0 block appended to a non-empty cache parks the cached prefix and its own rows in the slab: mini (pos0 + T) rows
             # (a verify pass sizes the slab for the whole cache once: pos0 grows every round, and a larger workspace is a new context)
             rows = max(rows, s.mini * (kv_state.smax if s.verify else s.pos0 + T))
-        s.x, s.y = self._ensure(rows, B, T, n_gpu, score_rows=B * T if s.every_pos else 0)
+        s.split_opt, split_bytes = self._split_decode_plan(s, kv_state)
+        s.x, s.y = self._ensure(rows, B, T, n_gpu, score_rows=B * T if s.every_pos else 0, split_bytes=split_bytes)
         if is_prefill and s.policy == 0 and n_gpu < L and self.defer_kv and s.pos0 == 0:
             self._await_all_deliveries()          # (host-blocking: afterwards nothing on the D2H stream reads the holding caches)
             s.hold = self._hold_caches(B, T, n_gpu)
