@@ -632,7 +632,7 @@ int lia_stream_decode_cached(lia_streamer* s, int entry, int slot, const void* h
  *              lost to the rounding come off lend_bytes).  lend_bytes == 0: none.
  * Every entry starts on a multiple of 256 bytes of its allocation, keeps LIA_CACHE_READ_SLACK bytes behind entry_bytes and lies
  * inside one region.  offset[e] is entry e's byte offset from the start of ITS allocation (slots / staging / workspace); entries
- * 0 .. in_slots - 1 are in the slots, the next in_staging in the staging allocation, the last in_workspace in the workspace.
+ * 0 .. in_slots - 1 are in the slots, the next in_staging in the staging allocation, the next in_workspace in the workspace.
  * Returns LIA_OK -- with n_entries == 0 where the mode has nothing to offer: keep_slots < 1, keep_slots >= n_slots, no staging
  * allocation, entry_bytes == 0 -- or LIA_ERR_INVALID (*out zeroed) for a landing_stride larger than a staging area. */
 #define LIA_CACHE_MAX_ENTRIES 64
@@ -643,9 +643,14 @@ typedef struct lia_cache_geometry {
   size_t landing_stride;    /* distance between two landing buffers in the staging allocation */
   size_t landing_capacity;  /* the largest encoded layer lia_stream_land takes */
   size_t offset[LIA_CACHE_MAX_ENTRIES];
+  int in_extra;             /* the last in_extra entries lie in the streamer's extra allocation (lia_cache_geometry_plan_extra) */
 } lia_cache_geometry;
 int lia_cache_geometry_plan(int n_slots, size_t slot_bytes, size_t staging_bytes, int keep_slots, size_t entry_bytes, size_t landing_bytes,
                             size_t lend_offset, size_t lend_bytes, lia_cache_geometry* out);
+/* The same with a fourth region behind the workspace entries: the whole of an allocation of extra_bytes (lia_stream_cache_extra),
+ * offsets from its start.  extra_bytes == 0: lia_cache_geometry_plan, field for field. */
+int lia_cache_geometry_plan_extra(int n_slots, size_t slot_bytes, size_t staging_bytes, int keep_slots, size_t entry_bytes,
+                                  size_t landing_bytes, size_t lend_offset, size_t lend_bytes, size_t extra_bytes, lia_cache_geometry* out);
 /* Opt-in geometry of the decode mode, refused while the mode is on and sticky until changed; all zero = the geometry above
  * without it, bit for bit.
  *   landing_bytes: the largest encoded layer that will be landed.  Landing buffers shrink from a whole staging area to this (+ read
@@ -660,6 +665,16 @@ int lia_cache_geometry_plan(int n_slots, size_t slot_bytes, size_t staging_bytes
  * stream while a streamer of that context has this set.  lia_stream_cache_layout: the geometry lia_stream_cache_enable(s, keep_slots,
  * entry_bytes) would use now (its n_entries is lia_stream_cache_capacity); with the mode on, the one in use. */
 int lia_stream_cache_configure(lia_streamer* s, size_t landing_bytes, int lend_workspace, size_t workspace_keep_bytes);
+/* One more region of the decode mode, owned by the streamer: a device allocation of `bytes` -- what a model saves by holding its
+ * HBM-resident layers in their wire format -- that holds entries behind the workspace's.  Allocated, resized (another size) or freed
+ * (0) by this call alone, never by a mode change; refused while the mode is on; freed with the streamer. */
+int lia_stream_cache_extra(lia_streamer* s, size_t bytes);
+/* Decode a wire-format layer that already lies in device memory into `slot`, on the decode stream behind the slot's last release;
+ * no copy.  The slot is then waited for and released like any other and the launch counts in lia_stream_decode_stats.  With the
+ * decode mode on, slot < keep_slots; with it off, any slot of the ring (its next writer is ordered as by lia_stream_begin).
+ * src_device must stay readable for packed_bytes + LIA_CACHE_READ_SLACK until the decode has run.  Refused: an unknown format,
+ * n_values % 1024, n_values * 2 > slot_bytes. */
+int lia_stream_decode_device(lia_streamer* s, int slot, const void* src_device, size_t packed_bytes, size_t n_values, int format);
 int lia_stream_cache_layout(lia_streamer* s, int keep_slots, size_t entry_bytes, lia_cache_geometry* out);
 /* the workspace a call on this context may use now: what lia_ctx_create allocated, or the kept part while the rest is lent */
 size_t lia_ctx_workspace_bytes(lia_ctx* ctx);

@@ -1,4 +1,4 @@
-// lia_cache_geometry_plan (include/lia_hip.h): where the wire cache's entries lie in the memory the streamer and the context own.
+// lia_cache_geometry_plan / _plan_extra (include/lia_hip.h): where the wire cache's entries lie in the memory the streamer and the context own.
 // Pure arithmetic on sizes -- no HIP, no other file of the library -- so the streamer, the planner and a host-only test program
 // (tools/cache_geometry_sweep.cpp) share one answer.
 #include <string.h>
@@ -14,15 +14,16 @@ static int fill_region(size_t begin, size_t end, size_t stride, int room, size_t
   return n;
 }
 
-extern "C" int lia_cache_geometry_plan(int n_slots, size_t slot_bytes, size_t staging_bytes, int keep_slots, size_t entry_bytes,
-                                       size_t landing_bytes, size_t lend_offset, size_t lend_bytes, lia_cache_geometry* out) {
+extern "C" int lia_cache_geometry_plan_extra(int n_slots, size_t slot_bytes, size_t staging_bytes, int keep_slots, size_t entry_bytes,
+                                             size_t landing_bytes, size_t lend_offset, size_t lend_bytes, size_t extra_bytes,
+                                             lia_cache_geometry* out) {
   if (!out) return LIA_ERR_INVALID;
   memset(out, 0, sizeof(*out));
   if (n_slots < 1 || keep_slots < 1 || keep_slots >= n_slots || slot_bytes == 0 || staging_bytes == 0 || entry_bytes == 0) return LIA_OK;
   // sizes beyond any device's memory: refuse before a sum below could wrap
   const size_t huge = (size_t)1 << 48;
   if (slot_bytes > huge || staging_bytes > huge || entry_bytes > huge || landing_bytes > huge || lend_offset > huge || lend_bytes > huge ||
-      n_slots > 4096)
+      extra_bytes > huge || n_slots > 4096)
     return LIA_ERR_INVALID;
   const size_t landing_stride = landing_bytes ? up256(landing_bytes + LIA_CACHE_READ_SLACK) : staging_bytes;
   if (landing_stride > staging_bytes) return LIA_ERR_INVALID;
@@ -38,6 +39,14 @@ extern "C" int lia_cache_geometry_plan(int n_slots, size_t slot_bytes, size_t st
   n += out->in_staging;
   if (lend_bytes) out->in_workspace = fill_region(lend_offset, lend_offset + lend_bytes, out->entry_stride, LIA_CACHE_MAX_ENTRIES - n, out->offset + n);
   n += out->in_workspace;
+  // the streamer's extra allocation (lia_stream_cache_extra), whole: offsets from its start
+  if (extra_bytes) out->in_extra = fill_region(0, extra_bytes, out->entry_stride, LIA_CACHE_MAX_ENTRIES - n, out->offset + n);
+  n += out->in_extra;
   out->n_entries = n;
   return LIA_OK;
+}
+
+extern "C" int lia_cache_geometry_plan(int n_slots, size_t slot_bytes, size_t staging_bytes, int keep_slots, size_t entry_bytes,
+                                       size_t landing_bytes, size_t lend_offset, size_t lend_bytes, lia_cache_geometry* out) {
+  return lia_cache_geometry_plan_extra(n_slots, slot_bytes, staging_bytes, keep_slots, entry_bytes, landing_bytes, lend_offset, lend_bytes, 0, out);
 }

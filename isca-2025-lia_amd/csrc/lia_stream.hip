@@ -41,14 +41,16 @@ struct lia_streamer {
   int bounce_next;
   double bytes, busy_ms;
   // wire cache (lia_stream_cache_*, decode mode): while keep_slots != 0 a pool of geo.n_entries wire-format layers lies where
-  // lia_cache_geometry_plan put it -- the slots from keep_slots on, the staging allocation behind the keep_slots landing buffers
-  // (which no longer belong to a slot) and, when configured, the tail of the context's workspace
+  // lia_cache_geometry_plan_extra put it -- the slots from keep_slots on, the staging allocation behind the keep_slots landing buffers
+  // (which no longer belong to a slot), when configured the tail of the context's workspace, and the extra allocation
   int keep_slots;
   lia_cache_geometry geo;              // of the mode that is on (zeroed while it is off)
   // lia_stream_cache_configure: sticky, all zero = whole staging areas as landing buffers and no workspace entries
   size_t cfg_landing_bytes, cfg_keep_bytes;
   int cfg_lend;
   bool lent;                           // this mode holds the context's workspace tail
+  char* extra;                         // lia_stream_cache_extra: a fourth region, owned by the streamer (NULL: none)
+  size_t extra_bytes;
   hipEvent_t ws_fence;                 // on the compute stream when the workspace is lent
   std::vector<char> entry_filled;
   std::vector<const void*> entry_src;
@@ -118,6 +120,7 @@ extern "C" int lia_stream_create(lia_ctx* ctx, int n_slots, size_t slot_bytes, l
   s->dec_ms = s->dec_in = s->dec_out = 0; s->dec_launches = 0;
   s->keep_slots = 0; memset(&s->geo, 0, sizeof(s->geo)); s->cache_idle = nullptr; s->ring_next = 0;
   s->cfg_landing_bytes = s->cfg_keep_bytes = 0; s->cfg_lend = 0; s->lent = false; s->ws_fence = nullptr;
+  s->extra = nullptr; s->extra_bytes = 0;
   HIP_TRY(hipMalloc((void**)&s->slots, s->slot_bytes * n_slots));
   if (ctx->serialized) s->copy = ctx->compute;
   else HIP_TRY(hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking));
@@ -160,6 +163,7 @@ extern "C" void lia_stream_destroy(lia_streamer* s) {
     if (s->decode != s->ctx->compute) (void)hipStreamDestroy(s->decode);
     (void)hipFree(s->staging);
   }
+  if (s->extra) (void)hipFree(s->extra);
   if (s->copy != s->ctx->compute) (void)hipStreamDestroy(s->copy);
   delete s;
 }
@@ -397,13 +401,14 @@ static size_t cache_lend_range(const lia_streamer* s, size_t* offset) {
 static int cache_plan(const lia_streamer* s, int keep_slots, size_t entry_bytes, lia_cache_geometry* g) {
   size_t off = 0;
   const size_t lend = cache_lend_range(s, &off);
-  return lia_cache_geometry_plan(s->n_slots, s->slot_bytes, s->staging ? s->staging_bytes : 0, keep_slots, entry_bytes, s->cfg_landing_bytes,
-                                 off, lend, g);
+  return lia_cache_geometry_plan_extra(s->n_slots, s->slot_bytes, s->staging ? s->staging_bytes : 0, keep_slots, entry_bytes,
+                                       s->cfg_landing_bytes, off, lend, s->extra ? s->extra_bytes : 0, g);
 }
 static char* cache_entry_ptr(lia_streamer* s, int e) {
   if (e < s->geo.in_slots) return s->slots + s->geo.offset[e];
   if (e < s->geo.in_slots + s->geo.in_staging) return s->staging + s->geo.offset[e];
-  return s->ctx->ws + s->geo.offset[e];
+  if (e < s->geo.n_entries - s->geo.in_extra) return s->ctx->ws + s->geo.offset[e];
+  return s->extra + s->geo.offset[e];
 }
 static char* cache_landing_ptr(lia_streamer* s, int landing) { return s->staging + (size_t)landing * s->geo.landing_stride; }
 
@@ -417,6 +422,30 @@ extern "C" int lia_stream_cache_configure(lia_streamer* s, size_t landing_bytes,
   s->cfg_landing_bytes = landing_bytes;
   s->cfg_lend = lend_workspace ? 1 : 0;
   s->cfg_keep_bytes = lend_workspace ? workspace_keep_bytes : 0;
+  return LIA_OK;
+}
+
+extern "C" int lia_stream_cache_extra(lia_streamer* s, size_t bytes) {
+  if (!s) return LIA_ERR_INVALID;
+  if (s->keep_slots) { lia_set_error("lia_stream_cache_extra: the mode is on"); return LIA_ERR_INVALID; }
+  if (bytes == s->extra_bytes) return LIA_OK;
+  if (s->extra) {
+    // decodes of a mode that has ended may still read entries here
+    if (s->staging) HIP_TRY(hipStreamSynchronize(s->decode));
+    HIP_TRY(hipStreamSynchronize(s->copy));
+    HIP_TRY(hipFree(s->extra));
+    s->extra = nullptr; s->extra_bytes = 0;
+  }
+  if (bytes) {
+    // a fresh allocation: its first writer, the copy stream, needs no fence
+    if (hipMalloc((void**)&s->extra, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      s->extra = nullptr;
+      lia_set_error("lia_stream_cache_extra: no device memory for %zu bytes", bytes);
+      return LIA_ERR_MEMORY;
+    }
+    s->extra_bytes = bytes;
+  }
   return LIA_OK;
 }
 
@@ -552,6 +581,21 @@ extern "C" int lia_stream_decode_cached(lia_streamer* s, int entry, int slot, co
   }
   if (int rc = cache_claim_slot(s, slot)) return rc;
   if (int rc = launch_decode(s, at, slot, n_values, format, (double)packed_bytes)) return rc;
+  return cache_slot_ready(s, slot);
+}
+
+// A wire-format layer that lies in device memory already (a resident layer the model holds packed): decode only.  Mode on or off,
+// the decode stream is the slot's next writer, behind its last consumer and whatever was queued into it before.
+extern "C" int lia_stream_decode_device(lia_streamer* s, int slot, const void* src_device, size_t packed_bytes, size_t n_values, int format) {
+  if (!s || slot < 0 || slot >= s->n_slots || (s->keep_slots && slot >= s->keep_slots) || !src_device || packed_bytes == 0 ||
+      n_values * 2 > s->slot_bytes || !wire_format_known(format) || (n_values % 1024)) {
+    lia_set_error("lia_stream_decode_device: slot=%d bytes=%zu n_values=%zu format=%d (%d slots%s)", slot, packed_bytes, n_values, format,
+                  s ? s->n_slots : 0, s && s->keep_slots ? ", decode mode on" : "");
+    return LIA_ERR_INVALID;
+  }
+  if (int rc = ensure_staging(s)) return rc;            // the decode stream and its timing events live with the staging areas
+  if (int rc = cache_claim_slot(s, slot)) return rc;
+  if (int rc = launch_decode(s, (const char*)src_device, slot, n_values, format, (double)packed_bytes)) return rc;
   return cache_slot_ready(s, slot);
 }
 

@@ -50,7 +50,8 @@ LIA_CACHE_MAX_ENTRIES, LIA_CACHE_READ_SLACK = 64, 4096
 class CacheGeometry(ctypes.Structure):
     """lia_cache_geometry: where the wire cache's entries lie (lia_cache_geometry_plan, lia_stream_cache_layout)"""
     _fields_ = [("n_entries", c_int), ("in_slots", c_int), ("in_staging", c_int), ("in_workspace", c_int), ("entry_stride", c_size_t),
-                ("landing_stride", c_size_t), ("landing_capacity", c_size_t), ("offset", c_size_t * LIA_CACHE_MAX_ENTRIES)]
+                ("landing_stride", c_size_t), ("landing_capacity", c_size_t), ("offset", c_size_t * LIA_CACHE_MAX_ENTRIES),
+                ("in_extra", c_int)]
 
 
 class BlockSampler(ctypes.Structure):
@@ -200,7 +201,11 @@ SIGNATURES = {
     "lia_stream_cache_enable": (c_int, [c_void_p, c_int, c_size_t]),
     "lia_stream_cache_disable": (c_int, [c_void_p]),
     "lia_cache_geometry_plan": (c_int, [c_int, c_size_t, c_size_t, c_int, c_size_t, c_size_t, c_size_t, c_size_t, ctypes.POINTER(CacheGeometry)]),
+    "lia_cache_geometry_plan_extra": (c_int, [c_int, c_size_t, c_size_t, c_int, c_size_t, c_size_t, c_size_t, c_size_t, c_size_t,
+                                              ctypes.POINTER(CacheGeometry)]),
     "lia_stream_cache_configure": (c_int, [c_void_p, c_size_t, c_int, c_size_t]),
+    "lia_stream_cache_extra": (c_int, [c_void_p, c_size_t]),
+    "lia_stream_decode_device": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_size_t, c_int]),
     "lia_stream_cache_layout": (c_int, [c_void_p, c_int, c_size_t, ctypes.POINTER(CacheGeometry)]),
     "lia_ctx_workspace_bytes": (c_size_t, [c_void_p]),
     "lia_ctx_workspace_ptr": (c_void_p, [c_void_p]),

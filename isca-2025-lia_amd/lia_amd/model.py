@@ -137,7 +137,8 @@ class LayerStore:
     def __init__(self, desc, offsets, total_bytes):
         self.desc, self.offsets, self.nbytes = desc, offsets, total_bytes
         self.tier = None          # "device" | "pinned" | "cxl" | "mapped" | "pageable" | "remote"
-        self.packed = 0           # 0: host copy is raw bf16; 10: it holds a lossless encoding of the pack10 family
+        self.packed = 0           # 0: the copy is raw bf16; 10: it holds a lossless encoding of the pack10 family (a host copy, or a
+                                  # resident layer held as its wire encoding: tier "device", to_device(packed=10))
         self.codec = 0            # which one: CODEC_V2 (lia_pack10.hip) or CODEC_RANS (lia_pack10a.hip); 0 with a raw copy
         self.shard = None         # (rank, world, slice bytes) when the host copy is one slice of the wire bytes
         self.stream_bytes = total_bytes   # bytes that cross the host link per use
@@ -189,17 +190,32 @@ class LayerStore:
         return None if (self.packed or self.shard or self.tier not in ("pinned", "cxl", "mapped", "pageable")) else self.host_ptr()
 
     def device_ptr(self):
+        """the RAW bf16 layer in device memory"""
         assert self.tier == "device"
+        if self.packed:
+            raise RuntimeError("this resident layer is held in its pack10 wire encoding (to_device(packed=10)): it has no raw device "
+                               "pointer; it is decoded into a streamer slot (packed_device_ptr), or re-tiered raw with to_device()")
+        return self._dev.data_ptr()
+
+    def packed_device_ptr(self):
+        """the wire encoding of a resident layer held packed: stream_bytes of it, + 4096 bytes the decode kernels may read behind"""
+        assert self.tier == "device" and self.packed
         return self._dev.data_ptr()
 
     def _raw_on_device(self):
         """The raw bf16 layer as a CUDA uint8 tensor, from whatever tier / wire format holds it now (a packed host copy is
         shipped encoded and rebuilt by the same decode kernels the streamer uses)."""
-        if self.tier == "device":
+        if self.tier == "device" and not self.packed:
             return self._dev
         if self.tier in (None, "remote"):
             raise RuntimeError(f"layer holds no data (tier {self.tier!r})")
         dev = torch.empty(self.nbytes, dtype=torch.uint8, device="cuda")
+        if self.tier == "device":
+            # a resident layer held packed: the encoder's own output with the read slack behind it, as a wire-cache entry holds it
+            N.check(self._lib.lia_pack_decode(ctypes.c_void_p(self._dev.data_ptr()), ctypes.c_void_p(dev.data_ptr()), self.nbytes // 2,
+                                              int(self.codec), None), "lia_pack_decode")
+            torch.cuda.synchronize()
+            return dev
         raw = getattr(self, "_raw_ptr", None)
         if raw or not (self.packed or self.shard):
             N.check(self._lib.lia_memcpy_h2d(dev.data_ptr(), raw or self.host_ptr(), self.nbytes), "lia_memcpy_h2d")
@@ -217,13 +233,38 @@ class LayerStore:
     def _fill_host(self, ptr, src):
         N.check(self._lib.lia_memcpy_d2h(ptr, src.data_ptr(), self.nbytes), "lia_memcpy_d2h")
 
-    def to_device(self):
-        """move_gpu_layer (lia/modeling_opt.py:229-268), minus the un-blocking (weights are already row-major)."""
-        if self.tier == "device":
+    READ_SLACK = 4096             # LIA_CACHE_READ_SLACK: what the decode kernels may read behind an encoded layer
+
+    def to_device(self, packed=0):
+        """move_gpu_layer (lia/modeling_opt.py:229-268), minus the un-blocking (weights are already row-major).  packed=10: the
+        layer stays in HBM as its pack10 wire encoding (0.66 of the bytes) in a tensor of exactly stream_bytes + READ_SLACK, and is
+        decoded into a streamer slot for every use (lia_stream_decode_device); a layer that pack10 refuses or does not shrink stays
+        raw, as a streamed one stays raw on the host.  The encoding goes through a pinned host copy (to_pinned, the one place that
+        encodes): the raw layer and the encoder's buffers are free, and handed back, before the encoding gets its tensor; a host copy
+        that already holds the format is uploaded as it is."""
+        fmt = self._fmt_of(packed)
+        if self.tier == "device" and (self.want_fmt == fmt or (not fmt and not self.packed)):
             return
-        dev = self._raw_on_device()
-        self._free()
-        self._dev, self.tier = dev, "device"
+        if fmt and not self.shard:
+            if not (self.tier in ("pinned", "cxl", "mapped") and self.packed == fmt):
+                try:
+                    self.to_pinned(fmt)
+                except MemoryError:
+                    pass                               # no room for the pinned copy: the layer is raw on the device again (to_pinned)
+            if self.tier != "device" and self.packed == fmt and self.stream_bytes + self.READ_SLACK < self.nbytes:
+                torch.cuda.empty_cache()
+                n, codec = int(self.stream_bytes), int(self.codec)
+                held = torch.zeros(n + self.READ_SLACK, dtype=torch.uint8, device="cuda")
+                N.check(self._lib.lia_memcpy_h2d(held.data_ptr(), self._ptr, n), "lia_memcpy_h2d")
+                self._free()
+                self._dev, self.tier = held, "device"
+                self.packed, self.codec, self.stream_bytes, self.want_fmt = fmt, codec, n, fmt
+                return
+        if self.tier != "device" or self.packed:
+            dev = self._raw_on_device()
+            self._free()
+            self._dev, self.tier = dev, "device"
+        self.want_fmt = fmt                            # (asked for: a layer that does not pack is not encoded again by every placement)
 
     def to_pageable(self):
         """plain (unpinned) host memory: what the reference streams from without --pin-weight (lia/modeling_opt.py:1219-1220)"""
@@ -576,16 +617,17 @@ class LiaOPTModel:
 
     # -- placement (first forward, and again whenever the flags change) -------------------------------
     @staticmethod
-    def _place_key(n_gpu_layers, pin_weight, enable_cxl, wire, raw_layers, shard):
+    def _place_key(n_gpu_layers, pin_weight, enable_cxl, wire, raw_layers, shard, resident_packed=0):
         return (int(n_gpu_layers), bool(pin_weight), bool(enable_cxl), LayerStore._fmt_of(wire), frozenset(raw_layers or ()),
-                tuple(shard) if shard else None)
+                tuple(shard) if shard else None, LayerStore._fmt_of(resident_packed))
 
-    def place(self, n_gpu_layers, pin_weight, enable_cxl, wire=False, raw_layers=(), shard=None):
+    def place(self, n_gpu_layers, pin_weight, enable_cxl, wire=False, raw_layers=(), shard=None, resident_packed=0):
         """Tier assignment, idempotent per flag set: move_gpu_layer / pin_memory of the reference (lia/modeling_opt.py:1182-1184,
         1214-1217) run on the first forward of a process; here a later call with other flags (policy 1 needs raw host copies,
         another gpu%, another wire format, the CXL tier) RE-PLACES the layers instead of failing -- every LayerStore can be
-        rebuilt on the device from whatever it holds."""
-        key = self._place_key(n_gpu_layers, pin_weight, enable_cxl, wire, raw_layers, shard)
+        rebuilt on the device from whatever it holds.  resident_packed=10: the resident layers are held as their wire encoding
+        (LayerStore.to_device(packed=10)); 0 re-tiers them raw."""
+        key = self._place_key(n_gpu_layers, pin_weight, enable_cxl, wire, raw_layers, shard, resident_packed)
         if self.placed_for == key:
             return
         fmt = LayerStore._fmt_of(wire)
@@ -597,7 +639,7 @@ class LiaOPTModel:
         # promotions first (they free host memory), then the host-side moves
         for i, st in enumerate(self.layers):
             if st.tier != "remote" and i < n_gpu_layers:
-                st.to_device()
+                st.to_device(LayerStore._fmt_of(resident_packed))
         for i, st in enumerate(self.layers):
             if st.tier == "remote" or i < n_gpu_layers:
                 continue
@@ -611,6 +653,8 @@ class LiaOPTModel:
                 st.to_pageable()              # no --pin-weight: plain host memory, staged through the bounce buffer
             # (a raw pinned / CXL copy left by an earlier --pin-weight call also serves an unpinned request)
         torch.cuda.synchronize()
+        if resident_packed:
+            torch.cuda.empty_cache()          # the raw layers and the encoder's buffers: what packing saves goes back to the device
         self.placed_for = key
 
     def streamed_bytes(self, n_gpu_layers):

@@ -37,6 +37,9 @@ class Box:
     host_threads: int = 0
     host_mem_gb: float = 0.0
     calibrated: dict = None           # set by calibrate(): the measured numbers, for the log
+    # ... and, with wire_cache, the resident layers are held in the wire format too and what they save holds more entries (the
+    # scheduler's LIA_RESIDENT_PACKED; resident_packed_default()).  Off in a Box that does not ask for it, like the two above
+    resident_packed: bool = False
 
     def __post_init__(self):
         if not self.host_threads:
@@ -188,12 +191,20 @@ def wire_cache_ws_default():
     return wire_cache_default() and os.environ.get("LIA_WIRE_CACHE_WS", "1") != "0"
 
 
-def wire_cache_layers(shape, box, n_str, n_slots=4, keep_slots=2, B=0, T=0):
+def resident_packed_default():
+    """whether the resident layers are held in the wire format beside that cache (LIA_RESIDENT_PACKED, default on)"""
+    import os
+    return wire_cache_default() and os.environ.get("LIA_RESIDENT_PACKED", "1") != "0"
+
+
+def wire_cache_layers(shape, box, n_str, n_slots=4, keep_slots=2, B=0, T=0, n_res=0):
     """Streamed layers a decode step finds in HBM in their wire format (streaming.WeightPipeline's decode mode), counted by the
     library's own geometry function (lia_cache_geometry_plan): what fits the n_slots - keep_slots streamer slots such a step has no
     use for and the staging areas (lia_pack10_bound: 1.13 x the raw layer each) behind the landing buffers; with box.wire_cache_ws
     the landing buffers are cut to an encoded layer and the workspace a prefill of B x T rows sized, less what a decode step of B
-    rows keeps, holds entries too.  They cost the step their compute, not their copy."""
+    rows keeps, holds entries too; with box.resident_packed the n_res resident layers are held encoded and what each saves (raw
+    bytes - encoded bytes - read slack) is a fourth region (lia_cache_geometry_plan_extra).  They cost the step their compute, not
+    their copy."""
     if not box.wire_cache or box.wire_ratio >= 1.0 or n_str <= 0 or n_slots <= keep_slots:
         return 0
     import ctypes
@@ -214,9 +225,12 @@ def wire_cache_layers(shape, box, n_str, n_slots=4, keep_slots=2, B=0, T=0):
             lend = max(ws - lend_at, 0)
             if lend < (64 << 20):                                                                      # OffloadScheduler.WS_LEND_MIN_BYTES
                 lend = 0
+    extra = 0
+    if getattr(box, "resident_packed", False) and n_res > 0:
+        extra = n_res * max(lb - (entry + N.LIA_CACHE_READ_SLACK), 0)        # WeightPipeline.configure_extra
     g = N.CacheGeometry()
-    if lib.lia_cache_geometry_plan(n_slots, slot, staging, keep_slots, entry, landing, lend_at, lend, ctypes.byref(g)) != 0:
-        lib.lia_cache_geometry_plan(n_slots, slot, staging, keep_slots, entry, 0, lend_at, lend, ctypes.byref(g))
+    if lib.lia_cache_geometry_plan_extra(n_slots, slot, staging, keep_slots, entry, landing, lend_at, lend, extra, ctypes.byref(g)) != 0:
+        lib.lia_cache_geometry_plan_extra(n_slots, slot, staging, keep_slots, entry, 0, lend_at, lend, extra, ctypes.byref(g))
     return min(n_str, g.n_entries)
 
 
@@ -241,8 +255,12 @@ def estimate(shape, B, T, new, gpu_percentage, decoding_policy, box=None, kv_in_
     lm_ms = 1e3 * shape.vocab * H * 2 / (box.hbm_gbs * 1e9)
     # a cached layer: its compute, and its wire-format decode kernel's HBM traffic beside the layer in front of it (encoded bytes
     # read, bf16 written: 0.54 ms measured for an OPT-30B layer) -- never cheaper than a resident layer
-    n_cached = wire_cache_layers(shape, box, n_str, B=B, T=T)
-    cached_ms = compute_ms + 1e3 * lb * (1.0 + box.wire_ratio) / (box.hbm_gbs * 1e9)
+    packed_res = bool(getattr(box, "resident_packed", False) and box.wire_cache and box.wire_ratio < 1.0 and 0 < n_gpu < L and decoding_policy in (0, 2, 3))
+    n_cached = wire_cache_layers(shape, box, n_str, B=B, T=T, n_res=n_gpu if packed_res else 0)
+    unpack_ms = 1e3 * lb * (1.0 + box.wire_ratio) / (box.hbm_gbs * 1e9)
+    cached_ms = compute_ms + unpack_ms
+    if packed_res:
+        resident_ms += unpack_ms          # a resident layer held packed is decoded into a slot every step, like a cached one
     decode_ms = n_gpu * resident_ms + n_cached * cached_ms + (n_str - n_cached) * streamed_ms + lm_ms + 0.5
     # prefill
     flops_layer = 2.0 * B * T * (4 * H * H + 2 * H * F) + 6.0 * B * T * T * H

@@ -338,7 +338,7 @@ def auto_plan(args, out=print):
     max_pct = int(args.plan_max_gpu_percentage)    # what-if / tests: cap the resident share
     fmt = args.stream_format or default_stream_format()
     box.wire_ratio = {"raw": 1.0, "pack10": 0.675}[fmt]
-    box.wire_cache, box.wire_cache_ws = planner.wire_cache_default(), planner.wire_cache_ws_default()      # (Llama models stream nothing: every layer is resident)
+    box.wire_cache, box.wire_cache_ws, box.resident_packed = planner.wire_cache_default(), planner.wire_cache_ws_default(), planner.resident_packed_default()      # (Llama models stream nothing: every layer is resident)
     shape = model_shape(args)
     pl = planner.plan(shape, args.batch_size, int(args.input_tokens), args.max_new_tokens, box, max_gpu_percentage=max_pct)
     args.gpu_percentage, args.prefill_policy, args.decoding_policy = pl.gpu_percentage, pl.prefill_policy, pl.decoding_policy
@@ -549,7 +549,7 @@ def plan_beside(args):
         box = planner.calibrate(verbose=False)
         fmt = args.stream_format or default_stream_format()
         box.wire_ratio = {"raw": 1.0, "pack10": 0.675}[fmt]
-        box.wire_cache, box.wire_cache_ws = planner.wire_cache_default(), planner.wire_cache_ws_default()
+        box.wire_cache, box.wire_cache_ws, box.resident_packed = planner.wire_cache_default(), planner.wire_cache_ws_default(), planner.resident_packed_default()
         shape = model_shape(args)
         B, T, new = args.batch_size, int(args.input_tokens), args.max_new_tokens
         pl = planner.plan(shape, B, T, new, box)

@@ -129,7 +129,10 @@ def check_verify_rows(block_ids, kv_state, row_lens, flags, n_gpu, L):
 class OffloadScheduler:
     """forward(input_ids, kv_state, **lia flags) -> (logits [B,vocab], next_ids [B]) on the device."""
 
-    def __init__(self, model, device=0, n_slots=None, dp_group=None, wire=None, wire_cache=None, wire_cache_ws=None, split_decode=None):
+    resident_packed = False     # (class-level: a scheduler built without __init__ holds its residents raw)
+
+    def __init__(self, model, device=0, n_slots=None, dp_group=None, wire=None, wire_cache=None, wire_cache_ws=None, split_decode=None,
+                 resident_packed=None):
         self.model, self.device, self.dp = model, device, dp_group
         # a decode step's GPU attention: "measured" = the split-key route where it was measured faster than the one-workgroup kernel
         # (ops.split_decode_pays), True = every step over more keys than one chunk (A/B runs, tests), False = never -- and always,
@@ -143,6 +146,10 @@ class OffloadScheduler:
         # ... and in the context's workspace beyond what such forwards need, which is sized for the prefill and idles during decode
         # (WeightPipeline.configure_cache); LIA_WIRE_CACHE_WS=0: slots and staging areas only, whole staging areas as landing buffers
         self.wire_cache_ws = (os.environ.get("LIA_WIRE_CACHE_WS", "1") != "0") if wire_cache_ws is None else bool(wire_cache_ws)
+        # ... and the HBM-resident layers are held in that wire format too, decoded into a slot for every use like a cached layer: what
+        # they save holds more entries at the same footprint (WeightPipeline.configure_extra).  Only where the wire cache applies
+        # (_resident_format); LIA_RESIDENT_PACKED=0: raw residents, computed from where they lie
+        self.resident_packed = (os.environ.get("LIA_RESIDENT_PACKED", "1") != "0") if resident_packed is None else bool(resident_packed)
         self._ws_need = 0           # workspace the forward being prepared needs (_ensure)
         self._cache_keep = 0        # the largest _ws_need of a forward that ran inside the decode mode on this context
         # wire format of the streamed layers: "pack10" (the lossless encoding of lia_pack10.hip) or "raw" bf16
@@ -590,12 +597,13 @@ class OffloadScheduler:
                     kv_state.move_cache(N.lib(), i, to_device=(i not in need_host))
         shard = (self.dp.rank, self.dp.world) if (self.dp is not None and self.dp.world > 1 and self.dp.mode == "allgather") else None
         wire, raw_set = placement_formats(s.prefill_policy, decoding_policy, self.wire, n_gpu, L, pin_weight, enable_cxl, cpu_set, self.dp is not None)
-        if m.placed_for != m._place_key(n_gpu, pin_weight, enable_cxl, wire, raw_set, shard):
+        res_fmt = self._resident_format(s, wire, coop, cpu_set)
+        if m.placed_for != m._place_key(n_gpu, pin_weight, enable_cxl, wire, raw_set, shard, res_fmt):
             # the flags changed since the last placement: the model re-tiers its layers (policy 1 wants raw host copies,
             # another gpu%, wire format or host tier).  Copies in flight read host buffers that are about to be freed and
             # the cached device pointers of the resident layers go stale.
             self.resident.replaced(self.pipe)
-        m.place(n_gpu, pin_weight, enable_cxl, wire, raw_layers=raw_set, shard=shard)
+        m.place(n_gpu, pin_weight, enable_cxl, wire, raw_layers=raw_set, shard=shard, resident_packed=res_fmt)
         if coop is not None and is_prefill:
             coop.new_sequence()                                      # the first decode step is not a sample of the steady state
         s.coop, s.cpu_set = coop, cpu_set
@@ -619,21 +627,38 @@ class OffloadScheduler:
             self._await_all_deliveries()          # (host-blocking: afterwards nothing on the D2H stream reads the holding caches)
             s.hold = self._hold_caches(B, T, n_gpu)
 
+    def _resident_format(self, s, wire, coop, cpu_set):
+        """10 where this placement holds its resident layers as their pack10 wire encoding, else 0 (raw): where the wire cache itself
+        applies -- the streamed layers travel as pack10, no data parallelism, no host-computed layers, a decode policy that streams (2,
+        3 or 0), and there are both resident and streamed layers.  Every other placement re-tiers the residents raw: policy 1, whose
+        resident prefix runs from raw pointers, the cooperative split, data parallelism."""
+        if not (self.resident_packed and self.wire_cache) or wire != 10 or self.dp is not None or coop is not None or cpu_set:
+            return 0
+        if s.decoding_policy not in (2, 3, 0) or s.prefill_policy == 1 or not (0 < s.n_gpu < s.L) or self.n_slots <= WeightPipeline.KEEP_SLOTS:
+            return 0
+        return 10
+
     def _run_layers(self, s, kv_state):
         """the decoder layers of one forward on the GPU path: the resident run, then every streamed layer behind its weight copy
         (or on the host cores, for the cooperative split's host set); returns the hidden state that feeds lm_head"""
         m, sh, ctx, pipe = self.model, self.model.shape, self.ctx, self.pipe
         B, T, L, n_gpu, is_prefill, policy, mini, overlap, pos0, hold = s.B, s.T, s.L, s.n_gpu, s.is_prefill, s.policy, s.mini, s.overlap, s.pos0, s.hold
         host_act, host_now, x, y = s.host_act, s.host_now, s.x, s.y
+        # resident layers held packed take slots like streamed ones: the order starts (and wraps) at layer 0
+        packed = frozenset(pipe.packed_residents()) if (pipe is not None and n_gpu > 0) else frozenset()
+        wrap_to = 0 if packed else n_gpu
+        raw_res = frozenset(range(n_gpu)) - packed if packed else frozenset()     # (layers pack10 refused: they need no slot)
         if n_gpu < L:
             self._set_wire_cache(s)
+        if packed and is_prefill and not pipe.keep:
+            pipe.trim_residents(min(packed))
         if n_gpu < L and overlap:
-            pipe.prefetch(n_gpu)                                   # no-op if the previous step already wrapped to it
+            pipe.prefetch(min(packed) if packed else n_gpu)        # no-op if the previous step already wrapped to it
         # the prefill's last layer: only hidden[:, -1, :] feeds lm_head (models.py:424-431), its K/V of every position feed decode
         tail_last = self.prefill_tail and not s.every_pos and is_prefill and T > 1 and (policy in (0, 3) or n_gpu == L) and (L - 1) not in host_now
         xlast = None
         first = 0
-        if not is_prefill and n_gpu > 0:
+        if not is_prefill and n_gpu > 0 and not packed:
             # decode: the resident run (whole batch, everything on the GPU incl. KV -- policy 3; :1246-1260) in ONE library call
             # (lia_decode_layers: the per-op route layer by layer, or with LIA_FUSED_DECODE=1 an attention launch and a
             # persistent chain launch per layer, lia_chain.hip)
@@ -643,6 +668,23 @@ class OffloadScheduler:
             x, y = y, x
             first = n_gpu
         for idx in range(first, L):
+            if idx in packed:
+                # resident layer held packed: decoded into a slot (no copy), then as below
+                if not overlap:
+                    pipe.prefetch(idx)
+                wptrs = pipe.acquire(idx)
+                if overlap:
+                    pipe.prefetch_ahead(idx, stream_order(idx, wrap_to, L, host_act | raw_res, skip_now=not is_prefill))
+                if tail_last and idx == L - 1:
+                    xlast = torch.empty((B, 1, sh.hidden), dtype=torch.bfloat16, device="cuda")
+                    ctx.layer_forward_last(m.desc, 3, wptrs, x, xlast, kv_state.kv[idx], B, T, pos0, 0)
+                else:
+                    ctx.layer_forward(m.desc, 3, wptrs, x, y, kv_state.kv[idx], B, T, pos0, 0)
+                    x, y = y, x
+                pipe.release(idx)
+                if not overlap:
+                    ctx.synchronize()
+                continue
             if idx < n_gpu:
                 # resident layer: whole batch, everything on the GPU incl. KV (policy 3; :1246-1260)
                 if tail_last and idx == L - 1:
@@ -662,7 +704,7 @@ class OffloadScheduler:
             wptrs = pipe.acquire(idx)
             if overlap:
                 # (decode forwards skip the host-computed layers; a prefill streams them all and skips them behind the wrap)
-                pipe.prefetch_ahead(idx, stream_order(idx, n_gpu, L, host_act, skip_now=not is_prefill))
+                pipe.prefetch_ahead(idx, stream_order(idx, wrap_to, L, host_act | raw_res, skip_now=not is_prefill))
             if policy in (0, 3):
                 # FlexGen-style minibatches (:1283-1365).  Policy 3 here = streamed weights with the cache kept in HBM
                 # (build-defined; the reference reserves 3 for resident layers, :1175-1176)
@@ -716,6 +758,8 @@ class OffloadScheduler:
                 self._cache_keep = max(self._cache_keep, self._ws_need)
                 idle = self.ctx.workspace_alloc_bytes - self._cache_keep
                 pipe.configure_cache(idle >= self.WS_LEND_MIN_BYTES, self._cache_keep)
+            else:
+                pipe.configure_extra()
             pipe.set_decode_mode(range(s.n_gpu, s.L))
         else:
             pipe.set_decode_mode(None)
@@ -723,12 +767,13 @@ class OffloadScheduler:
     def wire_cache_info(self, regions=False):
         """{"enabled", "on", "capacity" (layers), "layers" (bound to an entry, in order), "bytes" (wire bytes held in HBM)};
         regions: also "workspace" (the context's idle workspace may hold entries) and "regions", the entries of the mode that is on
-        in the idle slots, the staging allocation and the workspace: {"slots", "staging", "workspace"}"""
+        in the idle slots, the staging allocation, the workspace and the streamer's extra region (what packed residents save):
+        {"slots", "staging", "workspace", "extra"}.  Resident layers are never among "layers": they hold no entry."""
         info = self.pipe.cache_info() if self.pipe else {"on": False, "capacity": 0, "layers": [], "bytes": 0}
         info = dict(info, enabled=self.wire_cache)
         if regions:
             info.update(workspace=self.wire_cache_ws,
-                        regions=self.pipe.cache_regions() if self.pipe else {"slots": 0, "staging": 0, "workspace": 0})
+                        regions=self.pipe.cache_regions() if self.pipe else {"slots": 0, "staging": 0, "workspace": 0, "extra": 0})
         return info
 
     def _deliver(self, s, kv_state):

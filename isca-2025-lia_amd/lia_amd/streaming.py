@@ -19,9 +19,15 @@ class WeightPipeline:
     streamed layers of a step in their wire format, and a packed layer that is not cached passes two stages with a resource each:
     `landed` (its copy is queued into a landing buffer) and `inflight` (its decode is queued into a slot).  The link runs ahead by
     landing buffers while the slots cycle through the cached layers.  configure_cache (lia_stream_cache_configure) sizes the landing
-    buffers for the layers that are landed and lends the mode the context's workspace beyond what its forwards need: more entries."""
+    buffers for the layers that are landed and lends the mode the context's workspace beyond what its forwards need: more entries.
+
+    Packed residents (LayerStore.to_device(packed=10): tier "device", packed): a resident layer held as its wire encoding goes
+    through the same ring -- prefetch / _issue decode it from where it lies (lia_stream_decode_device), no copy, no landing buffer,
+    no cache entry; it needs nothing but a slot.  What the model saves by holding them packed is the streamer's extra region
+    (lia_stream_cache_extra, configure_extra): more entries at the same footprint."""
 
     KEEP_SLOTS = 2
+    _extra = 0                      # bytes of the extra region asked of the library (configure_extra)
 
     def __init__(self, ctx, model, n_slots, dp_group=None):
         self.ctx, self.model, self.lib = ctx, model, N.lib()
@@ -70,6 +76,37 @@ class WeightPipeline:
     def can_prefetch(self):
         return bool(self.free_slots)
 
+    # -- resident layers -----------------------------------------------------------------------------
+    def _resident(self, layer_idx):
+        """0: streamed; 1: resident, raw (needs no slot, is never prefetched); 2: resident, held packed (decoded into a slot)"""
+        st = self.model.layers[layer_idx]
+        if getattr(st, "tier", None) != "device":
+            return 0
+        return 2 if st.packed else 1
+
+    @property
+    def _n_resident(self):
+        """resident layers that appear in the prefetch order: all of them while one is held packed, else none"""
+        layers = self.model.layers
+        if not any(getattr(st, "tier", None) == "device" and st.packed for st in layers):
+            return 0
+        return sum(1 for st in layers if st.tier == "device")
+
+    def packed_residents(self):
+        return [i for i in range(len(self.model.layers)) if self._resident(i) == 2]
+
+    def _decode_resident(self, layer_idx, slot):
+        st = self.model.layers[layer_idx]
+        N.check(self.lib.lia_stream_decode_device(self.handle, slot, ctypes.c_void_p(st.packed_device_ptr()), st.stream_bytes, st.nbytes // 2,
+                                                  int(getattr(st, "codec", 0) or st.packed)), "lia_stream_decode_device")
+
+    def trim_residents(self, first):
+        """Before a prefill: of the packed residents a decode step's wrap has queued, only `first` keeps its slot -- a prefill's
+        slots are the link's lead over the resident compute."""
+        for li, _ in list(self.inflight):
+            if li != first and self._resident(li) == 2:
+                self.forget(li)
+
     # -- decode mode ---------------------------------------------------------------------------------
     def _cacheable(self, layer_idx):
         st = self.model.layers[layer_idx]
@@ -91,6 +128,25 @@ class WeightPipeline:
                 return cand[:c], size
         return [], 0
 
+    def configure_extra(self):
+        """The streamer's extra region = what the model saves by holding resident layers packed: sum of raw bytes - (encoded bytes
+        + read slack).  Another size than the last one turns the mode off first (the region is part of its geometry); the library is
+        called only for a positive sum, or to free a region that no packed resident stands for any more.  Returns whether it changed."""
+        if self.dp is not None or self.n_slots <= self.KEEP_SLOTS:
+            return False
+        saved = sum(int(st.nbytes) - (int(st.stream_bytes) + N.LIA_CACHE_READ_SLACK) for st in self.model.layers if getattr(st, "tier", None) == "device" and st.packed)
+        saved = max(saved, 0)
+        if saved == self._extra:
+            return False
+        if self.keep:
+            self.set_decode_mode(None)
+        self._extra, self._plan = saved, None
+        try:
+            N.check(self.lib.lia_stream_cache_extra(self.handle, saved), "lia_stream_cache_extra")
+        except MemoryError:
+            pass                                  # no room on the device: the mode runs without the region
+        return True
+
     def configure_cache(self, lend_workspace, keep_bytes=0):
         """Before set_decode_mode: landing buffers sized for the largest encoded layer this model streams (any of them may be landed,
         not only the ones behind the bound layers), and, lend_workspace, the context's workspace beyond its first keep_bytes as room
@@ -99,10 +155,11 @@ class WeightPipeline:
         set_decode_mode binds and refills.  Returns whether the configuration changed."""
         if self.dp is not None or self.n_slots <= self.KEEP_SLOTS:
             return False
+        extra = self.configure_extra()
         sizes = [int(self.model.layers[i].stream_bytes) for i in range(len(self.model.layers)) if self._cacheable(i)]
         cfg = (max(sizes, default=0), bool(lend_workspace), int(keep_bytes) if lend_workspace else 0)
         if cfg == self._cfg:
-            return False
+            return extra
         if self.keep:
             self.set_decode_mode(None)
         try:
@@ -152,11 +209,11 @@ class WeightPipeline:
                 "bytes": sum(int(self.model.layers[i].stream_bytes) for i in self.cache_filled)}
 
     def cache_regions(self):
-        """entries of the mode that is on per region: {"slots", "staging", "workspace"} (lia_stream_cache_layout)"""
+        """entries of the mode that is on per region: {"slots", "staging", "workspace", "extra"} (lia_stream_cache_layout)"""
         g = N.CacheGeometry()
         if self.keep:
             N.check(self.lib.lia_stream_cache_layout(self.handle, self.keep, 1, ctypes.byref(g)), "lia_stream_cache_layout")
-        return {"slots": g.in_slots, "staging": g.in_staging, "workspace": g.in_workspace}
+        return {"slots": g.in_slots, "staging": g.in_staging, "workspace": g.in_workspace, "extra": g.in_extra}
 
     def _land(self, layer_idx):
         st = self.model.layers[layer_idx]
@@ -169,7 +226,9 @@ class WeightPipeline:
         st = self.model.layers[layer_idx]
         slot = self.free_slots.pop(0)
         fmt = int(getattr(st, "codec", 0) or st.packed)
-        if layer_idx in self.cache:
+        if getattr(st, "tier", None) == "device":
+            self._decode_resident(layer_idx, slot)
+        elif layer_idx in self.cache:
             N.check(self.lib.lia_stream_decode_cached(self.handle, self.cache[layer_idx], slot, ctypes.c_void_p(st.host_ptr()), st.stream_bytes,
                                                       st.nbytes // 2, fmt, int(st.is_dma_able())), "lia_stream_decode_cached")
             self.cache_filled.add(layer_idx)
@@ -191,17 +250,20 @@ class WeightPipeline:
     def _pump(self, idx, next_layer):
         """decode mode's prefetch_ahead: slots go to the layers behind idx strictly in the order they are needed; behind the first
         layer that finds none, packed layers without a cache entry still start their copies while a landing buffer is free."""
-        in_order = True
-        for _, nxt in zip(range(len(self.cache) + 2 * self.keep + 2), next_layer):
+        in_order, n_res = True, self._n_resident
+        for _, nxt in zip(range(len(self.cache) + 2 * self.keep + 2 + n_res), next_layer):
             if nxt == idx or not (self.free_slots or self.free_landing):
                 break
             if nxt in self.held or any(li == nxt for li, _ in self.inflight):
                 continue
+            res = self._resident(nxt) if n_res else 0
+            if res == 1:
+                continue                                       # a raw resident layer: computed from where it lies
             if in_order and self.free_slots:
                 self._issue(nxt)
                 continue
             in_order = False
-            if nxt in self.cache or not self.model.layers[nxt].packed or any(li == nxt for li, _ in self.landed):
+            if res or nxt in self.cache or not self.model.layers[nxt].packed or any(li == nxt for li, _ in self.landed):
                 continue                                       # needs nothing but a slot
             if not self.free_landing:
                 break
@@ -217,7 +279,9 @@ class WeightPipeline:
             return
         st = self.model.layers[layer_idx]
         slot = self.free_slots.pop(0)
-        if self.dp is None and st.packed:
+        if getattr(st, "tier", None) == "device":
+            self._decode_resident(layer_idx, slot)
+        elif self.dp is None and st.packed:
             N.check(self.lib.lia_stream_prefetch_packed(self.handle, slot, ctypes.c_void_p(st.host_ptr()), st.stream_bytes, st.nbytes // 2,
                                                         int(getattr(st, "codec", 0) or st.packed), int(st.is_dma_able())), "lia_stream_prefetch_packed")
         elif self.dp is None:
@@ -329,6 +393,21 @@ class WeightPipeline:
         if self.keep:
             self._pump(idx, next_layer)
             return
+        n_res = self._n_resident
+        if n_res:
+            # Resident layers in the order (stream_order wraps to layer 0 while residents are held packed).  Outside the decode mode
+            # the slots are the link's lead: a packed resident takes one ahead of time only as the very next layer, and never a
+            # second one; the others are decoded when they are next -- they need nothing but a slot.
+            ahead = sum(1 for li, _ in self.inflight if self._resident(li) == 2)
+            for j, nxt in zip(range(self.n_slots - 1 + n_res), next_layer):
+                if nxt == idx or not self.can_prefetch():
+                    break
+                res = self._resident(nxt)
+                if res == 2 and j == 0 and not ahead:
+                    self.prefetch(nxt)
+                if not res:
+                    self.prefetch(nxt)
+            return
         for _, nxt in zip(range(self.n_slots - 1), next_layer):
             if nxt == idx or not self.can_prefetch():
                 break
@@ -374,6 +453,10 @@ class WeightPipeline:
             self.free_slots.append(slot)
         self.inflight = []
         torch.cuda.synchronize()
+        if self._extra:
+            # the packed residents the extra region stands for may be about to become raw again: its bytes go back first
+            self._extra, self._plan = 0, None
+            N.check(self.lib.lia_stream_cache_extra(self.handle, 0), "lia_stream_cache_extra")
 
     def stats(self, reset=False):
         b, ms = ctypes.c_double(), ctypes.c_double()
@@ -389,7 +472,7 @@ class WeightPipeline:
 
 def stream_order(idx, first, L, skip=frozenset(), skip_now=True):
     """The streamed layers behind idx in the order they will be needed, without end: idx + 1 ... L - 1, then first ... L - 1 of
-    the next forward, and so on.  skip: the layers a decode step computes on the host cores, which need no slot; a prefill
+    the next forward, and so on (first = 0 while resident layers are held packed: they take slots like streamed ones).  skip: the layers a decode step computes on the host cores, which need no slot; a prefill
     streams every layer (skip_now=False), so for it they are left out only behind the wrap, where the next forward is a
     decode step.  (skip never holds `first`: OffloadScheduler.cpu_layer_order.)"""
     i, skipping = idx, skip_now
