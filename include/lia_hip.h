@@ -285,6 +285,36 @@ int lia_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int M, int H, c
                  void* stream);
 int lia_llama_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int M, int H, const lia_bf16* normw, const lia_bf16* lm,
                        int vocab, float eps, const int64_t* targets, float* logprobs, int64_t* greedy_ids, void* stream);
+/* ---- log-probabilities of emitted tokens with their top-N alternatives (build-defined) -------------------------
+ * lia_topn_logprobs (the bare kernel): per row r of logits [M, ld] (bf16, device, ld >= vocab >= 1), under the MODEL'S OWN
+ * distribution -- the fp32 log-softmax of the raw logits; no temperature, top-k / top-p, suppress_token or token mask:
+ *   chosen[r]                = l[ids[r]] - (m + log s), bit for bit lia_token_logprobs' value for targets = ids (an id outside
+ *                              [0, vocab) gives 0.0)
+ *   top_ids[r, 0 .. n_top)   = the n_top tokens of largest logit, by logit descending, ties by the lower id; the order of a row is
+ *                              that of the sampler's 16-bit key of the bf16 pattern (so +0.0 sorts above -0.0)
+ *   top_logprobs[r, j]       = l_j - (m + log s) of top_ids[r, j], the same expression; a -inf logit gives -inf and is listed only
+ *                              when fewer than n_top logits are finite
+ * chosen: fp32 [M]; top_ids: int64 [M, n_top]; top_logprobs: fp32 [M, n_top]; ids: int64 [M]; all device, rows n_top apart.
+ * n_top in [0, LIA_LOGPROB_MAX_TOP] and <= vocab; top_ids / top_logprobs may be NULL only with n_top = 0.  The selection is exact
+ * (integer histograms of the key, prefix sums in id order) and the same in every run.  Logits are finite or +-inf, not NaN.
+ * LIA_ERR_INVALID, by name: a NULL logits / ids / chosen, M <= 0, vocab <= 0, ld < vocab, n_top outside the range or > vocab, a
+ * NULL top array with n_top > 0.
+ * lia_ctx_set_logprob_sink: where the head calls leave these values.  The context keeps the POINTERS only: device memory the caller
+ * owns and keeps alive until the compute stream has passed the head call (nothing is copied, nothing synchronises); `rows` rows.
+ * chosen == NULL clears the sink.  WHILE A SINK IS SET lia_lm_head, lia_llama_lm_head, lia_sample, lia_lm_verify,
+ * lia_lm_verify_rows, lia_llama_lm_verify, lia_lm_verify_sample and lia_llama_lm_verify_sample run the kernel behind their own id
+ * kernel on the logits they have in hand, with ids = the head's own output for the row (the argmax, the draw, the greedy / sampled
+ * id of each block position); row i of the call writes sink row i -- for the verify heads i = b * T + t, whichever workspace chunk
+ * the row falls into.  lia_sample rewrites the rows lia_lm_head wrote, with the sampled id as chosen.  The heads' own outputs are
+ * byte for byte those of the call without a sink; without a sink every head launches exactly what it launched before.
+ * LIA_ERR_INVALID, by name, before anything is launched: n_top outside [0, LIA_LOGPROB_MAX_TOP], rows < 1 or a NULL top array
+ * with n_top > 0 (here); at the head call n_top > vocab or a call with more rows than the sink; lia_lm_verify_reject,
+ * lia_llama_lm_verify_reject, lia_lm_score and lia_llama_lm_score while a sink is set.  lia_token_logprobs and lia_topn_logprobs
+ * do not look at the sink. */
+#define LIA_LOGPROB_MAX_TOP 32
+int lia_ctx_set_logprob_sink(lia_ctx* ctx, int n_top, float* chosen, int64_t* top_ids, float* top_logprobs, long rows);
+int lia_topn_logprobs(lia_ctx* ctx, const lia_bf16* logits, long ld, int M, int vocab, const int64_t* ids, int n_top,
+                      float* chosen, int64_t* top_ids, float* top_logprobs, void* stream);
 /* ---- speculative verification: the greedy token behind every position of a draft block, and how much of the
  * draft it confirms.  hidden [B * T, ldh]: the last layer's output for the block [pending | d_1 .. d_{T-1}] of every row.
  * Final norm + lm_head GEMM per chunk exactly as lia_lm_score (same CHUNK RULE, same workspace, logits never materialised), then

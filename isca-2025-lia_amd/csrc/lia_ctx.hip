@@ -211,6 +211,27 @@ extern "C" int lia_ctx_set_token_mask(lia_ctx* c, const int32_t* mask_device, lo
   return LIA_OK;
 }
 
+// the log-probability sink of the head calls: the pointers only, as the token mask -- nothing is copied, nothing waits
+extern "C" int lia_ctx_set_logprob_sink(lia_ctx* c, int n_top, float* chosen, int64_t* top_ids, float* top_logprobs, long rows) {
+  if (!c) return LIA_ERR_INVALID;
+  if (!chosen) { c->lp_chosen = nullptr; c->lp_top_ids = nullptr; c->lp_top = nullptr; c->lp_n_top = 0; c->lp_rows = 0; return LIA_OK; }
+  if (n_top < 0 || n_top > LIA_LOGPROB_MAX_TOP) {
+    lia_set_error("lia_ctx_set_logprob_sink: n_top=%d must be in [0, %d]", n_top, LIA_LOGPROB_MAX_TOP);
+    return LIA_ERR_INVALID;
+  }
+  if (rows < 1) { lia_set_error("lia_ctx_set_logprob_sink: rows=%ld must be >= 1", rows); return LIA_ERR_INVALID; }
+  if (n_top > 0 && (!top_ids || !top_logprobs)) {
+    lia_set_error("lia_ctx_set_logprob_sink: NULL %s with n_top=%d (NULL only with n_top = 0)", !top_ids ? "top_ids" : "top_logprobs", n_top);
+    return LIA_ERR_INVALID;
+  }
+  c->lp_chosen = chosen;
+  c->lp_top_ids = top_ids;
+  c->lp_top = top_logprobs;
+  c->lp_n_top = n_top;
+  c->lp_rows = rows;
+  return LIA_OK;
+}
+
 extern "C" int lia_ctx_set_option(lia_ctx* c, int key, long value) {
   if (!c) return LIA_ERR_INVALID;
   switch (key) {

@@ -66,6 +66,10 @@ extern "C" void lia_verify_reject_accept_launch(const int64_t* block_ids, const 
                                                 int* accepted, int* common, int64_t* next, hipStream_t st);
 extern "C" void lia_token_logprobs_launch(const bf16_t* logits, long ld, int M, int vocab, const int64_t* targets, float* logprobs,
                                           int64_t* greedy, hipStream_t st);
+// lia_logprobs.hip: row r's chosen[r], top_ids / top_logprobs[r * n_top ..) of logits row r with ids[r]; n_top in [0, LIA_LOGPROB_MAX_TOP]
+// and <= vocab (the callers check)
+extern "C" void lia_topn_logprobs_launch(const bf16_t* logits, long ld, int M, int vocab, const int64_t* ids, int n_top, float* chosen,
+                                         int64_t* top_ids, float* top_logprobs, hipStream_t st);
 extern "C" void lia_verify_argmax_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress, int T, int r0,
                                          int64_t* greedy, hipStream_t st);
 extern "C" void lia_verify_argmax_rows_launch(const bf16_t* logits, long ld, int n, int vocab, int suppress, int n_suppress,
@@ -220,6 +224,13 @@ struct lia_ctx {
   const uint32_t* token_mask;  // NULL: no table -- every head call is the unmasked one
   long token_mask_ld;          // words between rows; 0: one row for every row
   int token_mask_rows;
+  // log-probability sink (lia_ctx_set_logprob_sink): the CALLER's device arrays -- only the pointers are kept.  While it is set the head
+  // calls run lia_topn_logprobs_kernel behind their own id kernel and row i of a call writes sink row i
+  float* lp_chosen;            // NULL: no sink -- every head call launches what it launched without one
+  int64_t* lp_top_ids;
+  float* lp_top;
+  int lp_n_top;
+  long lp_rows;
 };
 
 // the workspace is about to be reused: a norm the previous layer call chained into it is gone, and so is a pending hint

@@ -188,6 +188,40 @@ static int token_mask_of(const char* who, const lia_ctx* ctx, long rows, int voc
   return LIA_OK;
 }
 
+// The log-probability sink of a head call on `rows` rows (lia_ctx_set_logprob_sink), checked against the call: LIA_OK with
+// sk->chosen = NULL (no sink: nothing more is launched) or the sink; the refusals by name.  The one place that words them.
+struct LiaSink { float* chosen; int64_t* top_ids; float* top; int n_top; };
+static int logprob_sink_of(const char* who, const lia_ctx* ctx, long rows, int vocab, LiaSink* sk) {
+  memset(sk, 0, sizeof(*sk));
+  if (!ctx->lp_chosen) return LIA_OK;
+  if (ctx->lp_n_top > vocab) {
+    lia_set_error("%s: the log-probability sink asks for n_top=%d alternatives, vocab=%d has fewer (lia_ctx_set_logprob_sink)", who,
+                  ctx->lp_n_top, vocab);
+    return LIA_ERR_INVALID;
+  }
+  if (rows > ctx->lp_rows) {
+    lia_set_error("%s: the call has %ld rows, the log-probability sink %ld (lia_ctx_set_logprob_sink)", who, rows, ctx->lp_rows);
+    return LIA_ERR_INVALID;
+  }
+  sk->chosen = ctx->lp_chosen;
+  sk->top_ids = ctx->lp_top_ids;
+  sk->top = ctx->lp_top;
+  sk->n_top = ctx->lp_n_top;
+  return LIA_OK;
+}
+// rows r0 .. r0 + n - 1 of the sink from the n logits rows in hand and the ids their head just wrote (ids: that of row r0)
+static void sink_write(const LiaSink& sk, const bf16_t* logits, long ld, int n, int vocab, const int64_t* ids, long r0, hipStream_t st) {
+  if (!sk.chosen) return;
+  lia_topn_logprobs_launch(logits, ld, n, vocab, ids, sk.n_top, sk.chosen + r0, sk.n_top ? sk.top_ids + r0 * sk.n_top : nullptr,
+                           sk.n_top ? sk.top + r0 * sk.n_top : nullptr, st);
+}
+// the heads that take no sink
+static bool logprob_sink_refused(const char* who, const lia_ctx* ctx, const char* why) {
+  if (!ctx->lp_chosen) return false;
+  lia_set_error("%s: a log-probability sink is set (lia_ctx_set_logprob_sink): %s", who, why);
+  return true;
+}
+
 // norm_b == nullptr: RMSNorm (Llama), else LayerNorm
 static int lm_head_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, int B, int T, int H, const bf16_t* norm_w, const bf16_t* norm_b,
                         const bf16_t* emb, int vocab, float eps, int suppress_token, bf16_t* logits, int64_t* next_ids, hipStream_t st) {
@@ -196,6 +230,8 @@ static int lm_head_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, int
   const uint32_t* mask;
   long ldm;
   if (int mrc = token_mask_of(who, ctx, B, vocab, &mask, &ldm)) return mrc;
+  LiaSink sk;
+  if (int src = logprob_sink_of(who, ctx, B, vocab, &sk)) return src;
   if (ctx->ws_bytes < scratch) { lia_set_error("%s: workspace too small", who); return LIA_ERR_MEMORY; }
   ws_invalidate(ctx);
   bf16_t* lno = (bf16_t*)ctx->ws;
@@ -210,6 +246,7 @@ static int lm_head_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, int
   if (rc) return rc;
   if (mask) lia_argmax_masked_launch(logits, next_ids, B, vocab, suppress_token, mask, ldm, st);
   else lia_argmax_launch(logits, next_ids, B, vocab, suppress_token, st);
+  sink_write(sk, logits, vocab, B, vocab, next_ids, 0, st);
   HIP_TRY(hipGetLastError());
   return LIA_OK;
 }
@@ -256,8 +293,11 @@ extern "C" int lia_sample(lia_ctx* ctx, const lia_bf16* logits, long ld, int B, 
   const uint32_t* mask;
   long ldm;
   if (int mrc = token_mask_of("lia_sample", ctx, B, vocab, &mask, &ldm)) return mrc;
+  LiaSink sk;
+  if (int src = logprob_sink_of("lia_sample", ctx, B, vocab, &sk)) return src;
   if (mask) lia_sample_masked_launch(logits, ld, B, vocab, temperature, top_k, top_p, suppress_token, uniforms, next_ids, stats, mask, ldm, (hipStream_t)stream);
   else lia_sample_launch(logits, ld, B, vocab, temperature, top_k, top_p, suppress_token, uniforms, next_ids, stats, (hipStream_t)stream);
+  sink_write(sk, logits, ld, B, vocab, next_ids, 0, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return LIA_OK;
 }
@@ -276,6 +316,27 @@ extern "C" int lia_token_logprobs(lia_ctx* ctx, const lia_bf16* logits, long ld,
   if (vocab <= 0) { lia_set_error("lia_token_logprobs: vocab=%d must be >= 1", vocab); return LIA_ERR_INVALID; }
   if (ld < vocab) { lia_set_error("lia_token_logprobs: ld=%ld < vocab=%d", ld, vocab); return LIA_ERR_INVALID; }
   lia_token_logprobs_launch(logits, ld, M, vocab, targets, logprobs, greedy_ids, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+extern "C" int lia_topn_logprobs(lia_ctx* ctx, const lia_bf16* logits, long ld, int M, int vocab, const int64_t* ids, int n_top,
+                                 float* chosen, int64_t* top_ids, float* top_logprobs, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!logits || !ids || !chosen) {
+    lia_set_error("lia_topn_logprobs: NULL %s", !logits ? "logits" : !ids ? "ids" : "chosen");
+    return LIA_ERR_INVALID;
+  }
+  if (M <= 0) { lia_set_error("lia_topn_logprobs: M=%d must be >= 1", M); return LIA_ERR_INVALID; }
+  if (vocab <= 0) { lia_set_error("lia_topn_logprobs: vocab=%d must be >= 1", vocab); return LIA_ERR_INVALID; }
+  if (ld < vocab) { lia_set_error("lia_topn_logprobs: ld=%ld < vocab=%d", ld, vocab); return LIA_ERR_INVALID; }
+  if (n_top < 0 || n_top > LIA_LOGPROB_MAX_TOP) { lia_set_error("lia_topn_logprobs: n_top=%d must be in [0, %d]", n_top, LIA_LOGPROB_MAX_TOP); return LIA_ERR_INVALID; }
+  if (n_top > vocab) { lia_set_error("lia_topn_logprobs: n_top=%d alternatives, vocab=%d has fewer", n_top, vocab); return LIA_ERR_INVALID; }
+  if (n_top > 0 && (!top_ids || !top_logprobs)) {
+    lia_set_error("lia_topn_logprobs: NULL %s with n_top=%d (NULL only with n_top = 0)", !top_ids ? "top_ids" : "top_logprobs", n_top);
+    return LIA_ERR_INVALID;
+  }
+  lia_topn_logprobs_launch(logits, ld, M, vocab, ids, n_top, chosen, top_ids, top_logprobs, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return LIA_OK;
 }
@@ -329,6 +390,7 @@ static int lm_rows_chunked(const char* who, lia_ctx* ctx, const bf16_t* hidden, 
 static int lm_score_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int M, int H, const bf16_t* norm_w,
                          const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, const int64_t* targets, float* logprobs,
                          int64_t* greedy_ids, hipStream_t st) {
+  if (logprob_sink_refused(who, ctx, "the score heads report log-probabilities themselves and write no sink")) return LIA_ERR_INVALID;
   const int rc = lm_rows_chunked(who, ctx, hidden, ldh, M, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
     lia_token_logprobs_launch(logits, vocab, n, vocab, targets + r0, logprobs + r0, greedy_ids + r0, st);
   });
@@ -370,9 +432,12 @@ static int lm_verify_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, l
   const uint32_t* mask;
   long ldm;
   if (int mrc = token_mask_of(who, ctx, (long)B * T, vocab, &mask, &ldm)) return mrc;
+  LiaSink sk;
+  if (int src = logprob_sink_of(who, ctx, (long)B * T, vocab, &sk)) return src;
   const int rc = lm_rows_chunked(who, ctx, hidden, ldh, B * T, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
     if (mask) lia_verify_argmax_masked_launch(logits, vocab, n, vocab, suppress_token, n_suppress, n_suppress_rows, T, r0, greedy, mask, ldm, st);
     else lia_verify_argmax_rows_launch(logits, vocab, n, vocab, suppress_token, n_suppress, n_suppress_rows, T, r0, greedy, st);
+    sink_write(sk, logits, vocab, n, vocab, greedy + r0, r0, st);
   });
   if (rc) return rc;
   lia_verify_accept_launch(block_ids, greedy, active, B, T, accepted, common, next, st);
@@ -447,6 +512,8 @@ static int lm_verify_sample_impl(const char* who, lia_ctx* ctx, const bf16_t* hi
   const uint32_t* mask;
   long ldm;
   if (int mrc = token_mask_of(who, ctx, (long)B * T, vocab, &mask, &ldm)) return mrc;
+  LiaSink sk;
+  if (int src = logprob_sink_of(who, ctx, (long)B * T, vocab, &sk)) return src;
   hipError_t copy_err = hipSuccess;
   const int rc = lm_rows_chunked(who, ctx, hidden, ldh, B * T, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
     if (mask)
@@ -456,6 +523,7 @@ static int lm_verify_sample_impl(const char* who, lia_ctx* ctx, const bf16_t* hi
     else
       lia_verify_sample_launch(logits, vocab, n, vocab, smp->temperature, smp->top_k, smp->top_p, suppress_token, n_suppress, n_suppress_rows,
                                T, r0, smp->uniforms, smp->ldu, smp->n_steps, smp->step0, smp->step_rows, block_ids, sampled, p_draft, st);
+    sink_write(sk, logits, vocab, n, vocab, sampled + r0, r0, st);
     if (logits_out && copy_err == hipSuccess)
       copy_err = hipMemcpyAsync(logits_out + (size_t)r0 * vocab, logits, (size_t)n * vocab * sizeof(bf16_t), hipMemcpyDeviceToDevice, st);
   });
@@ -508,6 +576,8 @@ static int lm_verify_reject_impl(const char* who, lia_ctx* ctx, const bf16_t* hi
                                  const int32_t* n_suppress_rows, const lia_block_rejector* rej, const int64_t* block_ids,
                                  const int32_t* active, int64_t* token, int32_t* ok, int32_t* accepted, int32_t* common, int64_t* next,
                                  float* p_tok, float* q_tok, float* resid_mass, bf16_t* logits_out, hipStream_t st) {
+  if (logprob_sink_refused(who, ctx, "rejection verification writes none -- an accepted draft token is not this head's own output"))
+    return LIA_ERR_INVALID;
   if (ctx->token_mask) {
     lia_set_error("%s: a token mask is set (lia_ctx_set_token_mask): rejection verification takes none -- the drafter's Q would have to be "
                   "masked the same way", who);

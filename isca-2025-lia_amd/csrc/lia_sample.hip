@@ -15,47 +15,14 @@
 // Membership is a key comparison: K = {key >= kappa_lo(t)}, kappa_lo(t) the smallest key whose s is >= t (a 16-step bisection by
 // one thread).  That is s_i >= t exactly, also where two keys give the same s (-0 / +0, or an s that rounds to 0 or inf).  A token
 // whose s is -inf (the suppressed one) carries no mass and is never kept.  Logits are finite or +-inf, not NaN.
-#include "lia_internal.h"
+#include "lia_row_passes.h"   // key_of, load_keys8, block_excl_scan, find_boundary_bin and the SMP_ key constants
 
-#define SMP_TILE (LIA_ROW_THREADS * 8)   // tokens per pass-E tile: 8 consecutive tokens per thread
 #define SMP_MAX_TILES 256                // pass-E carries kept in LDS: vocab <= 256 * 8192 (lia_sample checks)
-#define SMP_KEY_NEG_INF 0x007F           // key_of(bf16 -inf); keys below it are negative NaNs
-#define SMP_KEY_POS_INF 0xFF80           // key_of(bf16 +inf)
-#define SMP_BINS 4096
 #define SMP_FIX 0x1p40f                  // fixed-point scale of the top-p masses (w <= 1, vocab <= 2^21: sums < 2^61)
 
-__device__ __forceinline__ int key_of(uint32_t h) { return (h & 0x8000u) ? (int)(~h & 0xFFFFu) : (int)(h | 0x8000u); }
 __device__ __forceinline__ float score_of_key(int k, float tau) {
   const uint32_t h = (k & 0x8000) ? (uint32_t)(k & 0x7FFF) : (uint32_t)(~k & 0xFFFF);
   return bf2f((bf16_t)h) / tau;                // the IEEE fp32 division of the contract
-}
-
-// keys of tokens i .. i + 7 (-1 past the end of the row); the suppressed token's key is that of -inf.  MASKED
-// (lia_ctx_set_token_mask): so is that of a token whose bit in the row's allowed-token mask is clear -- mrow: the mask row as bytes;
-// i is a multiple of 8, so byte i >> 3 holds the bits of exactly these 8 tokens.  The passes need nothing else: membership, the
-// histograms' bins and the weights are functions of the key.
-template <int MASKED = 0>
-__device__ __forceinline__ void load_keys8(const bf16_t* __restrict__ row, int i, int vocab, bool vec, int suppress, int k[8],
-                                           const uint8_t* __restrict__ mrow = nullptr) {
-  if (vec && i < vocab) {            // vec: vocab % 8 == 0 and 16-byte aligned rows
-    const uint4 v = *(const uint4*)(row + i);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) k[e] = key_of((w[e >> 1] >> ((e & 1) * 16)) & 0xffffu);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) k[e] = i + e < vocab ? key_of(row[i + e]) : -1;
-  }
-  const unsigned d = (unsigned)(suppress - i);
-  if (d < 8u) k[d] = SMP_KEY_NEG_INF;
-  if constexpr (MASKED) {
-    if (i < vocab) {
-      const uint32_t allow = mrow[i >> 3];
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        if (k[e] >= 0 && !((allow >> e) & 1u)) k[e] = SMP_KEY_NEG_INF;
-    }
-  }
 }
 
 // smallest key in (-inf, +inf] whose score is >= t (keys above SMP_KEY_NEG_INF: a -inf score is never kept)
@@ -66,49 +33,6 @@ __device__ int key_lower_bound(float t, float tau) {
     if (score_of_key(mid, tau) >= t) hi = mid; else lo = mid + 1;
   }
   return lo;
-}
-
-// exclusive prefix sum over the workgroup in thread order; *total (if not NULL): the sum of all, the same bits in every thread.
-// red: LIA_ROW_WAVES T of LDS.
-template <typename T> __device__ __forceinline__ T block_excl_scan(T v, T* red, T* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  T x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  T ex = __shfl_up(x, 1, 64);
-  if (lane == 0) ex = 0;
-  if (lane == 63) red[w] = x;
-  __syncthreads();
-  T pre = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < LIA_ROW_WAVES; ++i) {
-    const T r = red[i];
-    if (i < w) pre += r;
-    tot += r;
-  }
-  __syncthreads();
-  if (total) *total = tot;
-  return pre + ex;
-}
-
-// The bin b of h[0 .. SMP_BINS) (bins in descending key order from the top) with  above(b) < thr <= above(b) + h[b],
-// above(b) = the sum of the bins above b.  Thread t owns bins 4095 - 4t - j, j < 4.  Writes (bin, above) to *out_bin, *out_above.
-template <typename T> __device__ __forceinline__ void find_boundary_bin(const T* h, T thr, T* red, int* out_bin, T* out_above) {
-  const int t = threadIdx.x;
-  if (t == 0) { *out_bin = 0; *out_above = 0; }     // (no bin qualifies only for a row without mass: no token is kept then)
-  T v[4], s = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { v[j] = h[SMP_BINS - 1 - 4 * t - j]; s += v[j]; }
-  T above = block_excl_scan<T>(s, red, (T*)nullptr);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (above < thr && thr <= above + v[j]) { *out_bin = SMP_BINS - 1 - 4 * t - j; *out_above = above; }
-    above += v[j];
-  }
-  __syncthreads();
 }
 
 // The row passes' LDS, shared by every kernel of this file (each is one row workgroup running the passes one after the other)

@@ -12,74 +12,18 @@
 // not taken -- its extra roundings have no bound as short as the one above.
 // exp is ocml's expf (about 1 ulp), log is logf.  -inf logits add exactly 0; a row of nothing but -inf has no distribution and
 // gives NaN.  A target outside [0, vocab) -- -1 is the documented "no target" -- gives 0.0.  Logits are finite or +-inf, not NaN.
-#include "lia_internal.h"
+#include "lia_row_passes.h"   // load_logits8 and the two passes (row_max_sum), shared with lia_topn_logprobs_kernel
 
 static_assert(LIA_ROW_THREADS == LIA_SCORE_ROW_THREADS, "lia_hip.h states the row kernel's lane count for the error bound of its tests");
-
-__device__ __forceinline__ void load_logits8(const bf16_t* __restrict__ row, int i, int vocab, bool vec, float f[8]) {
-  if (vec) {                       // vec: vocab % 8 == 0, ld % 8 == 0 and a 16-byte aligned base; i < vocab
-    const uint4 v = *(const uint4*)(row + i);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = bf2f((w[e >> 1] >> ((e & 1) * 16)) & 0xffff);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = i + e < vocab ? bf2f(row[i + e]) : -INFINITY;    // (-inf past the end: no maximum, no mass)
-  }
-}
 
 __global__ __launch_bounds__(LIA_ROW_THREADS) void lia_token_logprobs_kernel(const bf16_t* __restrict__ logits, long ld, int vocab, int vec,
                                                                              const int64_t* __restrict__ targets,
                                                                              float* __restrict__ logprobs, int64_t* __restrict__ greedy) {
-  __shared__ float sv[LIA_ROW_WAVES];
-  __shared__ int si[LIA_ROW_WAVES];
-  __shared__ float ss[LIA_ROW_WAVES];
-  const int tid = threadIdx.x, lane = tid & 63;
   const bf16_t* row = logits + (long)blockIdx.x * ld;
-
-  // ---- pass 1: the maximum and its first index; indices ascend inside a lane, so a lane keeps the first of equal values ----
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int i = tid * 8; i < vocab; i += LIA_ROW_THREADS * 8) {
-    float f[8];
-    load_logits8(row, i, vocab, vec, f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (i + e < vocab && (f[e] > best || (f[e] == best && i + e < bi))) { best = f[e]; bi = i + e; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-  }
-  if (lane == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
-  __syncthreads();
-  best = sv[0]; bi = si[0];
-#pragma unroll
-  for (int w = 1; w < LIA_ROW_WAVES; ++w)
-    if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-  const float m = best;              // the same bits in every thread
-
-  // ---- pass 2: s = sum exp(l - m); the row comes from L2 ----
-  float s = 0.f;
-  for (int i = tid * 8; i < vocab; i += LIA_ROW_THREADS * 8) {
-    float f[8];
-    load_logits8(row, i, vocab, vec, f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s += expf(f[e] - m);
-  }
-  s = wave_sum(s);
-  if (lane == 0) ss[tid >> 6] = s;
-  __syncthreads();
-  s = ss[lane & (LIA_ROW_WAVES - 1)];
-#pragma unroll
-  for (int o = LIA_ROW_WAVES / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-
-  if (tid == 0) {
-    const int64_t t = targets[blockIdx.x];
-    greedy[blockIdx.x] = bi == 0x7fffffff ? 0 : bi;
-    logprobs[blockIdx.x] = (t >= 0 && t < (int64_t)vocab) ? bf2f(row[t]) - (m + logf(s)) : 0.f;
+  const RowMaxSum p = row_max_sum(row, vocab, vec);
+  if (threadIdx.x == 0) {
+    greedy[blockIdx.x] = p.bi == 0x7fffffff ? 0 : p.bi;
+    logprobs[blockIdx.x] = row_logprob(row, vocab, targets[blockIdx.x], p.m, p.s);
   }
 }
 

@@ -138,6 +138,8 @@ SIGNATURES = {
     "lia_ctx_set_key_starts": (c_int, [c_void_p, c_void_p, c_int]),
     "lia_ctx_set_row_lens": (c_int, [c_void_p, c_void_p, c_int]),
     "lia_ctx_set_token_mask": (c_int, [c_void_p, c_void_p, c_long, c_int]),
+    "lia_ctx_set_logprob_sink": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_long]),
+    "lia_topn_logprobs": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lia_attn_block_takes": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "lia_attn_split_chunk": (c_int, [c_int]),
     "lia_attn_split_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),

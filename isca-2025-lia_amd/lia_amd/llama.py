@@ -219,10 +219,11 @@ class LlamaScheduler:
         return self.hidden.get(B, T)
 
     def forward(self, input_ids, kv_state, gpu_percentage=100, num_minibatch=1, pin_weight=True, enable_cxl=False,
-                suppress_token=-1, sampler=None, token_mask=None, **_ignored):
+                suppress_token=-1, sampler=None, token_mask=None, logprobs=None, **_ignored):
         """sampler (sampling.Sampler, generate(do_sample=True)): the returned ids are its draw from the logits instead of their argmax.
         token_mask (int32 CUDA [B, W] or one broadcast row, constraints.Constraint): the allowed-token table of this call's head,
-        set on the context around lm_head and the sampler only (lia_ctx_set_token_mask)."""
+        set on the context around lm_head and the sampler only (lia_ctx_set_token_mask).  logprobs (ops.LogprobRequest): as
+        OffloadScheduler.forward -- the log-probability of every returned id and its n_top alternatives, in the request's tensors."""
         m, sh = self.model, self.model.shape
         lib = N.lib()
         B, T = input_ids.shape
@@ -234,6 +235,8 @@ class LlamaScheduler:
         x_lm, T_lm = (x, T) if xlast is None else (xlast, 1)     # (the last layer already reduced the block to its last position)
         if token_mask is not None:
             ctx.set_token_mask(token_mask)
+        if logprobs is not None:
+            ctx.set_logprob_sink(logprobs, (B,))
         try:
             ctx.token_mask_fits(sh.vocab)
             N.check(lib.lia_llama_lm_head(ctx.handle, ctypes.c_void_p(x_lm.data_ptr()), B, T_lm, sh.hidden, ctypes.c_void_p(m.final_norm_w.data_ptr()),
@@ -244,6 +247,8 @@ class LlamaScheduler:
         finally:
             if token_mask is not None:
                 ctx.set_token_mask(None)
+            if logprobs is not None:
+                ctx.set_logprob_sink(None)
         ctx.synchronize()
         kv_state.len += T
         return logits, nxt_ids
@@ -271,11 +276,13 @@ class LlamaScheduler:
         return lp.view(B, T), greedy.view(B, T)
 
     def verify(self, block_ids, kv_state, suppress_token=-1, n_suppress=0, active=None, gpu_percentage=100, num_minibatch=1,
-               pin_weight=True, enable_cxl=False, sampler=None, return_logits=False, rejector=None, token_mask=None, **_ignored):
+               pin_weight=True, enable_cxl=False, sampler=None, return_logits=False, rejector=None, token_mask=None, logprobs=None,
+               **_ignored):
         """Speculative verification: OffloadScheduler.verify for a Llama -- the block [pending | draft] appended at kv_state.len,
         every position through the last layer with the block attention kernel, lia_llama_lm_verify; -> (ops.VerifyResult, common),
         kv_state.len = pos0 + common + 1.  sampler / return_logits / rejector: sampled and rejection verification, as
-        OffloadScheduler.verify.  token_mask (int32 CUDA [B, T, W] or one broadcast row): the verify head's allowed-token table."""
+        OffloadScheduler.verify.  token_mask (int32 CUDA [B, T, W] or one broadcast row): the verify head's allowed-token table.
+        logprobs (ops.LogprobRequest): the head's own id of every block position with its log-probability and alternatives."""
         check_verify_block(block_ids, kv_state)
         m, sh = self.model, self.model.shape
         pos0 = kv_state.len
@@ -289,6 +296,8 @@ class LlamaScheduler:
         act_dev = None if active is None else torch.as_tensor(active).to(device="cuda", dtype=torch.int32).contiguous()
         if token_mask is not None:
             self.ctx.set_token_mask(token_mask)
+        if logprobs is not None:
+            self.ctx.set_logprob_sink(logprobs, tuple(block_ids.shape))
         try:
             if rejector is not None:
                 res = self.ctx.llama_lm_verify_reject(x, m.final_norm_w, m.lm_head, ids_dev, rejector, sh.rms_eps, suppress_token, n_suppress,
@@ -301,6 +310,8 @@ class LlamaScheduler:
         finally:
             if token_mask is not None:
                 self.ctx.set_token_mask(None)
+            if logprobs is not None:
+                self.ctx.set_logprob_sink(None)
         self.ctx.synchronize()
         common = int(res.common.item())
         kv_state.len = pos0 + common + 1

@@ -37,6 +37,27 @@ VerifyResult = collections.namedtuple("VerifyResult", "greedy accepted common ne
                                       defaults=(None,) * 6)
 
 
+LOGPROB_MAX_TOP = 32       # LIA_LOGPROB_MAX_TOP (include/lia_hip.h)
+
+
+class LogprobRequest:
+    """forward(logprobs=) / verify(logprobs=): ask the head of that one call for the log-probability of every id it emits and the
+    n_top most likely tokens beside it, under the model's own distribution (lia_ctx_set_logprob_sink).  After the call: chosen
+    (float32 [rows...]), top_ids (int64 [rows..., n_top]) and top_logprobs (float32 [rows..., n_top]) on the device -- rows... is [B]
+    behind forward, [B, T] behind verify."""
+
+    def __init__(self, n_top):
+        self.n_top = int(n_top)
+        self.chosen = self.top_ids = self.top_logprobs = None
+
+    def allocate(self, shape, device):
+        shape = tuple(int(d) for d in shape)
+        self.chosen = torch.empty(shape, dtype=torch.float32, device=device)
+        self.top_ids = torch.empty(shape + (self.n_top,), dtype=torch.int64, device=device)
+        self.top_logprobs = torch.empty(shape + (self.n_top,), dtype=torch.float32, device=device)
+        return self
+
+
 class Context:
     """lia_ctx: compute stream + D2H stream + per-layer workspace (include/lia_hip.h)."""
 
@@ -49,6 +70,7 @@ class Context:
         self.workspace_alloc_bytes = workspace_bytes
         self.stream = self.lib.lia_ctx_compute_stream(h)
         self._token_mask = None          # (tensor [rows, W], ldm in words): the table lia_ctx_set_token_mask points at
+        self._logprob_sink = None        # the LogprobRequest whose tensors lia_ctx_set_logprob_sink points at
 
     @property
     def workspace_bytes(self):
@@ -222,13 +244,56 @@ class Context:
         N.check(self.lib.lia_ctx_set_token_mask(self.handle, ctypes.c_void_p(m.data_ptr() + 4 * r0 * ldm), ldm, rows - r0 if ldm else 1),
                 "lia_ctx_set_token_mask")
 
+    def set_logprob_sink(self, req, shape=None):
+        """lia_ctx_set_logprob_sink: req (LogprobRequest; its tensors are allocated here for a head call on `shape` = [B] or [B, T]
+        rows, on the device) or None to clear.  While it is set every head call on this context also writes, per row, the
+        log-probability of the id it emits and the n_top alternatives.  The library keeps the pointers only: this object keeps the
+        request alive; its tensors are read once the compute stream has passed the head call."""
+        if req is None:
+            self._logprob_sink = None
+            N.check(self.lib.lia_ctx_set_logprob_sink(self.handle, 0, None, None, None, 0), "lia_ctx_set_logprob_sink")
+            return
+        if not isinstance(req, LogprobRequest):
+            raise ValueError(f"logprobs: expected an ops.LogprobRequest, got {type(req).__name__}")
+        if not 0 <= req.n_top <= LOGPROB_MAX_TOP:
+            raise ValueError(f"logprobs: n_top={req.n_top} must be in [0, {LOGPROB_MAX_TOP}]")
+        req.allocate(shape, f"cuda:{self.device}")
+        self._logprob_sink = req
+        self._point_logprob_sink(req, 0)
+
+    def _point_logprob_sink(self, req, r0):
+        """the sink from row r0 of the request's tensors on"""
+        n, rows = req.n_top, req.chosen.numel()
+        N.check(self.lib.lia_ctx_set_logprob_sink(self.handle, n, ctypes.c_void_p(req.chosen.data_ptr() + 4 * r0),
+                                                  ctypes.c_void_p(req.top_ids.data_ptr() + 8 * r0 * n) if n else None,
+                                                  ctypes.c_void_p(req.top_logprobs.data_ptr() + 4 * r0 * n) if n else None, rows - r0),
+                "lia_ctx_set_logprob_sink")
+
+    def topn_logprobs(self, logits, ids, n_top, stream=None):
+        """lia_topn_logprobs (the bare kernel): per row of logits [M, vocab] (bf16, rows may be strided) the log-probability of ids[r]
+        (int64 [M]) and the n_top tokens of largest logit with theirs, ordered by logit descending, ties by the lower id.  Returns
+        (float32 [M], int64 [M, n_top], float32 [M, n_top]) on the device."""
+        if not logits.is_cuda or logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+            raise ValueError(f"logits: expected a [M, vocab] bf16 CUDA tensor with unit column stride, got {logits.dtype} {logits.device} "
+                             f"shape {tuple(logits.shape)} strides {logits.stride()}")
+        M, vocab = logits.shape
+        _chk(ids, torch.int64)
+        if ids.numel() != M:
+            raise ValueError(f"ids has {ids.numel()} entries, logits {M} rows")
+        n = int(n_top)
+        out = LogprobRequest(max(n, 0)).allocate((M,), logits.device)
+        N.check(self.lib.lia_topn_logprobs(self.handle, _ptr(logits), logits.stride(0), M, vocab, _ptr(ids), n, _ptr(out.chosen),
+                                           _ptr(out.top_ids) if n > 0 else None, _ptr(out.top_logprobs) if n > 0 else None,
+                                           self._st(stream)), "lia_topn_logprobs")
+        return out.chosen, out.top_ids, out.top_logprobs
+
     LM_HEAD_ROWS = 256       # rows per lia_lm_head call (its argmax scratch is sized for that many)
 
     def lm_head(self, hidden, lnw, lnb, emb, eps=1e-5, suppress_token=-1, stream=None):
         """final LN + tied lm_head on the LAST position + argmax (models.py:424-431, greedy_search.py:367).  A batch beyond 256 rows
         (the reference's --batch-size 900 ... 1580 lines, llm/scripts/cxl_offloading.sh:13-39) goes through in chunks of 256 rows:
         rows are independent, the results are those of one call.  With a token mask set (set_token_mask) chunk b0 reads the table
-        from its row b0 on; the table is pointed back at row 0 afterwards."""
+        from its row b0 on; the table is pointed back at row 0 afterwards.  A log-probability sink (set_logprob_sink) likewise."""
         for t in (hidden, lnw, lnb, emb):
             _chk(t)
         B, T, H = hidden.shape
@@ -239,16 +304,23 @@ class Context:
         tm = self._token_mask if B > self.LM_HEAD_ROWS else None
         if tm is not None and 1 < tm.shape[0] < B:
             raise ValueError(f"lia_lm_head: the call has {B} rows, the token mask table {tm.shape[0]}")
+        lp = self._logprob_sink if B > self.LM_HEAD_ROWS else None
+        if lp is not None and lp.chosen.numel() < B:
+            raise ValueError(f"lia_lm_head: the call has {B} rows, the log-probability sink {lp.chosen.numel()}")
         try:
             for b0 in range(0, B, self.LM_HEAD_ROWS):
                 nb = min(self.LM_HEAD_ROWS, B - b0)
                 if tm is not None and b0:
                     self._point_token_mask(tm, b0)
+                if lp is not None and b0:
+                    self._point_logprob_sink(lp, b0)
                 N.check(self.lib.lia_lm_head(self.handle, _ptr(hidden[b0:b0 + nb]), nb, T, H, _ptr(lnw), _ptr(lnb), _ptr(emb), vocab, eps, suppress_token,
                                              _ptr(logits[b0:b0 + nb]), _ptr(nxt[b0:b0 + nb]), self._st(stream)), "lia_lm_head")
         finally:
             if tm is not None:
                 self._point_token_mask(tm, 0)
+            if lp is not None:
+                self._point_logprob_sink(lp, 0)
         return logits, nxt
 
     def sample(self, logits, temperature, top_k, top_p, uniforms, suppress_token=-1, stats=None, stream=None):

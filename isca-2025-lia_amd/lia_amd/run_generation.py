@@ -150,6 +150,10 @@ def build_parser():
                    help="with --sampled-verify: draw = accept a draft token iff it equals the sampler's own draw; rejection = the draft model "
                         "samples its own logits and a token is accepted with probability min(1, p / q), else a draw of the residual "
                         "(an exact sample, but not the ids of plain --do-sample; common acceptance only, not with --draft-coupled)")
+    p.add_argument("--logprobs", default=None, type=int,
+                   help="report every generated token's log-probability and its N most likely alternatives (generate(logprobs=N), "
+                        "N in 0..32; the model's own distribution, before temperature / filters / constraints): printed per token "
+                        "with --prompt, written to --result-json")
     p.add_argument("--suppress-tokens", default=None, type=str,
                    help="constrained decoding: token ids no row may emit, e.g. 5,6,7 (generate(suppress_tokens=): they count as -inf in "
                         "the argmax and in the sampler)")
@@ -158,6 +162,19 @@ def build_parser():
                         "line; every other token counts as -inf (not with --acceptance row or --verify-rule rejection)")
     add_init_args(p)
     return p
+
+
+def format_logprobs(lp, new_ids, tokenizer=None, row=0):
+    """--logprobs: one line per generated token of `row` -- the token, its log-probability under the model's own distribution, and
+    the alternatives of that step (logprobs.TokenLogprobs; new_ids: the generated ids [B, n_new])"""
+    name = (lambda t: repr(tokenizer.decode([t]))) if tokenizer is not None else str
+    lines = []
+    for s_, tok in enumerate(new_ids[row].tolist()):
+        alts = ", ".join(f"{name(int(i))} {float(v):.4f}" for i, v in zip(lp.top_ids[row, s_].tolist(), lp.top_logprobs[row, s_].tolist())
+                         if i >= 0)
+        lines.append(f"  step {s_}: {name(tok)} logprob {float(lp.token_logprobs[row, s_]):.4f}" + (f" | top: {alts}" if alts else ""))
+    lines.append(f"  sequence logprob {float(lp.sequence_logprob()[row]):.4f}")
+    return lines
 
 
 def constraint_kwargs(args, vocab):
@@ -729,6 +746,12 @@ def _main(args, rec=None):
             generate_kwargs.update(sampled_verify=True)
             if args.verify_rule != "draw":
                 generate_kwargs.update(verify_rule=args.verify_rule)
+    if args.logprobs is not None:
+        if args.followup:
+            raise SystemExit("[ERROR] --logprobs with --followup is not supported on the command line (generate(past=, logprobs=) serves it)")
+        if args.profile:
+            raise SystemExit("[ERROR] --logprobs with --profile is not supported: the profiled generate() keeps its own result layout")
+        generate_kwargs["logprobs"] = args.logprobs
     tokenizer = load_tokenizer(args.model_id)
     if args.prompt_file is not None:
         input_ids, generate_kwargs["attention_mask"] = prompt_file_inputs(args, model.shape.vocab, tokenizer,
@@ -751,7 +774,7 @@ def _main(args, rec=None):
         tic = time.time()
         # (not with a drafter: the brackets describe a prefill and single-token decode steps, and the first verify pass may move
         # to a larger workspace -- a new library context -- between them)
-        if rec is not None and spec_log is None and i == 0 and args.num_warmup >= 1 and hasattr(sched, "coop_report"):
+        if rec is not None and spec_log is None and args.logprobs is None and i == 0 and args.num_warmup >= 1 and hasattr(sched, "coop_report"):
             profile_once(model, input_ids, generate_kwargs, warm=False)       # the first warm-up iteration, bracketed
             output = profile_once.last[0]
             if not args.token_latency:
@@ -761,7 +784,8 @@ def _main(args, rec=None):
                                                   "dominant_decode": _dominant(rows, "decode")}
         else:
             output = generate(model, input_ids, **generate_kwargs)
-        gen_ids = output[0] if args.token_latency else output
+        gen_ids = output[0] if (args.token_latency or args.logprobs is not None) else output
+        token_lp = output[-1] if args.logprobs is not None else None
         toc = time.time()
         total_new_tokens = [int(o.shape[0] - i_.shape[0]) for i_, o in zip(input_ids, gen_ids)]
         if tokenizer is not None and args.prompt is not None:                 # run_generation.py:321-323
@@ -770,6 +794,8 @@ def _main(args, rec=None):
             for b, text in enumerate(tokenizer.batch_decode(gen_ids[:, input_ids.shape[1]:], skip_special_tokens=True)):
                 print(f"row {b}: {text!r}", flush=True)
         print(gen_ids[0, input_ids.shape[1]:].tolist(), total_new_tokens[:4], flush=True)
+        if token_lp is not None and args.prompt is not None:
+            print("\n".join(format_logprobs(token_lp, gen_ids[:, input_ids.shape[1]:], tokenizer)), flush=True)
         print("Iteration: %d, Time: %.6f sec" % (i, toc - tic), flush=True)
         if rec is not None:
             from . import hostinfo as _hi
@@ -789,6 +815,9 @@ def _main(args, rec=None):
                                 "fraction_of_63_gbs_link_over_wall": round(b / max(total_time, 1e-9) / 63e9, 3),
                                 "wire_format": ("pack10" if any(getattr(st, "packed", 0) for st in model.layers) else "raw"),
                                 "wire_format_note": "the format of the host copies that streamed (a policy-1 / NUMA-tier / unpinned placement ships raw: scheduler.placement_formats)"}
+    if args.logprobs is not None:                                  # the last iteration's arrays
+        res["logprobs"] = {"n_top": args.logprobs, "token_logprobs": token_lp.token_logprobs.tolist(), "top_ids": token_lp.top_ids.tolist(),
+                           "top_logprobs": token_lp.top_logprobs.tolist(), "sequence_logprob": token_lp.sequence_logprob().tolist()}
     if spec_log is not None:
         # (with a drafter a latency entry is a target pass of several tokens: "Average 2... latency" above is per pass)
         res["speculative"] = summarize_speculation(spec_log, total_list, args.batch_size, acceptance=args.acceptance)

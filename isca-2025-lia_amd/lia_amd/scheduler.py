@@ -303,7 +303,7 @@ class OffloadScheduler:
     # the step record `s`; none reaches back.
     def forward(self, input_ids, kv_state, prefill_policy=1, decoding_policy=1, no_overlap=False, pin_weight=False,
                 gpu_percentage=0, num_minibatch=1, enable_cxl=False, max_new_tokens=None, suppress_token=-1, cpu_layers=0,
-                cpu_layers_start=None, sampler=None, append_policy=None, token_mask=None):
+                cpu_layers_start=None, sampler=None, append_policy=None, token_mask=None, logprobs=None):
         """cpu_layers (build-defined): with decoding policy 2, that many of the streamed layers run
         their decode step entirely on the host cores (policy 1, weights read in place) instead of crossing the link --
         the cooperative split of the reference taken per layer.  Prefill is unaffected (policy 0 for every layer).
@@ -314,7 +314,10 @@ class OffloadScheduler:
         prefill policy like every multi-token call, or by append_policy = 2 where the caches live on the host -- q, k, v of the
         block travel to the host attention instead of the cached prefix to the GPU (the one multi-token policy 2).
         token_mask (int32 CUDA [B, W] or one broadcast row [1, W], constraints.Constraint): the allowed-token table of this call's
-        head -- set on the context around lm_head and the sampler, cleared behind them (lia_ctx_set_token_mask)."""
+        head -- set on the context around lm_head and the sampler, cleared behind them (lia_ctx_set_token_mask).
+        logprobs (ops.LogprobRequest): the head also leaves, per row, the log-probability of the id it returns (the argmax, or the
+        sampler's draw) and the request's n_top alternatives in the request's device tensors [B] / [B, n_top] -- the sink is set
+        around lm_head and the sampler only (lia_ctx_set_logprob_sink)."""
         s = self._validate(input_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch, append_policy)
         self._place(s, kv_state, pin_weight, enable_cxl, max_new_tokens, cpu_layers, cpu_layers_start)
         m, sh, ctx = self.model, self.model.shape, self.ctx
@@ -333,6 +336,8 @@ class OffloadScheduler:
                 ctx.set_option(N.LIA_OPT_SPLIT_DECODE, 0)
         if token_mask is not None:
             ctx.set_token_mask(token_mask)
+        if logprobs is not None:
+            ctx.set_logprob_sink(logprobs, (s.B,))
         try:
             logits, nxt = ctx.lm_head(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, sh.ln_eps, suppress_token)
             if sampler is not None:
@@ -340,6 +345,8 @@ class OffloadScheduler:
         finally:
             if token_mask is not None:
                 ctx.set_token_mask(None)
+            if logprobs is not None:
+                ctx.set_logprob_sink(None)
         self._deliver(s, kv_state)
         return logits, nxt
 
@@ -384,7 +391,7 @@ class OffloadScheduler:
 
     def verify(self, block_ids, kv_state, suppress_token=-1, n_suppress=0, active=None, prefill_policy=1, decoding_policy=1,
                no_overlap=False, pin_weight=False, gpu_percentage=0, num_minibatch=1, enable_cxl=False, append_policy=None,
-               sampler=None, return_logits=False, rejector=None, token_mask=None, **_decode_only):
+               sampler=None, return_logits=False, rejector=None, token_mask=None, logprobs=None, **_decode_only):
         """Speculative verification: one pass of the weights over block_ids [B, T] = [pending | d_1 .. d_{T-1}]
         appended at kv_state.len on a NON-EMPTY cache.  forward()'s phases with the last layer on every position, lm_verify in
         place of lm_head and LIA_OPT_BLOCK_ATTENTION set around the layers; the K/V rows are delivered as in forward().  Returns
@@ -397,7 +404,9 @@ class OffloadScheduler:
         measurements) also returns the block's logits.  rejector (sampling.RejectorBlock, rejection verification of a stochastic
         drafter's block): the head is lm_verify_reject -- res.greedy holds `token`, res.ok / p_tok / q_tok / resid_mass the accept
         test.  Everything else is the same pass.  token_mask (int32 CUDA [B, T, W] or one broadcast row): the allowed-token table of
-        the verify head, row (b, t) for block position t of row b; set around the head call only.  Not with a rejector."""
+        the verify head, row (b, t) for block position t of row b; set around the head call only.  Not with a rejector.
+        logprobs (ops.LogprobRequest): the verify head also leaves, per block position, the log-probability of ITS id there
+        (res.greedy[b, t]) and the n_top alternatives in the request's device tensors [B, T] / [B, T, n_top].  Not with a rejector."""
         from . import speculative
         check_verify_block(block_ids, kv_state)
         B, T = block_ids.shape
@@ -421,11 +430,15 @@ class OffloadScheduler:
             ctx.set_option(N.LIA_OPT_BLOCK_ATTENTION, 0)
         if token_mask is not None:
             ctx.set_token_mask(token_mask)
+        if logprobs is not None:
+            ctx.set_logprob_sink(logprobs, (B, T))
         try:
             res = self._verify_head(ctx, hidden, ids_dev, act_dev, suppress_token, n_suppress, sampler, rejector, return_logits)
         finally:
             if token_mask is not None:
                 ctx.set_token_mask(None)
+            if logprobs is not None:
+                ctx.set_logprob_sink(None)
         self._deliver(s, kv_state)
         common = int(res.common.item())
         kv_state.len = pos0 + common + 1

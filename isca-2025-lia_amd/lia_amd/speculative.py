@@ -435,7 +435,7 @@ def speculative_search_rows(model, sched, input_ids, max_new_tokens, min_new_tok
 
 def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, eos_token_id, pad_token_id, token_latency, lia,
                        draft, draft_tokens, spec_log=None, step_hook=None, max_steps=None, past=None, return_state=False,
-                       reserve_tokens=0, starts=None, sampler=None, rejector=None, constraint=None):
+                       reserve_tokens=0, starts=None, sampler=None, rejector=None, constraint=None, logprobs=None):
     """_greedy_search with a drafter: the ordinary prefill, then rounds of propose -> verify -> append.  The EOS / pad / unfinished
     bookkeeping is applied token by token as the greedy loop applies it; a finished row is inactive (it never limits `common`, its
     block is pad tokens, as the greedy loop feeds them); a round ends behind the token at which a row finishes, so the cache holds
@@ -448,7 +448,11 @@ def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, 
     `common` draft tokens every active row accepted and then res.next -- per row its own accepted draft token or the head's token.
     constraint (constraints.Constraint; greedy and the draw rule): the first forward takes step 0's token mask, a verify pass one row
     per (row, position) -- position t's built from ids + draft[:t].  The drafter is not told: a proposal the mask forbids is simply
-    not accepted, and the ids are those of the plain constrained run."""
+    not accepted, and the ids are those of the plain constrained run.
+    logprobs (int N; greedy and the draw rule): the first forward and every verify pass take a logprobs.LogprobRequest; a round keeps
+    the verify head's rows t = 0 .. common of every row -- the accepted draft tokens and the correction token, each the head's own
+    id at its position -- for exactly the tokens it appends; a TokenLogprobs follows the other results."""
+    from . import logprobs as token_logprobs
     from .generation import GenerationState, turn_positions
     if rejector is not None:
         sampler = None
@@ -484,10 +488,14 @@ def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, 
     ids_buf[:, :T] = ids
     limit = max_new_tokens if max_steps is None else min(max_new_tokens, max_steps)
     state = {"step": 0, "unfinished": unfinished}
+    recorder = None if logprobs is None else token_logprobs.Recorder(B, max_new_tokens, logprobs)
 
-    def append(tokens):
-        """one generated token per row, greedy_search.py:398-421; True when the generation is over"""
+    def append(tokens, values=None):
+        """one generated token per row, greedy_search.py:398-421; True when the generation is over.  values: the head's
+        (chosen, top_ids, top_logprobs) of these tokens, recorded for the rows that were unfinished before them"""
         unf = state["unfinished"]
+        if values is not None:
+            recorder.record(state["step"], unf if eos_token_id is not None else None, *values)
         if eos_token_id is not None:
             tokens = tokens * unf + pad_token_id * (1 - unf)
         ids_buf[:, T + state["step"]] = tokens
@@ -506,9 +514,15 @@ def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, 
     tic = time.time()
     suppress = eos_token_id if (eos_token_id is not None and 0 < min_new_tokens) else -1
     first_mask = {} if constraint is None else {"token_mask": constraint.step_mask(0, ids, unfinished, suppress)}
+    request = None if recorder is None else recorder.request()
+    lp_kw = {} if request is None else {"logprobs": request}
     _, nxt = sched.forward(first, kv, max_new_tokens=max_new_tokens, suppress_token=suppress,
-                           **_first_kw(sampler if rejector is None else rejector.sampler), **first_mask, **lia)
-    over, _ = append(nxt.cpu())
+                           **_first_kw(sampler if rejector is None else rejector.sampler), **first_mask, **lp_kw, **lia)
+    if recorder is None:
+        over, _ = append(nxt.cpu())
+    else:
+        tokens, *values = token_logprobs.fetch(nxt, request)
+        over, _ = append(tokens, values)
     latency_list.append(time.time() - tic)
     rnd = 0
     while not over:
@@ -533,9 +547,14 @@ def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, 
         if rview is not None:
             rview.draft_logits = draft.draft_logits        # [B, k, vocab]: the Q behind prop (a finished row's is never looked at)
         mask_kw = {} if constraint is None else {"token_mask": constraint.block_mask(g, ids_buf[:, :T + g], prop, active, sup_tok, n_sup)}
+        request = None if recorder is None else recorder.request()
+        lp_kw = {} if request is None else {"logprobs": request}
         res, common = sched.verify(block, kv, suppress_token=sup_tok, n_suppress=n_sup, active=active.to(torch.int32), **_verify_kw(view),
-                                   **_reject_kw(rview), **mask_kw, **lia)
-        if rview is None:
+                                   **_reject_kw(rview), **mask_kw, **lp_kw, **lia)
+        values = None
+        if recorder is not None:                           # (never with a rejector: generate() refuses the pair)
+            greedy, *values = token_logprobs.fetch(res.greedy, request)
+        elif rview is None:
             greedy = res.greedy.cpu()
         else:                                              # the accepted draft tokens, then each row's token behind them
             greedy = torch.cat([block[:, 1:common + 1], res.next.cpu()[:, None]], dim=1)
@@ -543,7 +562,7 @@ def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, 
             spec_log.append((common, res.accepted.cpu().tolist()))
         n_app = 0
         for i in range(common + 1):
-            over, newly = append(greedy[:, i])
+            over, newly = append(greedy[:, i], None if values is None else [v[:, i] for v in values])
             n_app += 1
             if over or newly:
                 break
@@ -552,6 +571,8 @@ def speculative_search(model, sched, input_ids, max_new_tokens, min_new_tokens, 
     step = state["step"]
     out = ids_buf[:, :T + step].clone() if step < max_new_tokens else ids_buf
     res = (out, latency_list) if token_latency else (out,)
+    if recorder is not None:
+        res = res + (recorder.result(step),)
     if return_state:
         flags = past.flags if past is not None else {key: v for key, v in lia.items() if key != "append_policy"}
         res = res + (GenerationState(kv, out.clone(), starts, flags),)
