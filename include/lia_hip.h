@@ -315,6 +315,40 @@ int lia_llama_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int M, in
 int lia_ctx_set_logprob_sink(lia_ctx* ctx, int n_top, float* chosen, int64_t* top_ids, float* top_logprobs, long rows);
 int lia_topn_logprobs(lia_ctx* ctx, const lia_bf16* logits, long ld, int M, int vocab, const int64_t* ids, int n_top,
                       float* chosen, int64_t* top_ids, float* top_logprobs, void* stream);
+/* ---- repetition, presence and frequency penalties (build-defined): the penalties that depend on a row's own token
+ * history -- HF's repetition_penalty, OpenAI's / vLLM's presence_penalty and frequency_penalty.
+ * A row's state is its COUNT ROW in DEVICE memory, one uint16 word per token: bit 15 = the token occurs in the prompt, bits 0..14 =
+ * n, how often it was generated so far, saturating at 32767.  A table is `rows` count rows ldc words apart; its base is 4-byte
+ * aligned and ldc even (two words share a 32-bit location, which the updates address atomically) and >= vocab.
+ * With theta = repetition (> 0; 1: off), alpha_p = presence, alpha_f = frequency (0: off), token i of a row with word c and raw
+ * bf16 logit l counts as, in fp32 and with every operation rounded on its own (no FMA, a correctly rounded division):
+ *   x = fp32(l);  if (c != 0) x = x < 0 ? x * theta : x / theta;  n = c & 0x7fff;  x = x - alpha_f * float(n);
+ *   x = x - (n > 0 ? alpha_p : 0);  bf16_round_to_nearest_even(x)
+ * +-inf stay +-inf; NaN logits and fp32-subnormal intermediates are not defined.
+ * lia_token_counts_add: ids [rows, n] (int64, device, ldi apart) are added to table rows 0 .. rows - 1.  generated = 0: bit 15 of the
+ *   id's word is set; 1: its count grows by one (saturating).  first (int32 [rows], device, or NULL): positions t < first[b] of row b
+ *   are skipped (left padding); active (int32 [rows], device, or NULL): a row with 0 is skipped (finished rows).  An id outside
+ *   [0, vocab) is ignored; the same id several times in a row counts that often; no other word changes.
+ * lia_apply_penalties: out [M, ldo] = the rows of logits [M, ld] rewritten with the values above under counts [M, ldc]; out ==
+ *   logits (in place) is allowed.  16-byte loads and stores when the three bases are 16-byte aligned and ld, ldc, ldo multiples of 8.
+ * lia_ctx_set_penalties: the context keeps the POINTERS only -- the table and a scratch of rows x lds bf16 values (lds >= vocab), both
+ *   the caller's, alive and (the table) unchanged until the compute stream has passed the head call.  counts == NULL clears it.  WHILE
+ *   IT IS SET lia_lm_head, lia_llama_lm_head and lia_sample run the penalty kernel from the logits they have in hand into the scratch
+ *   and their id kernel -- the masked instantiation while a token mask is set too -- on the scratch; row i of the call reads table row
+ *   i and writes scratch row i.  A penalised call gives, bit for bit, what the same call without penalties gives on logits rewritten
+ *   with the values above.  The logits a head writes stay the raw ones, and a log-probability sink still reads the raw logits: the
+ *   model's own distribution, with the penalised id as chosen.  Without it every head launches exactly what it launched before.
+ * LIA_ERR_INVALID, by name, before anything is launched: repetition not finite or <= 0, presence or frequency not finite, an odd or
+ * non-positive ldc, a table that is not 4-byte aligned, ldc < vocab, ld / ldo < vocab, generated outside {0, 1}, ldi < n, rows or M
+ * < 1, a NULL scratch with a table; at the head call ldc < vocab, lds < vocab or a call with more rows than the table; every verify
+ * head (lia_lm_verify, lia_lm_verify_rows, lia_lm_verify_sample, lia_lm_verify_reject and the lia_llama_ forms: each block position
+ * would need its own counts) and lia_lm_score / lia_llama_lm_score while penalties are set. */
+int lia_token_counts_add(lia_ctx* ctx, uint16_t* counts, long ldc, int rows, int vocab, const int64_t* ids, long ldi, int n,
+                         const int32_t* first, const int32_t* active, int generated, void* stream);
+int lia_apply_penalties(lia_ctx* ctx, const lia_bf16* logits, long ld, int M, int vocab, const uint16_t* counts, long ldc,
+                        float repetition, float presence, float frequency, lia_bf16* out, long ldo, void* stream);
+int lia_ctx_set_penalties(lia_ctx* ctx, const uint16_t* counts, long ldc, int rows, float repetition, float presence, float frequency,
+                          lia_bf16* scratch, long lds);
 /* ---- speculative verification: the greedy token behind every position of a draft block, and how much of the
  * draft it confirms.  hidden [B * T, ldh]: the last layer's output for the block [pending | d_1 .. d_{T-1}] of every row.
  * Final norm + lm_head GEMM per chunk exactly as lia_lm_score (same CHUNK RULE, same workspace, logits never materialised), then

@@ -232,6 +232,31 @@ extern "C" int lia_ctx_set_logprob_sink(lia_ctx* c, int n_top, float* chosen, in
   return LIA_OK;
 }
 
+// the penalties of the head calls: the pointers only, as the token mask -- the caller owns the count table and the scratch of
+// rows x lds bf16 values, and keeps both alive until the compute stream has passed the head call.  The pitches are checked against
+// the vocabulary where it is known, at the head call.
+extern "C" int lia_ctx_set_penalties(lia_ctx* c, const uint16_t* counts, long ldc, int rows, float repetition, float presence,
+                                     float frequency, lia_bf16* scratch, long lds) {
+  if (!c) return LIA_ERR_INVALID;
+  if (!counts) {
+    c->pen_counts = nullptr; c->pen_scratch = nullptr; c->pen_ldc = c->pen_lds = 0; c->pen_rows = 0;
+    return LIA_OK;
+  }
+  if (penalty_args_invalid("lia_ctx_set_penalties", repetition, presence, frequency, counts, ldc, -1)) return LIA_ERR_INVALID;
+  if (rows <= 0) { lia_set_error("lia_ctx_set_penalties: rows=%d must be >= 1", rows); return LIA_ERR_INVALID; }
+  if (!scratch) { lia_set_error("lia_ctx_set_penalties: NULL scratch with a count table (rows x lds bf16 values, the caller's)"); return LIA_ERR_INVALID; }
+  if (lds <= 0) { lia_set_error("lia_ctx_set_penalties: lds=%ld must be >= the vocabulary", lds); return LIA_ERR_INVALID; }
+  c->pen_counts = counts;
+  c->pen_ldc = ldc;
+  c->pen_rows = rows;
+  c->pen_theta = repetition;
+  c->pen_presence = presence;
+  c->pen_frequency = frequency;
+  c->pen_scratch = (bf16_t*)scratch;
+  c->pen_lds = lds;
+  return LIA_OK;
+}
+
 extern "C" int lia_ctx_set_option(lia_ctx* c, int key, long value) {
   if (!c) return LIA_ERR_INVALID;
   switch (key) {

@@ -76,6 +76,13 @@ extern "C" void lia_verify_argmax_rows_launch(const bf16_t* logits, long ld, int
                                               const int* n_suppress_rows, int T, int r0, int64_t* greedy, hipStream_t st);
 extern "C" void lia_verify_accept_launch(const int64_t* block_ids, const int64_t* greedy, const int* active, int B, int T, int* accepted,
                                          int* common, int64_t* next, hipStream_t st);
+// lia_penalty.hip: out [M, ldo] = logits [M, ld] penalised under counts [M, ldc] (out == logits allowed); ids [B, n] added to counts
+// [B, ldc] -- generated = 0: the prompt bit, 1: the saturating count; first / active: int32 [B] or NULL.  The callers check the
+// pitches (>= vocab; ldc even) and the table's 4-byte alignment
+extern "C" void lia_penalty_launch(const bf16_t* logits, long ld, int M, int vocab, const uint16_t* counts, long ldc, float theta,
+                                   float alpha_p, float alpha_f, bf16_t* out, long ldo, hipStream_t st);
+extern "C" void lia_token_counts_launch(uint16_t* counts, long ldc, int B, int vocab, const int64_t* ids, long ldi, int n, const int* first,
+                                        const int* active, int generated, hipStream_t st);
 // lia_llama.hip
 extern "C" void lia_rmsnorm_launch(const bf16_t* x, long ldx, const bf16_t* w, bf16_t* y, long ldy, long rows, int H, float eps,
                                    hipStream_t st);
@@ -231,6 +238,15 @@ struct lia_ctx {
   float* lp_top;
   int lp_n_top;
   long lp_rows;
+  // penalties (lia_ctx_set_penalties): the CALLER's count table and scratch -- only the pointers are kept.  While it is set lm_head and
+  // sample run lia_penalty_kernel from their logits into the scratch and their id kernel on the scratch; row i of a call reads table
+  // row i and writes scratch row i
+  const uint16_t* pen_counts;  // NULL: no table -- every head call launches what it launched without one
+  long pen_ldc;
+  int pen_rows;
+  float pen_theta, pen_presence, pen_frequency;
+  bf16_t* pen_scratch;
+  long pen_lds;
 };
 
 // the workspace is about to be reused: a norm the previous layer call chained into it is gone, and so is a pending hint
@@ -262,6 +278,10 @@ static inline void chain_publish(lia_ctx* ctx, const void* y, const void* ln, lo
 }
 
 // ---- sub-layer ops the layer operators build on (lia_ops.hip)
+// the penalty settings and a count table (lia_ops.hip), worded once for the three entry points: true = refused, the error is set.
+// vocab < 0: the pitch is checked for evenness only (lia_ctx_set_penalties does not know the vocabulary)
+LIA_HIDDEN bool penalty_args_invalid(const char* who, float repetition, float presence, float frequency, const void* counts, long ldc,
+                                     int vocab);
 LIA_HIDDEN LiaOutMap plain_out(bf16_t* y, long ldy, int N);
 LIA_HIDDEN int gemm_checked(lia_ctx* ctx, const bf16_t* x, long ldx, const bf16_t* w, int M, int N, int K, const LiaEpilogue& ep,
                             const LiaOutMap& om, float* ws, size_t ws_bytes, int split, hipStream_t st, const LiaPost* post = nullptr,

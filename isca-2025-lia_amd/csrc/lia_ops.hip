@@ -222,6 +222,39 @@ static bool logprob_sink_refused(const char* who, const lia_ctx* ctx, const char
   return true;
 }
 
+// The penalties of a head call on `rows` rows (lia_ctx_set_penalties), checked against the call: LIA_OK with pn->counts = NULL (no
+// table: nothing more is launched) or the table, the settings and the scratch; the refusals by name.  The one place that words them.
+struct LiaPenalties { const uint16_t* counts; long ldc; float theta, presence, frequency; bf16_t* scratch; long lds; };
+bool penalty_args_invalid(const char* who, float repetition, float presence, float frequency, const void* counts, long ldc, int vocab) {
+  if (!std::isfinite(repetition) || !(repetition > 0.f)) { lia_set_error("%s: repetition=%g must be finite and > 0 (1: off)", who, (double)repetition); return true; }
+  if (!std::isfinite(presence)) { lia_set_error("%s: presence=%g must be finite (0: off)", who, (double)presence); return true; }
+  if (!std::isfinite(frequency)) { lia_set_error("%s: frequency=%g must be finite (0: off)", who, (double)frequency); return true; }
+  if ((uintptr_t)counts & 3) { lia_set_error("%s: counts=%p is not 4-byte aligned (two words share a 32-bit location)", who, counts); return true; }
+  if (ldc % 2 || ldc <= 0) { lia_set_error("%s: ldc=%ld must be even and > 0 (two words share a 32-bit location)", who, ldc); return true; }
+  if (vocab >= 0 && ldc < vocab) { lia_set_error("%s: ldc=%ld < vocab=%d", who, ldc, vocab); return true; }
+  return false;
+}
+static int penalties_of(const char* who, const lia_ctx* ctx, long rows, int vocab, LiaPenalties* pn) {
+  memset(pn, 0, sizeof(*pn));
+  if (!ctx->pen_counts) return LIA_OK;
+  if (ctx->pen_ldc < vocab) { lia_set_error("%s: the count table has ldc=%ld words per row, vocab=%d (lia_ctx_set_penalties)", who, ctx->pen_ldc, vocab); return LIA_ERR_INVALID; }
+  if (ctx->pen_lds < vocab) { lia_set_error("%s: the penalty scratch has lds=%ld values per row, vocab=%d (lia_ctx_set_penalties)", who, ctx->pen_lds, vocab); return LIA_ERR_INVALID; }
+  if (rows > ctx->pen_rows) { lia_set_error("%s: the call has %ld rows, the count table %d (lia_ctx_set_penalties)", who, rows, ctx->pen_rows); return LIA_ERR_INVALID; }
+  *pn = LiaPenalties{ctx->pen_counts, ctx->pen_ldc, ctx->pen_theta, ctx->pen_presence, ctx->pen_frequency, ctx->pen_scratch, ctx->pen_lds};
+  return LIA_OK;
+}
+// scratch rows 0 .. n - 1 = the n logits rows in hand, penalised under table rows 0 .. n - 1
+static void penalties_write(const LiaPenalties& pn, const bf16_t* logits, long ld, int n, int vocab, hipStream_t st) {
+  lia_penalty_launch(logits, ld, n, vocab, pn.counts, pn.ldc, pn.theta, pn.presence, pn.frequency, pn.scratch, pn.lds, st);
+}
+// the heads that take no penalties
+static bool penalties_refused(const char* who, const lia_ctx* ctx, const char* why) {
+  if (!ctx->pen_counts) return false;
+  lia_set_error("%s: penalties are set (lia_ctx_set_penalties): %s", who, why);
+  return true;
+}
+#define LIA_NO_BLOCK_PENALTIES "every block position would need its own counts -- penalties are not applied under speculation"
+
 // norm_b == nullptr: RMSNorm (Llama), else LayerNorm
 static int lm_head_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, int B, int T, int H, const bf16_t* norm_w, const bf16_t* norm_b,
                         const bf16_t* emb, int vocab, float eps, int suppress_token, bf16_t* logits, int64_t* next_ids, hipStream_t st) {
@@ -232,6 +265,8 @@ static int lm_head_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, int
   if (int mrc = token_mask_of(who, ctx, B, vocab, &mask, &ldm)) return mrc;
   LiaSink sk;
   if (int src = logprob_sink_of(who, ctx, B, vocab, &sk)) return src;
+  LiaPenalties pn;
+  if (int prc = penalties_of(who, ctx, B, vocab, &pn)) return prc;
   if (ctx->ws_bytes < scratch) { lia_set_error("%s: workspace too small", who); return LIA_ERR_MEMORY; }
   ws_invalidate(ctx);
   bf16_t* lno = (bf16_t*)ctx->ws;
@@ -244,8 +279,24 @@ static int lm_head_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, int
   size_t have = ctx->ws_bytes - scratch;
   int rc = gemm_checked(ctx, lno, H, emb, B, vocab, H, ep, om, (float*)(ctx->ws + scratch), std::min(have, gemm_need), 0, st);
   if (rc) return rc;
-  if (mask) lia_argmax_masked_launch(logits, next_ids, B, vocab, suppress_token, mask, ldm, st);
-  else lia_argmax_launch(logits, next_ids, B, vocab, suppress_token, st);
+  if (pn.counts) {
+    // the argmax of the penalised rows: the head's own kernel where the scratch rows are vocab apart (what penalties.py allocates;
+    // 9.0 against 12.4 us at B 64 x 50272), else the verify heads' argmax launch, which takes a pitch (the same scan and tie rule;
+    // T = 1, n_suppress = 1: `suppress` holds for every row, and block row i reads mask row i)
+    penalties_write(pn, logits, vocab, B, vocab, st);
+    if (pn.lds == vocab) {
+      if (mask) lia_argmax_masked_launch(pn.scratch, next_ids, B, vocab, suppress_token, mask, ldm, st);
+      else lia_argmax_launch(pn.scratch, next_ids, B, vocab, suppress_token, st);
+    } else if (mask) {
+      lia_verify_argmax_masked_launch(pn.scratch, pn.lds, B, vocab, suppress_token, 1, nullptr, 1, 0, next_ids, mask, ldm, st);
+    } else {
+      lia_verify_argmax_rows_launch(pn.scratch, pn.lds, B, vocab, suppress_token, 1, nullptr, 1, 0, next_ids, st);
+    }
+  } else if (mask) {
+    lia_argmax_masked_launch(logits, next_ids, B, vocab, suppress_token, mask, ldm, st);
+  } else {
+    lia_argmax_launch(logits, next_ids, B, vocab, suppress_token, st);
+  }
   sink_write(sk, logits, vocab, B, vocab, next_ids, 0, st);
   HIP_TRY(hipGetLastError());
   return LIA_OK;
@@ -295,9 +346,49 @@ extern "C" int lia_sample(lia_ctx* ctx, const lia_bf16* logits, long ld, int B, 
   if (int mrc = token_mask_of("lia_sample", ctx, B, vocab, &mask, &ldm)) return mrc;
   LiaSink sk;
   if (int src = logprob_sink_of("lia_sample", ctx, B, vocab, &sk)) return src;
+  LiaPenalties pn;
+  if (int prc = penalties_of("lia_sample", ctx, B, vocab, &pn)) return prc;
+  const bf16_t* raw = logits;                      // (the sink reads the model's own distribution)
+  const long raw_ld = ld;
+  if (pn.counts) {
+    penalties_write(pn, logits, ld, B, vocab, (hipStream_t)stream);
+    logits = pn.scratch;
+    ld = pn.lds;
+  }
   if (mask) lia_sample_masked_launch(logits, ld, B, vocab, temperature, top_k, top_p, suppress_token, uniforms, next_ids, stats, mask, ldm, (hipStream_t)stream);
   else lia_sample_launch(logits, ld, B, vocab, temperature, top_k, top_p, suppress_token, uniforms, next_ids, stats, (hipStream_t)stream);
-  sink_write(sk, logits, ld, B, vocab, next_ids, 0, (hipStream_t)stream);
+  sink_write(sk, raw, raw_ld, B, vocab, next_ids, 0, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// penalties: the bare kernels (lia_penalty.hip); lia_ctx_set_penalties is in lia_ctx.hip
+// ------------------------------------------------------------------------------------------------
+extern "C" int lia_token_counts_add(lia_ctx* ctx, uint16_t* counts, long ldc, int rows, int vocab, const int64_t* ids, long ldi, int n,
+                                    const int32_t* first, const int32_t* active, int generated, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!counts || !ids) { lia_set_error("lia_token_counts_add: NULL %s", !counts ? "counts" : "ids"); return LIA_ERR_INVALID; }
+  if (rows <= 0) { lia_set_error("lia_token_counts_add: rows=%d must be >= 1", rows); return LIA_ERR_INVALID; }
+  if (vocab <= 0) { lia_set_error("lia_token_counts_add: vocab=%d must be >= 1", vocab); return LIA_ERR_INVALID; }
+  if (n < 0 || ldi < n) { lia_set_error("lia_token_counts_add: n=%d must be >= 0 and ldi=%ld >= n", n, ldi); return LIA_ERR_INVALID; }
+  if (generated != 0 && generated != 1) { lia_set_error("lia_token_counts_add: generated=%d must be 0 (prompt) or 1 (generated)", generated); return LIA_ERR_INVALID; }
+  if (penalty_args_invalid("lia_token_counts_add", 1.f, 0.f, 0.f, counts, ldc, vocab)) return LIA_ERR_INVALID;
+  lia_token_counts_launch(counts, ldc, rows, vocab, ids, ldi, n, first, active, generated, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LIA_OK;
+}
+
+extern "C" int lia_apply_penalties(lia_ctx* ctx, const lia_bf16* logits, long ld, int M, int vocab, const uint16_t* counts, long ldc,
+                                   float repetition, float presence, float frequency, lia_bf16* out, long ldo, void* stream) {
+  if (!ctx) return LIA_ERR_INVALID;
+  if (!logits || !counts || !out) { lia_set_error("lia_apply_penalties: NULL %s", !logits ? "logits" : !counts ? "counts" : "out"); return LIA_ERR_INVALID; }
+  if (M <= 0) { lia_set_error("lia_apply_penalties: M=%d must be >= 1", M); return LIA_ERR_INVALID; }
+  if (vocab <= 0) { lia_set_error("lia_apply_penalties: vocab=%d must be >= 1", vocab); return LIA_ERR_INVALID; }
+  if (ld < vocab) { lia_set_error("lia_apply_penalties: ld=%ld < vocab=%d", ld, vocab); return LIA_ERR_INVALID; }
+  if (ldo < vocab) { lia_set_error("lia_apply_penalties: ldo=%ld < vocab=%d", ldo, vocab); return LIA_ERR_INVALID; }
+  if (penalty_args_invalid("lia_apply_penalties", repetition, presence, frequency, counts, ldc, vocab)) return LIA_ERR_INVALID;
+  lia_penalty_launch(logits, ld, M, vocab, counts, ldc, repetition, presence, frequency, out, ldo, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return LIA_OK;
 }
@@ -391,6 +482,7 @@ static int lm_score_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, lo
                          const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, const int64_t* targets, float* logprobs,
                          int64_t* greedy_ids, hipStream_t st) {
   if (logprob_sink_refused(who, ctx, "the score heads report log-probabilities themselves and write no sink")) return LIA_ERR_INVALID;
+  if (penalties_refused(who, ctx, "the score heads report the model's own distribution and emit no token")) return LIA_ERR_INVALID;
   const int rc = lm_rows_chunked(who, ctx, hidden, ldh, M, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
     lia_token_logprobs_launch(logits, vocab, n, vocab, targets + r0, logprobs + r0, greedy_ids + r0, st);
   });
@@ -424,6 +516,7 @@ static int lm_verify_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, l
                           const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, int suppress_token, int n_suppress,
                           const int64_t* block_ids, const int32_t* active, int64_t* greedy, int32_t* accepted, int32_t* common,
                           int64_t* next, hipStream_t st, const int32_t* n_suppress_rows = nullptr) {
+  if (penalties_refused(who, ctx, LIA_NO_BLOCK_PENALTIES)) return LIA_ERR_INVALID;
   if (B <= 0) { lia_set_error("%s: B=%d must be >= 1", who, B); return LIA_ERR_INVALID; }
   if (T < 2) { lia_set_error("%s: T=%d must be >= 2 (the pending token and at least one draft token)", who, T); return LIA_ERR_INVALID; }
   if ((long)B * T > 0x7fffffffL) { lia_set_error("%s: B=%d x T=%d rows", who, B, T); return LIA_ERR_INVALID; }
@@ -497,6 +590,7 @@ static int lm_verify_sample_impl(const char* who, lia_ctx* ctx, const bf16_t* hi
                                  const int32_t* n_suppress_rows, const lia_block_sampler* smp, const int64_t* block_ids,
                                  const int32_t* active, int64_t* sampled, int32_t* accepted, int32_t* common, int64_t* next,
                                  float* p_draft, bf16_t* logits_out, hipStream_t st) {
+  if (penalties_refused(who, ctx, LIA_NO_BLOCK_PENALTIES)) return LIA_ERR_INVALID;
   if (!smp) { lia_set_error("%s: NULL sampler", who); return LIA_ERR_INVALID; }
   if (!smp->uniforms) { lia_set_error("%s: NULL uniforms", who); return LIA_ERR_INVALID; }
   if (B <= 0) { lia_set_error("%s: B=%d must be >= 1", who, B); return LIA_ERR_INVALID; }
@@ -578,6 +672,7 @@ static int lm_verify_reject_impl(const char* who, lia_ctx* ctx, const bf16_t* hi
                                  float* p_tok, float* q_tok, float* resid_mass, bf16_t* logits_out, hipStream_t st) {
   if (logprob_sink_refused(who, ctx, "rejection verification writes none -- an accepted draft token is not this head's own output"))
     return LIA_ERR_INVALID;
+  if (penalties_refused(who, ctx, LIA_NO_BLOCK_PENALTIES)) return LIA_ERR_INVALID;
   if (ctx->token_mask) {
     lia_set_error("%s: a token mask is set (lia_ctx_set_token_mask): rejection verification takes none -- the drafter's Q would have to be "
                   "masked the same way", who);

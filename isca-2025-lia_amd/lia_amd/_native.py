@@ -140,6 +140,10 @@ SIGNATURES = {
     "lia_ctx_set_token_mask": (c_int, [c_void_p, c_void_p, c_long, c_int]),
     "lia_ctx_set_logprob_sink": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_long]),
     "lia_topn_logprobs": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lia_token_counts_add": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "lia_apply_penalties": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_float, c_float, c_float, c_void_p, c_long,
+                                    c_void_p]),
+    "lia_ctx_set_penalties": (c_int, [c_void_p, c_void_p, c_long, c_int, c_float, c_float, c_float, c_void_p, c_long]),
     "lia_attn_block_takes": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "lia_attn_split_chunk": (c_int, [c_int]),
     "lia_attn_split_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),

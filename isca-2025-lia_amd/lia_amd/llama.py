@@ -219,11 +219,13 @@ class LlamaScheduler:
         return self.hidden.get(B, T)
 
     def forward(self, input_ids, kv_state, gpu_percentage=100, num_minibatch=1, pin_weight=True, enable_cxl=False,
-                suppress_token=-1, sampler=None, token_mask=None, logprobs=None, **_ignored):
+                suppress_token=-1, sampler=None, token_mask=None, logprobs=None, penalties=None, **_ignored):
         """sampler (sampling.Sampler, generate(do_sample=True)): the returned ids are its draw from the logits instead of their argmax.
         token_mask (int32 CUDA [B, W] or one broadcast row, constraints.Constraint): the allowed-token table of this call's head,
         set on the context around lm_head and the sampler only (lia_ctx_set_token_mask).  logprobs (ops.LogprobRequest): as
-        OffloadScheduler.forward -- the log-probability of every returned id and its n_top alternatives, in the request's tensors."""
+        OffloadScheduler.forward -- the log-probability of every returned id and its n_top alternatives, in the request's tensors.
+        penalties (penalties.Penalties): as OffloadScheduler.forward -- the ids come from the logits penalised under the
+        generation's count table, set on the context around the head only."""
         m, sh = self.model, self.model.shape
         lib = N.lib()
         B, T = input_ids.shape
@@ -239,6 +241,8 @@ class LlamaScheduler:
             ctx.set_logprob_sink(logprobs, (B,))
         try:
             ctx.token_mask_fits(sh.vocab)
+            if penalties is not None:
+                penalties.bind(ctx)
             N.check(lib.lia_llama_lm_head(ctx.handle, ctypes.c_void_p(x_lm.data_ptr()), B, T_lm, sh.hidden, ctypes.c_void_p(m.final_norm_w.data_ptr()),
                                           ctypes.c_void_p(m.lm_head.data_ptr()), sh.vocab, sh.rms_eps, suppress_token,
                                           ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(nxt_ids.data_ptr()), st), "lia_llama_lm_head")
@@ -249,6 +253,8 @@ class LlamaScheduler:
                 ctx.set_token_mask(None)
             if logprobs is not None:
                 ctx.set_logprob_sink(None)
+            if penalties is not None:
+                ctx.set_penalties(None)
         ctx.synchronize()
         kv_state.len += T
         return logits, nxt_ids
@@ -411,6 +417,16 @@ class LlamaScheduler:
             raise ValueError("set_token_mask takes None only: a table is passed per call, forward(token_mask=) / verify(token_mask=)")
         if self.ctx is not None:
             self.ctx.set_token_mask(None)
+
+    supports_penalties = True         # forward(penalties=): generate()'s repetition / presence / frequency penalties
+
+    def set_penalties(self, table):
+        """None only (generate() when a penalised generation ends): no count table on the library context; as
+        OffloadScheduler.set_penalties"""
+        if table is not None:
+            raise ValueError("set_penalties takes None only: the table is passed per call, forward(penalties=)")
+        if self.ctx is not None:
+            self.ctx.set_penalties(None)
 
     def stream_stats(self, reset=False):
         return self.pipe.stats(reset) if self.pipe else (0.0, 0.0)

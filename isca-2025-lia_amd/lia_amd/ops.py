@@ -71,6 +71,7 @@ class Context:
         self.stream = self.lib.lia_ctx_compute_stream(h)
         self._token_mask = None          # (tensor [rows, W], ldm in words): the table lia_ctx_set_token_mask points at
         self._logprob_sink = None        # the LogprobRequest whose tensors lia_ctx_set_logprob_sink points at
+        self._penalties = None           # (counts, scratch, repetition, presence, frequency): what lia_ctx_set_penalties points at
 
     @property
     def workspace_bytes(self):
@@ -287,13 +288,97 @@ class Context:
                                            self._st(stream)), "lia_topn_logprobs")
         return out.chosen, out.top_ids, out.top_logprobs
 
+    # ---- penalties (lia_penalty.hip) -----------------------------------------------------------------
+    @staticmethod
+    def _chk_counts(counts):
+        if not isinstance(counts, torch.Tensor) or not counts.is_cuda or counts.dtype not in (torch.int16, torch.uint16) or counts.dim() != 2 \
+                or counts.stride(1) != 1:
+            raise ValueError("count table: expected a 16-bit integer CUDA tensor [rows, ldc] with unit column stride, got "
+                             + (f"{counts.dtype} {counts.device} shape {tuple(counts.shape)}" if isinstance(counts, torch.Tensor)
+                                else type(counts).__name__))
+
+    def set_penalties(self, counts, repetition=1.0, presence=0.0, frequency=0.0, scratch=None, synchronize=True):
+        """lia_ctx_set_penalties: counts (int16 / uint16 CUDA [rows, >= vocab]: bit 15 = in the prompt, bits 0..14 = times generated;
+        or None to clear) and the settings.  While set, lm_head and sample pick their ids from the logits penalised under row i of
+        the table (include/lia_hip.h); the logits they return stay raw.  scratch (bf16 CUDA [rows, >= vocab], allocated here when
+        None) receives the penalised rows.  The library keeps the pointers only: this object keeps the tensors alive.  synchronize=False:
+        the caller knows that torch's stream wrote nothing the head will read (a table kept by the library's own stream)."""
+        if counts is None:
+            self._penalties = None
+            N.check(self.lib.lia_ctx_set_penalties(self.handle, None, 0, 0, 1.0, 0.0, 0.0, None, 0), "lia_ctx_set_penalties")
+            return
+        self._chk_counts(counts)
+        if scratch is None:
+            scratch = torch.empty(tuple(counts.shape), dtype=torch.bfloat16, device=counts.device)
+        if not scratch.is_cuda or scratch.dtype != torch.bfloat16 or scratch.dim() != 2 or scratch.stride(1) != 1 \
+                or scratch.shape[0] < counts.shape[0]:
+            raise ValueError(f"penalty scratch: expected a bf16 CUDA tensor [>= {counts.shape[0]} rows, >= vocab] with unit column stride, got "
+                             f"{scratch.dtype} {scratch.device} shape {tuple(scratch.shape)}")
+        if synchronize:
+            torch.cuda.current_stream().synchronize()          # (the library's stream reads what torch's wrote)
+        self._penalties = (counts, scratch, float(repetition), float(presence), float(frequency))
+        try:
+            self._point_penalties(0)
+        except Exception:
+            self._penalties = None
+            raise
+
+    def _point_penalties(self, r0):
+        """the table and the scratch from their row r0 on"""
+        counts, scratch, theta, presence, frequency = self._penalties
+        N.check(self.lib.lia_ctx_set_penalties(self.handle, ctypes.c_void_p(counts.data_ptr() + 2 * r0 * counts.stride(0)), counts.stride(0),
+                                               counts.shape[0] - r0, theta, presence, frequency,
+                                               ctypes.c_void_p(scratch.data_ptr() + 2 * r0 * scratch.stride(0)), scratch.stride(0)),
+                "lia_ctx_set_penalties")
+
+    def token_counts_add(self, counts, ids, generated, vocab=None, first=None, active=None, stream=None):
+        """lia_token_counts_add: ids (int64 CUDA [B, n], unit column stride) are added to rows 0 .. B - 1 of counts -- generated False:
+        the prompt bit, True: the saturating count.  first / active (int32 CUDA [B] or None): positions t < first[b] and rows with
+        active[b] == 0 are skipped; ids outside [0, vocab) are ignored (vocab: the table's width when None)."""
+        self._chk_counts(counts)
+        if not ids.is_cuda or ids.dtype != torch.int64 or ids.dim() != 2 or (ids.shape[1] > 1 and ids.stride(1) != 1):
+            raise ValueError(f"ids: expected an int64 CUDA tensor [B, n] with unit column stride, got {ids.dtype} {ids.device} "
+                             f"shape {tuple(ids.shape)} strides {ids.stride()}")
+        B, n = ids.shape
+        if B > counts.shape[0]:
+            raise ValueError(f"ids has {B} rows, the count table {counts.shape[0]}")
+        for name, t in (("first", first), ("active", active)):
+            _chk(t, torch.int32)
+            if t is not None and t.numel() != B:
+                raise ValueError(f"{name} has {t.numel()} entries, ids {B} rows")
+        ldi = ids.stride(0) if B > 1 else max(n, 1)
+        N.check(self.lib.lia_token_counts_add(self.handle, _ptr(counts), counts.stride(0), B, counts.shape[1] if vocab is None else int(vocab),
+                                              _ptr(ids), ldi, n, _ptr(first), _ptr(active), int(bool(generated)), self._st(stream)),
+                "lia_token_counts_add")
+
+    def apply_penalties(self, logits, counts, repetition=1.0, presence=0.0, frequency=0.0, out=None, stream=None):
+        """lia_apply_penalties (the bare kernel): the rows of logits [M, vocab] (bf16, rows may be strided) rewritten under counts
+        [M, >= vocab] -> out (a new [M, vocab] tensor when None; `logits` itself: in place)."""
+        self._chk_counts(counts)
+        if not logits.is_cuda or logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+            raise ValueError(f"logits: expected a [M, vocab] bf16 CUDA tensor with unit column stride, got {logits.dtype} {logits.device} "
+                             f"shape {tuple(logits.shape)} strides {logits.stride()}")
+        M, vocab = logits.shape
+        if counts.shape[0] < M:
+            raise ValueError(f"logits has {M} rows, the count table {counts.shape[0]}")
+        if out is None:
+            out = torch.empty((M, vocab), dtype=torch.bfloat16, device=logits.device)
+        elif not out.is_cuda or out.dtype != torch.bfloat16 or tuple(out.shape) != (M, vocab) or out.stride(1) != 1:
+            raise ValueError(f"out: expected a [{M}, {vocab}] bf16 CUDA tensor with unit column stride, got {out.dtype} {out.device} "
+                             f"shape {tuple(out.shape)} strides {out.stride()}")
+        N.check(self.lib.lia_apply_penalties(self.handle, _ptr(logits), logits.stride(0), M, vocab, _ptr(counts), counts.stride(0),
+                                             float(repetition), float(presence), float(frequency), _ptr(out), out.stride(0),
+                                             self._st(stream)), "lia_apply_penalties")
+        return out
+
     LM_HEAD_ROWS = 256       # rows per lia_lm_head call (its argmax scratch is sized for that many)
 
     def lm_head(self, hidden, lnw, lnb, emb, eps=1e-5, suppress_token=-1, stream=None):
         """final LN + tied lm_head on the LAST position + argmax (models.py:424-431, greedy_search.py:367).  A batch beyond 256 rows
         (the reference's --batch-size 900 ... 1580 lines, llm/scripts/cxl_offloading.sh:13-39) goes through in chunks of 256 rows:
         rows are independent, the results are those of one call.  With a token mask set (set_token_mask) chunk b0 reads the table
-        from its row b0 on; the table is pointed back at row 0 afterwards.  A log-probability sink (set_logprob_sink) likewise."""
+        from its row b0 on; the table is pointed back at row 0 afterwards.  A log-probability sink (set_logprob_sink) and the penalties
+        (set_penalties: count table and scratch) likewise."""
         for t in (hidden, lnw, lnb, emb):
             _chk(t)
         B, T, H = hidden.shape
@@ -307,6 +392,9 @@ class Context:
         lp = self._logprob_sink if B > self.LM_HEAD_ROWS else None
         if lp is not None and lp.chosen.numel() < B:
             raise ValueError(f"lia_lm_head: the call has {B} rows, the log-probability sink {lp.chosen.numel()}")
+        pn = self._penalties if B > self.LM_HEAD_ROWS else None
+        if pn is not None and pn[0].shape[0] < B:
+            raise ValueError(f"lia_lm_head: the call has {B} rows, the count table {pn[0].shape[0]}")
         try:
             for b0 in range(0, B, self.LM_HEAD_ROWS):
                 nb = min(self.LM_HEAD_ROWS, B - b0)
@@ -314,6 +402,8 @@ class Context:
                     self._point_token_mask(tm, b0)
                 if lp is not None and b0:
                     self._point_logprob_sink(lp, b0)
+                if pn is not None and b0:
+                    self._point_penalties(b0)
                 N.check(self.lib.lia_lm_head(self.handle, _ptr(hidden[b0:b0 + nb]), nb, T, H, _ptr(lnw), _ptr(lnb), _ptr(emb), vocab, eps, suppress_token,
                                              _ptr(logits[b0:b0 + nb]), _ptr(nxt[b0:b0 + nb]), self._st(stream)), "lia_lm_head")
         finally:
@@ -321,6 +411,8 @@ class Context:
                 self._point_token_mask(tm, 0)
             if lp is not None:
                 self._point_logprob_sink(lp, 0)
+            if pn is not None:
+                self._point_penalties(0)
         return logits, nxt
 
     def sample(self, logits, temperature, top_k, top_p, uniforms, suppress_token=-1, stats=None, stream=None):

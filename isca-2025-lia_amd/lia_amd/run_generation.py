@@ -154,6 +154,13 @@ def build_parser():
                    help="report every generated token's log-probability and its N most likely alternatives (generate(logprobs=N), "
                         "N in 0..32; the model's own distribution, before temperature / filters / constraints): printed per token "
                         "with --prompt, written to --result-json")
+    p.add_argument("--repetition-penalty", default=None, type=float,
+                   help="HF's repetition_penalty (> 0; 1.0: off): the logit of a token of the prompt or generated so far is divided by it "
+                        "(a negative one multiplied), greedy and sampled (generate(repetition_penalty=); not with --draft-model)")
+    p.add_argument("--presence-penalty", default=None, type=float,
+                   help="OpenAI's / vLLM's presence_penalty (0: off): subtracted from the logit of every token generated so far")
+    p.add_argument("--frequency-penalty", default=None, type=float,
+                   help="OpenAI's / vLLM's frequency_penalty (0: off): subtracted once per time the token was generated so far")
     p.add_argument("--suppress-tokens", default=None, type=str,
                    help="constrained decoding: token ids no row may emit, e.g. 5,6,7 (generate(suppress_tokens=): they count as -inf in "
                         "the argmax and in the sampler)")
@@ -201,6 +208,12 @@ def constraint_kwargs(args, vocab):
                              f"the vocabulary [0, {vocab})")
         banned |= set(range(vocab)) - set(ids.tolist())
     return {"suppress_tokens": sorted(banned)} if banned else {}
+
+
+def penalty_kwargs(args):
+    """generate()'s penalty kwargs of the command line: none without --repetition-penalty / --presence-penalty / --frequency-penalty"""
+    names = ("repetition_penalty", "presence_penalty", "frequency_penalty")
+    return {k: getattr(args, k) for k in names if getattr(args, k, None) is not None}
 
 
 def check_spec_sample_flags(args):
@@ -736,6 +749,7 @@ def _main(args, rec=None):
         if args.cpu_layers < 0 and args.cpu_layers_start is not None:
             generate_kwargs["cpu_layers_start"] = args.cpu_layers_start
     generate_kwargs.update(constraint_kwargs(args, model.shape.vocab))
+    generate_kwargs.update(penalty_kwargs(args))
     spec_log = None
     if args.draft_model:
         spec_log = []

@@ -15,7 +15,8 @@ DEVICE = "cuda"          # where generate() draws U (the lia_sample kernel reads
 DEFAULT_TEMPERATURE, DEFAULT_TOP_K, DEFAULT_TOP_P = 1.0, 50, 1.0
 
 # HF sampling knobs this build does not implement, with the value that means "off"; generate(do_sample=True) refuses any other
-UNSUPPORTED = {"repetition_penalty": 1.0, "min_p": None, "typical_p": 1.0, "epsilon_cutoff": 0.0, "eta_cutoff": 0.0,
+# (repetition_penalty is generate()'s own keyword: penalties.py)
+UNSUPPORTED = {"min_p": None, "typical_p": 1.0, "epsilon_cutoff": 0.0, "eta_cutoff": 0.0,
                "no_repeat_ngram_size": 0, "num_return_sequences": 1}
 
 

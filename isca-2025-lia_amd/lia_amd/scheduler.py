@@ -303,7 +303,7 @@ class OffloadScheduler:
     # the step record `s`; none reaches back.
     def forward(self, input_ids, kv_state, prefill_policy=1, decoding_policy=1, no_overlap=False, pin_weight=False,
                 gpu_percentage=0, num_minibatch=1, enable_cxl=False, max_new_tokens=None, suppress_token=-1, cpu_layers=0,
-                cpu_layers_start=None, sampler=None, append_policy=None, token_mask=None, logprobs=None):
+                cpu_layers_start=None, sampler=None, append_policy=None, token_mask=None, logprobs=None, penalties=None):
         """cpu_layers (build-defined): with decoding policy 2, that many of the streamed layers run
         their decode step entirely on the host cores (policy 1, weights read in place) instead of crossing the link --
         the cooperative split of the reference taken per layer.  Prefill is unaffected (policy 0 for every layer).
@@ -317,7 +317,10 @@ class OffloadScheduler:
         head -- set on the context around lm_head and the sampler, cleared behind them (lia_ctx_set_token_mask).
         logprobs (ops.LogprobRequest): the head also leaves, per row, the log-probability of the id it returns (the argmax, or the
         sampler's draw) and the request's n_top alternatives in the request's device tensors [B] / [B, n_top] -- the sink is set
-        around lm_head and the sampler only (lia_ctx_set_logprob_sink)."""
+        around lm_head and the sampler only (lia_ctx_set_logprob_sink).
+        penalties (penalties.Penalties): the head picks its ids from the logits penalised under the generation's count table -- the
+        queued counts run and the table is set on the context in front of lm_head, cleared behind the sampler
+        (lia_ctx_set_penalties); the returned logits stay raw."""
         s = self._validate(input_ids, kv_state, prefill_policy, decoding_policy, no_overlap, gpu_percentage, num_minibatch, append_policy)
         self._place(s, kv_state, pin_weight, enable_cxl, max_new_tokens, cpu_layers, cpu_layers_start)
         m, sh, ctx = self.model, self.model.shape, self.ctx
@@ -339,6 +342,8 @@ class OffloadScheduler:
         if logprobs is not None:
             ctx.set_logprob_sink(logprobs, (s.B,))
         try:
+            if penalties is not None:
+                penalties.bind(ctx)
             logits, nxt = ctx.lm_head(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, sh.ln_eps, suppress_token)
             if sampler is not None:
                 nxt = sampler(ctx, logits, suppress_token)
@@ -347,6 +352,8 @@ class OffloadScheduler:
                 ctx.set_token_mask(None)
             if logprobs is not None:
                 ctx.set_logprob_sink(None)
+            if penalties is not None:
+                ctx.set_penalties(None)
         self._deliver(s, kv_state)
         return logits, nxt
 
@@ -510,6 +517,16 @@ class OffloadScheduler:
             raise ValueError("set_token_mask takes None only: a table is passed per call, forward(token_mask=) / verify(token_mask=)")
         if self.ctx is not None:
             self.ctx.set_token_mask(None)
+
+    supports_penalties = True         # forward(penalties=): generate()'s repetition / presence / frequency penalties
+
+    def set_penalties(self, table):
+        """None only (generate() when a penalised generation ends, also after an exception): no count table on the library context.
+        forward(penalties=) sets one itself, around its head call."""
+        if table is not None:
+            raise ValueError("set_penalties takes None only: the table is passed per call, forward(penalties=)")
+        if self.ctx is not None:
+            self.ctx.set_penalties(None)
 
     # -- left-padded batches (generation.generate(..., attention_mask=)) -----------------------------------------------------
     def set_key_starts(self, starts):
