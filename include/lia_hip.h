@@ -240,7 +240,9 @@ int lia_embed_ragged(const int64_t* ids, const lia_bf16* tok, const lia_bf16* po
 int lia_ctx_set_token_mask(lia_ctx* ctx, const int32_t* mask_device, long ldm_words, int rows);
 /* final LN on the last position + tied lm_head + greedy argmax: modeling_opt.py:1563, models.py:424-431,
  * greedy_search.py:367,395.  logits [B,vocab], next_ids [B] (device).  suppress_token >= 0: that token's score
- * counts as -inf (EOS while min_new_tokens is unmet, run_generation.py:173,179-182); -1: none. */
+ * counts as -inf (EOS while min_new_tokens is unmet, run_generation.py:173,179-182); -1: none.  Any B >= 1: rows are independent and
+ * go through in chunks of 256 (the workspace need is that of min(B, 256) rows); row i reads row i of a token mask, a log-probability
+ * sink and the penalties' tables, whichever chunk it falls into, and those are checked against the whole B before anything is launched. */
 int lia_lm_head(lia_ctx* ctx, const lia_bf16* hidden, int B, int T, int H, const lia_bf16* lnw, const lia_bf16* lnb,
                 const lia_bf16* emb, int vocab, float eps, int suppress_token, lia_bf16* logits, int64_t* next_ids,
                 void* stream);
@@ -476,6 +478,7 @@ int lia_llama_layer_forward_last(lia_ctx* ctx, const lia_llama_desc* d, const vo
                                  lia_bf16* y_last, lia_kv* kv, const lia_bf16* cos_table, const lia_bf16* sin_table, int B, int T,
                                  int pos0, int b0, void* stream);
 int lia_llama_embed(const int64_t* ids, const lia_bf16* tok, lia_bf16* y, int B, int T, int H, void* stream);
+/* lia_lm_head with the final RMSNorm and the untied lm_head of a Llama: any B >= 1, as there */
 int lia_llama_lm_head(lia_ctx* ctx, const lia_bf16* hidden, int B, int T, int H, const lia_bf16* normw, const lia_bf16* lm,
                       int vocab, float eps, int suppress_token, lia_bf16* logits, int64_t* next_ids, void* stream);
 

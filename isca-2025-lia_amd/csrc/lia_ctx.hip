@@ -202,19 +202,17 @@ extern "C" int lia_ctx_set_row_lens(lia_ctx* c, const int32_t* lens, int n_rows)
 // and unchanged until the compute stream has passed the head call that reads it)
 extern "C" int lia_ctx_set_token_mask(lia_ctx* c, const int32_t* mask_device, long ldm_words, int rows) {
   if (!c) return LIA_ERR_INVALID;
-  if (!mask_device || rows == 0) { c->token_mask = nullptr; c->token_mask_ld = 0; c->token_mask_rows = 0; return LIA_OK; }
+  if (!mask_device || rows == 0) { c->mods.mask = LiaTokenMask{}; return LIA_OK; }
   if (rows < 0 || ldm_words < 0) { lia_set_error("lia_ctx_set_token_mask: rows=%d ldm=%ld must be >= 0", rows, ldm_words); return LIA_ERR_INVALID; }
   if ((uintptr_t)mask_device & 3) { lia_set_error("lia_ctx_set_token_mask: mask=%p is not 4-byte aligned", (const void*)mask_device); return LIA_ERR_INVALID; }
-  c->token_mask = (const uint32_t*)mask_device;
-  c->token_mask_ld = ldm_words;
-  c->token_mask_rows = rows;
+  c->mods.mask = LiaTokenMask{(const uint32_t*)mask_device, ldm_words, rows};
   return LIA_OK;
 }
 
 // the log-probability sink of the head calls: the pointers only, as the token mask -- nothing is copied, nothing waits
 extern "C" int lia_ctx_set_logprob_sink(lia_ctx* c, int n_top, float* chosen, int64_t* top_ids, float* top_logprobs, long rows) {
   if (!c) return LIA_ERR_INVALID;
-  if (!chosen) { c->lp_chosen = nullptr; c->lp_top_ids = nullptr; c->lp_top = nullptr; c->lp_n_top = 0; c->lp_rows = 0; return LIA_OK; }
+  if (!chosen) { c->mods.sink = LiaSink{}; return LIA_OK; }
   if (n_top < 0 || n_top > LIA_LOGPROB_MAX_TOP) {
     lia_set_error("lia_ctx_set_logprob_sink: n_top=%d must be in [0, %d]", n_top, LIA_LOGPROB_MAX_TOP);
     return LIA_ERR_INVALID;
@@ -224,11 +222,7 @@ extern "C" int lia_ctx_set_logprob_sink(lia_ctx* c, int n_top, float* chosen, in
     lia_set_error("lia_ctx_set_logprob_sink: NULL %s with n_top=%d (NULL only with n_top = 0)", !top_ids ? "top_ids" : "top_logprobs", n_top);
     return LIA_ERR_INVALID;
   }
-  c->lp_chosen = chosen;
-  c->lp_top_ids = top_ids;
-  c->lp_top = top_logprobs;
-  c->lp_n_top = n_top;
-  c->lp_rows = rows;
+  c->mods.sink = LiaSink{chosen, top_ids, top_logprobs, n_top, rows};
   return LIA_OK;
 }
 
@@ -238,22 +232,12 @@ extern "C" int lia_ctx_set_logprob_sink(lia_ctx* c, int n_top, float* chosen, in
 extern "C" int lia_ctx_set_penalties(lia_ctx* c, const uint16_t* counts, long ldc, int rows, float repetition, float presence,
                                      float frequency, lia_bf16* scratch, long lds) {
   if (!c) return LIA_ERR_INVALID;
-  if (!counts) {
-    c->pen_counts = nullptr; c->pen_scratch = nullptr; c->pen_ldc = c->pen_lds = 0; c->pen_rows = 0;
-    return LIA_OK;
-  }
+  if (!counts) { c->mods.penalties = LiaPenalties{}; return LIA_OK; }
   if (penalty_args_invalid("lia_ctx_set_penalties", repetition, presence, frequency, counts, ldc, -1)) return LIA_ERR_INVALID;
   if (rows <= 0) { lia_set_error("lia_ctx_set_penalties: rows=%d must be >= 1", rows); return LIA_ERR_INVALID; }
   if (!scratch) { lia_set_error("lia_ctx_set_penalties: NULL scratch with a count table (rows x lds bf16 values, the caller's)"); return LIA_ERR_INVALID; }
   if (lds <= 0) { lia_set_error("lia_ctx_set_penalties: lds=%ld must be >= the vocabulary", lds); return LIA_ERR_INVALID; }
-  c->pen_counts = counts;
-  c->pen_ldc = ldc;
-  c->pen_rows = rows;
-  c->pen_theta = repetition;
-  c->pen_presence = presence;
-  c->pen_frequency = frequency;
-  c->pen_scratch = (bf16_t*)scratch;
-  c->pen_lds = lds;
+  c->mods.penalties = LiaPenalties{counts, ldc, rows, repetition, presence, frequency, (bf16_t*)scratch, lds};
   return LIA_OK;
 }
 

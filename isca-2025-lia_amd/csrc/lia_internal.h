@@ -167,6 +167,32 @@ LIA_HIDDEN int lia_attn_dispatch(const bf16_t* q, long ldq, const bf16_t* kc, co
                                  int pos0, int heads, int kv_heads, int d, int Bc, int b0, int post_scale, const int* starts, int tail,
                                  hipStream_t st, LiaAttnOpts* opts = nullptr);
 
+// ---- head modifiers: ambient state of the context that every head call (lm_head, sample, lm_score, lm_verify*) looks at.  Each is
+// the CALLER's device memory -- only pointers are kept -- and row i of a call uses row i of each.  A NULL first member: not set, and
+// a head launches what it launched without it.  lia_ctx_set_token_mask / _logprob_sink / _penalties (lia_ctx.hip) fill them;
+// head_mods_resolve (lia_ops.hip) is the one place a head reads them.
+struct LiaTokenMask {          // the MASKED kernel instantiations in place of the plain ones
+  const uint32_t* table;
+  long ld;                     // words between rows; 0: one row for every row
+  int rows;
+};
+struct LiaSink {               // lia_topn_logprobs_kernel behind the head's own id kernel
+  float* chosen;
+  int64_t* top_ids;
+  float* top;
+  int n_top;
+  long rows;
+};
+struct LiaPenalties {          // lm_head and sample: lia_penalty_kernel from their logits into the scratch, their id kernel on the scratch
+  const uint16_t* counts;
+  long ldc;
+  int rows;
+  float theta, presence, frequency;
+  bf16_t* scratch;
+  long lds;
+};
+struct LiaHeadMods { LiaTokenMask mask; LiaSink sink; LiaPenalties penalties; };
+
 // ---- context (lia_ctx.hip)
 struct lia_ctx {
   int device;
@@ -226,27 +252,7 @@ struct lia_ctx {
   int* row_lens_dev;
   int row_lens_cap;
   int row_lens_n;             // 0: no table
-  // allowed-token masks (lia_ctx_set_token_mask): the CALLER's device table -- only the pointer is kept.  While it is set the head
-  // calls (lm_head, sample, lm_verify*) take the MASKED kernel instantiations and row i of a call reads table row i
-  const uint32_t* token_mask;  // NULL: no table -- every head call is the unmasked one
-  long token_mask_ld;          // words between rows; 0: one row for every row
-  int token_mask_rows;
-  // log-probability sink (lia_ctx_set_logprob_sink): the CALLER's device arrays -- only the pointers are kept.  While it is set the head
-  // calls run lia_topn_logprobs_kernel behind their own id kernel and row i of a call writes sink row i
-  float* lp_chosen;            // NULL: no sink -- every head call launches what it launched without one
-  int64_t* lp_top_ids;
-  float* lp_top;
-  int lp_n_top;
-  long lp_rows;
-  // penalties (lia_ctx_set_penalties): the CALLER's count table and scratch -- only the pointers are kept.  While it is set lm_head and
-  // sample run lia_penalty_kernel from their logits into the scratch and their id kernel on the scratch; row i of a call reads table
-  // row i and writes scratch row i
-  const uint16_t* pen_counts;  // NULL: no table -- every head call launches what it launched without one
-  long pen_ldc;
-  int pen_rows;
-  float pen_theta, pen_presence, pen_frequency;
-  bf16_t* pen_scratch;
-  long pen_lds;
+  LiaHeadMods mods;           // what the head calls also look at: token mask, log-probability sink, penalties (above)
 };
 
 // the workspace is about to be reused: a norm the previous layer call chained into it is gone, and so is a pending hint

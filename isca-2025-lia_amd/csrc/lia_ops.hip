@@ -167,64 +167,92 @@ extern "C" int lia_attention_padded(const lia_bf16* q, long ldq, const lia_bf16*
   return LIA_OK;
 }
 
-// The allowed-token table of a head call on `rows` rows (lia_ctx_set_token_mask), checked against the call: LIA_OK with *mask = NULL
-// (no table: the unmasked launches) or the table and its pitch; the refusals by name.  The one place that words them.
-static int token_mask_of(const char* who, const lia_ctx* ctx, long rows, int vocab, const uint32_t** mask, long* ldm) {
-  *mask = nullptr;
-  *ldm = 0;
-  if (!ctx->token_mask) return LIA_OK;
-  const long W = ((long)vocab + 31) / 32;
-  if (ctx->token_mask_ld != 0 && ctx->token_mask_ld < W) {
-    lia_set_error("%s: the token mask has ldm=%ld words per row, vocab=%d needs ceil(vocab / 32) = %ld (or 0: one row for every row)", who,
-                  ctx->token_mask_ld, vocab, W);
-    return LIA_ERR_INVALID;
-  }
-  if (ctx->token_mask_ld != 0 && rows > ctx->token_mask_rows) {
-    lia_set_error("%s: the call has %ld rows, the token mask table %d (lia_ctx_set_token_mask)", who, rows, ctx->token_mask_rows);
-    return LIA_ERR_INVALID;
-  }
-  *mask = ctx->token_mask;
-  *ldm = ctx->token_mask_ld;
-  return LIA_OK;
+// ------------------------------------------------------------------------------------------------
+// head modifiers (LiaHeadMods, lia_internal.h): the one path by which a head call sees the token mask, the log-probability sink and
+// the penalties of its context
+// ------------------------------------------------------------------------------------------------
+// What a head does with each modifier WHEN IT IS SET: NULL -- takes it; a reason -- refuses the call, by name, with that reason;
+// LIA_MOD_UNSEEN -- never looks at it.
+struct LiaHeadTakes { const char *mask, *sink, *penalties; };
+#define LIA_MOD_UNSEEN ""
+#define LIA_NO_BLOCK_PENALTIES "every block position would need its own counts -- penalties are not applied under speculation"
+
+static bool head_mod_refused(const char* who, bool set, const char* why, const char* what) {
+  if (!set || !why || !*why) return false;
+  lia_set_error("%s: %s: %s", who, what, why);
+  return true;
 }
 
-// The log-probability sink of a head call on `rows` rows (lia_ctx_set_logprob_sink), checked against the call: LIA_OK with
-// sk->chosen = NULL (no sink: nothing more is launched) or the sink; the refusals by name.  The one place that words them.
-struct LiaSink { float* chosen; int64_t* top_ids; float* top; int n_top; };
-static int logprob_sink_of(const char* who, const lia_ctx* ctx, long rows, int vocab, LiaSink* sk) {
-  memset(sk, 0, sizeof(*sk));
-  if (!ctx->lp_chosen) return LIA_OK;
-  if (ctx->lp_n_top > vocab) {
-    lia_set_error("%s: the log-probability sink asks for n_top=%d alternatives, vocab=%d has fewer (lia_ctx_set_logprob_sink)", who,
-                  ctx->lp_n_top, vocab);
-    return LIA_ERR_INVALID;
+// The modifiers of a head call on `rows` rows of `vocab` logits, checked against the call: *out holds what the head takes (a NULL
+// first member: not set -- the launches without it); LIA_ERR_INVALID with the fault by name otherwise.  The one place that words
+// these faults and orders them: what the head does not take (sink, penalties, mask), then the head's own arguments (args_invalid:
+// true = refused, the error is set), then the fit of what it takes (mask, sink, penalties).  Nothing is launched before it returns.
+template <typename ArgsInvalid>
+static int head_mods_resolve(const char* who, const lia_ctx* ctx, const LiaHeadTakes& no, long rows, int vocab, LiaHeadMods* out,
+                             ArgsInvalid args_invalid) {
+  const LiaTokenMask& mk = ctx->mods.mask;
+  const LiaSink& sk = ctx->mods.sink;
+  const LiaPenalties& pn = ctx->mods.penalties;
+  if (head_mod_refused(who, sk.chosen, no.sink, "a log-probability sink is set (lia_ctx_set_logprob_sink)")) return LIA_ERR_INVALID;
+  if (head_mod_refused(who, pn.counts, no.penalties, "penalties are set (lia_ctx_set_penalties)")) return LIA_ERR_INVALID;
+  if (head_mod_refused(who, mk.table, no.mask, "a token mask is set (lia_ctx_set_token_mask)")) return LIA_ERR_INVALID;
+  if (args_invalid()) return LIA_ERR_INVALID;
+  *out = LiaHeadMods{};
+  if (mk.table && !no.mask) {
+    const long W = ((long)vocab + 31) / 32;
+    if (mk.ld != 0 && mk.ld < W) {
+      lia_set_error("%s: the token mask has ldm=%ld words per row, vocab=%d needs ceil(vocab / 32) = %ld (or 0: one row for every row)", who,
+                    mk.ld, vocab, W);
+      return LIA_ERR_INVALID;
+    }
+    if (mk.ld != 0 && rows > mk.rows) {
+      lia_set_error("%s: the call has %ld rows, the token mask table %d (lia_ctx_set_token_mask)", who, rows, mk.rows);
+      return LIA_ERR_INVALID;
+    }
+    out->mask = mk;
   }
-  if (rows > ctx->lp_rows) {
-    lia_set_error("%s: the call has %ld rows, the log-probability sink %ld (lia_ctx_set_logprob_sink)", who, rows, ctx->lp_rows);
-    return LIA_ERR_INVALID;
+  if (sk.chosen && !no.sink) {
+    if (sk.n_top > vocab) {
+      lia_set_error("%s: the log-probability sink asks for n_top=%d alternatives, vocab=%d has fewer (lia_ctx_set_logprob_sink)", who,
+                    sk.n_top, vocab);
+      return LIA_ERR_INVALID;
+    }
+    if (rows > sk.rows) {
+      lia_set_error("%s: the call has %ld rows, the log-probability sink %ld (lia_ctx_set_logprob_sink)", who, rows, sk.rows);
+      return LIA_ERR_INVALID;
+    }
+    out->sink = sk;
   }
-  sk->chosen = ctx->lp_chosen;
-  sk->top_ids = ctx->lp_top_ids;
-  sk->top = ctx->lp_top;
-  sk->n_top = ctx->lp_n_top;
+  if (pn.counts && !no.penalties) {
+    if (pn.ldc < vocab) { lia_set_error("%s: the count table has ldc=%ld words per row, vocab=%d (lia_ctx_set_penalties)", who, pn.ldc, vocab); return LIA_ERR_INVALID; }
+    if (pn.lds < vocab) { lia_set_error("%s: the penalty scratch has lds=%ld values per row, vocab=%d (lia_ctx_set_penalties)", who, pn.lds, vocab); return LIA_ERR_INVALID; }
+    if (rows > pn.rows) { lia_set_error("%s: the call has %ld rows, the count table %d (lia_ctx_set_penalties)", who, rows, pn.rows); return LIA_ERR_INVALID; }
+    out->penalties = pn;
+  }
   return LIA_OK;
 }
+// ... for a head whose own arguments were checked in front of it
+static int head_mods_resolve(const char* who, const lia_ctx* ctx, const LiaHeadTakes& no, long rows, int vocab, LiaHeadMods* out) {
+  return head_mods_resolve(who, ctx, no, rows, vocab, out, [] { return false; });
+}
+// the mask and the penalties as a call on rows r0 .. sees them: each table from its row r0 on (the sink: sink_write takes r0)
+static LiaHeadMods head_mods_at_row(LiaHeadMods m, long r0) {
+  if (m.mask.table) m.mask.table += r0 * m.mask.ld;
+  if (m.penalties.counts) { m.penalties.counts += r0 * m.penalties.ldc; m.penalties.scratch += r0 * m.penalties.lds; }
+  return m;
+}
+
 // rows r0 .. r0 + n - 1 of the sink from the n logits rows in hand and the ids their head just wrote (ids: that of row r0)
 static void sink_write(const LiaSink& sk, const bf16_t* logits, long ld, int n, int vocab, const int64_t* ids, long r0, hipStream_t st) {
   if (!sk.chosen) return;
   lia_topn_logprobs_launch(logits, ld, n, vocab, ids, sk.n_top, sk.chosen + r0, sk.n_top ? sk.top_ids + r0 * sk.n_top : nullptr,
                            sk.n_top ? sk.top + r0 * sk.n_top : nullptr, st);
 }
-// the heads that take no sink
-static bool logprob_sink_refused(const char* who, const lia_ctx* ctx, const char* why) {
-  if (!ctx->lp_chosen) return false;
-  lia_set_error("%s: a log-probability sink is set (lia_ctx_set_logprob_sink): %s", who, why);
-  return true;
+// scratch rows 0 .. n - 1 = the n logits rows in hand, penalised under table rows 0 .. n - 1
+static void penalties_write(const LiaPenalties& pn, const bf16_t* logits, long ld, int n, int vocab, hipStream_t st) {
+  lia_penalty_launch(logits, ld, n, vocab, pn.counts, pn.ldc, pn.theta, pn.presence, pn.frequency, pn.scratch, pn.lds, st);
 }
-
-// The penalties of a head call on `rows` rows (lia_ctx_set_penalties), checked against the call: LIA_OK with pn->counts = NULL (no
-// table: nothing more is launched) or the table, the settings and the scratch; the refusals by name.  The one place that words them.
-struct LiaPenalties { const uint16_t* counts; long ldc; float theta, presence, frequency; bf16_t* scratch; long lds; };
+// the penalty settings and a count table, worded once for the three entry points (lia_internal.h)
 bool penalty_args_invalid(const char* who, float repetition, float presence, float frequency, const void* counts, long ldc, int vocab) {
   if (!std::isfinite(repetition) || !(repetition > 0.f)) { lia_set_error("%s: repetition=%g must be finite and > 0 (1: off)", who, (double)repetition); return true; }
   if (!std::isfinite(presence)) { lia_set_error("%s: presence=%g must be finite (0: off)", who, (double)presence); return true; }
@@ -234,71 +262,61 @@ bool penalty_args_invalid(const char* who, float repetition, float presence, flo
   if (vocab >= 0 && ldc < vocab) { lia_set_error("%s: ldc=%ld < vocab=%d", who, ldc, vocab); return true; }
   return false;
 }
-static int penalties_of(const char* who, const lia_ctx* ctx, long rows, int vocab, LiaPenalties* pn) {
-  memset(pn, 0, sizeof(*pn));
-  if (!ctx->pen_counts) return LIA_OK;
-  if (ctx->pen_ldc < vocab) { lia_set_error("%s: the count table has ldc=%ld words per row, vocab=%d (lia_ctx_set_penalties)", who, ctx->pen_ldc, vocab); return LIA_ERR_INVALID; }
-  if (ctx->pen_lds < vocab) { lia_set_error("%s: the penalty scratch has lds=%ld values per row, vocab=%d (lia_ctx_set_penalties)", who, ctx->pen_lds, vocab); return LIA_ERR_INVALID; }
-  if (rows > ctx->pen_rows) { lia_set_error("%s: the call has %ld rows, the count table %d (lia_ctx_set_penalties)", who, rows, ctx->pen_rows); return LIA_ERR_INVALID; }
-  *pn = LiaPenalties{ctx->pen_counts, ctx->pen_ldc, ctx->pen_theta, ctx->pen_presence, ctx->pen_frequency, ctx->pen_scratch, ctx->pen_lds};
-  return LIA_OK;
-}
-// scratch rows 0 .. n - 1 = the n logits rows in hand, penalised under table rows 0 .. n - 1
-static void penalties_write(const LiaPenalties& pn, const bf16_t* logits, long ld, int n, int vocab, hipStream_t st) {
-  lia_penalty_launch(logits, ld, n, vocab, pn.counts, pn.ldc, pn.theta, pn.presence, pn.frequency, pn.scratch, pn.lds, st);
-}
-// the heads that take no penalties
-static bool penalties_refused(const char* who, const lia_ctx* ctx, const char* why) {
-  if (!ctx->pen_counts) return false;
-  lia_set_error("%s: penalties are set (lia_ctx_set_penalties): %s", who, why);
-  return true;
-}
-#define LIA_NO_BLOCK_PENALTIES "every block position would need its own counts -- penalties are not applied under speculation"
 
-// norm_b == nullptr: RMSNorm (Llama), else LayerNorm
+// Where a row of a verify block stands: block rows r0 .. of T positions each, `suppress` counting as -inf at positions < n_suppress
+// (n_suppress_rows, device int32 [B] or NULL: one bound per row in its place).  NULL in the pick helpers: plain rows, as lm_head's.
+struct LiaBlockPos { int n_suppress; const int* n_suppress_rows; int T, r0; };
+
+// The greedy id of n logits rows `ld` apart, under the call's mask.  Plain rows `vocab` apart: the head's own argmax kernel (what
+// penalties.py allocates for the penalised rows; 9.0 against 12.4 us at B 64 x 50272); plain rows at another pitch (a pitched penalty
+// scratch): the verify heads' argmax launch, which takes a pitch -- the same scan and tie rule; T = 1, n_suppress = 1: `suppress`
+// holds for every row, and block row i reads mask row i.  A verify block: that launch.
+static void pick_argmax(const LiaTokenMask& mk, const bf16_t* logits, long ld, int n, int vocab, int suppress, const LiaBlockPos* blk,
+                        int64_t* ids, hipStream_t st) {
+  static const LiaBlockPos every_row{1, nullptr, 1, 0};
+  if (!blk && ld == vocab) {
+    if (mk.table) lia_argmax_masked_launch(logits, ids, n, vocab, suppress, mk.table, mk.ld, st);
+    else lia_argmax_launch(logits, ids, n, vocab, suppress, st);
+    return;
+  }
+  if (!blk) blk = &every_row;
+  if (mk.table) lia_verify_argmax_masked_launch(logits, ld, n, vocab, suppress, blk->n_suppress, blk->n_suppress_rows, blk->T, blk->r0, ids, mk.table, mk.ld, st);
+  else lia_verify_argmax_rows_launch(logits, ld, n, vocab, suppress, blk->n_suppress, blk->n_suppress_rows, blk->T, blk->r0, ids, st);
+}
+
+// norm_b == nullptr: RMSNorm (Llama), else LayerNorm.  Any B >= 1: the rows go through in chunks of LIA_HEAD_CHUNK -- rows are
+// independent, so the results are those of one call -- and chunk b0 uses row b0 .. of the logits, the ids and every modifier.
+#define LIA_HEAD_CHUNK 256    // the skinny GEMM regime's M (split-K slabs in the workspace)
 static int lm_head_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, int B, int T, int H, const bf16_t* norm_w, const bf16_t* norm_b,
                         const bf16_t* emb, int vocab, float eps, int suppress_token, bf16_t* logits, int64_t* next_ids, hipStream_t st) {
-  size_t scratch = align_up((size_t)B * H * 2, 256);
-  size_t gemm_need = (size_t)8 * B * vocab * 4;
-  const uint32_t* mask;
-  long ldm;
-  if (int mrc = token_mask_of(who, ctx, B, vocab, &mask, &ldm)) return mrc;
-  LiaSink sk;
-  if (int src = logprob_sink_of(who, ctx, B, vocab, &sk)) return src;
-  LiaPenalties pn;
-  if (int prc = penalties_of(who, ctx, B, vocab, &pn)) return prc;
-  if (ctx->ws_bytes < scratch) { lia_set_error("%s: workspace too small", who); return LIA_ERR_MEMORY; }
+  LiaHeadMods all;
+  if (int rc = head_mods_resolve(who, ctx, LiaHeadTakes{}, B, vocab, &all)) return rc;
+  if (ctx->ws_bytes < align_up((size_t)std::min(B, LIA_HEAD_CHUNK) * H * 2, 256)) { lia_set_error("%s: workspace too small", who); return LIA_ERR_MEMORY; }
   ws_invalidate(ctx);
   bf16_t* lno = (bf16_t*)ctx->ws;
-  // hidden[:, -1, :] -> final LN (lia/modeling_opt.py:1563 applies it to all positions; only the last one feeds
-  // lm_head, models.py:424-431, and LN is row-wise, so the other rows are never needed)
-  if (norm_b) lia_layernorm_launch(hidden + (long)(T - 1) * H, (long)T * H, norm_w, norm_b, lno, H, B, H, eps, st);
-  else lia_rmsnorm_launch(hidden + (long)(T - 1) * H, (long)T * H, norm_w, lno, H, B, H, eps, st);
-  LiaEpilogue ep{nullptr, nullptr, 0, 0};
-  LiaOutMap om = plain_out(logits, vocab, vocab);
-  size_t have = ctx->ws_bytes - scratch;
-  int rc = gemm_checked(ctx, lno, H, emb, B, vocab, H, ep, om, (float*)(ctx->ws + scratch), std::min(have, gemm_need), 0, st);
-  if (rc) return rc;
-  if (pn.counts) {
-    // the argmax of the penalised rows: the head's own kernel where the scratch rows are vocab apart (what penalties.py allocates;
-    // 9.0 against 12.4 us at B 64 x 50272), else the verify heads' argmax launch, which takes a pitch (the same scan and tie rule;
-    // T = 1, n_suppress = 1: `suppress` holds for every row, and block row i reads mask row i)
-    penalties_write(pn, logits, vocab, B, vocab, st);
-    if (pn.lds == vocab) {
-      if (mask) lia_argmax_masked_launch(pn.scratch, next_ids, B, vocab, suppress_token, mask, ldm, st);
-      else lia_argmax_launch(pn.scratch, next_ids, B, vocab, suppress_token, st);
-    } else if (mask) {
-      lia_verify_argmax_masked_launch(pn.scratch, pn.lds, B, vocab, suppress_token, 1, nullptr, 1, 0, next_ids, mask, ldm, st);
+  const LiaEpilogue ep{nullptr, nullptr, 0, 0};
+  for (int b0 = 0; b0 < B; b0 += LIA_HEAD_CHUNK) {
+    const int n = std::min(LIA_HEAD_CHUNK, B - b0);
+    const size_t scratch = align_up((size_t)n * H * 2, 256);
+    const size_t gemm_need = (size_t)8 * n * vocab * 4;
+    const LiaHeadMods m = head_mods_at_row(all, b0);
+    const bf16_t* x = hidden + (long)b0 * T * H;
+    bf16_t* lg = logits + (long)b0 * vocab;
+    // hidden[:, -1, :] -> final LN (lia/modeling_opt.py:1563 applies it to all positions; only the last one feeds
+    // lm_head, models.py:424-431, and LN is row-wise, so the other rows are never needed)
+    if (norm_b) lia_layernorm_launch(x + (long)(T - 1) * H, (long)T * H, norm_w, norm_b, lno, H, n, H, eps, st);
+    else lia_rmsnorm_launch(x + (long)(T - 1) * H, (long)T * H, norm_w, lno, H, n, H, eps, st);
+    const LiaOutMap om = plain_out(lg, vocab, vocab);
+    if (int rc = gemm_checked(ctx, lno, H, emb, n, vocab, H, ep, om, (float*)(ctx->ws + scratch), std::min(ctx->ws_bytes - scratch, gemm_need), 0, st)) return rc;
+    if (m.penalties.counts) {
+      penalties_write(m.penalties, lg, vocab, n, vocab, st);
+      pick_argmax(m.mask, m.penalties.scratch, m.penalties.lds, n, vocab, suppress_token, nullptr, next_ids + b0, st);
     } else {
-      lia_verify_argmax_rows_launch(pn.scratch, pn.lds, B, vocab, suppress_token, 1, nullptr, 1, 0, next_ids, st);
+      pick_argmax(m.mask, lg, vocab, n, vocab, suppress_token, nullptr, next_ids + b0, st);
     }
-  } else if (mask) {
-    lia_argmax_masked_launch(logits, next_ids, B, vocab, suppress_token, mask, ldm, st);
-  } else {
-    lia_argmax_launch(logits, next_ids, B, vocab, suppress_token, st);
+    sink_write(m.sink, lg, vocab, n, vocab, next_ids + b0, b0, st);
+    HIP_TRY(hipGetLastError());
   }
-  sink_write(sk, logits, vocab, B, vocab, next_ids, 0, st);
-  HIP_TRY(hipGetLastError());
   return LIA_OK;
 }
 
@@ -307,7 +325,7 @@ extern "C" int lia_lm_head(lia_ctx* ctx, const lia_bf16* hidden, int B, int T, i
                            lia_bf16* logits, int64_t* next_ids, void* stream) {
   if (!ctx) return LIA_ERR_INVALID;
   if (!hidden || !lnw || !lnb || !emb || !logits || !next_ids) { lia_set_error("lia_lm_head: NULL tensor"); return LIA_ERR_MISSING; }
-  if (B <= 0 || B > 256 || T <= 0 || vocab % 16) { lia_set_error("lia_lm_head: B=%d (<=256) T=%d vocab=%d (%%16)", B, T, vocab); return LIA_ERR_INVALID; }
+  if (B <= 0 || T <= 0 || vocab % 16) { lia_set_error("lia_lm_head: B=%d T=%d vocab=%d (%%16)", B, T, vocab); return LIA_ERR_INVALID; }
   return lm_head_impl("lia_lm_head", ctx, hidden, B, T, H, lnw, lnb, emb, vocab, eps, suppress_token, logits, next_ids, (hipStream_t)stream);
 }
 
@@ -315,7 +333,7 @@ extern "C" int lia_llama_lm_head(lia_ctx* ctx, const lia_bf16* hidden, int B, in
                                  int vocab, float eps, int suppress_token, lia_bf16* logits, int64_t* next_ids, void* stream) {
   if (!ctx) return LIA_ERR_INVALID;
   if (!hidden || !normw || !lm || !logits || !next_ids) { lia_set_error("lia_llama_lm_head: NULL tensor"); return LIA_ERR_MISSING; }
-  if (B <= 0 || B > 256 || T <= 0 || vocab % 16) { lia_set_error("lia_llama_lm_head: B=%d T=%d vocab=%d", B, T, vocab); return LIA_ERR_INVALID; }
+  if (B <= 0 || T <= 0 || vocab % 16) { lia_set_error("lia_llama_lm_head: B=%d T=%d vocab=%d", B, T, vocab); return LIA_ERR_INVALID; }
   return lm_head_impl("lia_llama_lm_head", ctx, hidden, B, T, H, normw, nullptr, lm, vocab, eps, suppress_token, logits, next_ids, (hipStream_t)stream);
 }
 
@@ -327,6 +345,29 @@ static bool sample_settings_invalid(const char* who, float temperature, int top_
   if (top_k < 0) { lia_set_error("%s: top_k=%d must be >= 0 (0: off)", who, top_k); return true; }
   if (!(top_p > 0.f && top_p <= 1.f)) { lia_set_error("%s: top_p=%g must be in (0, 1] (1: off)", who, (double)top_p); return true; }
   return false;
+}
+
+// A draw's settings and, for a verify block, where its uniforms come from: position t of block row b draws with
+// uniforms[(step0 + t) * ldu + b] of an n_steps-row table (step_rows, device int32 [B] or NULL: a step origin per row)
+struct LiaDraw { float tau; int top_k; float top_p; const float* uniforms; };
+struct LiaBlockDraw { LiaBlockPos pos; long ldu; int n_steps, step0; const int* step_rows; const int64_t* block_ids; };
+
+// The drawn id of n logits rows `ld` apart, under the call's mask.  Plain rows (blk == NULL): lia_sample's kernel, aux = stats or
+// NULL; a verify block: the block draw, aux = p_draft or NULL.
+static void pick_draw(const LiaTokenMask& mk, const bf16_t* logits, long ld, int n, int vocab, const LiaDraw& d, int suppress,
+                      const LiaBlockDraw* blk, int64_t* ids, float* aux, hipStream_t st) {
+  if (!blk) {
+    if (mk.table) lia_sample_masked_launch(logits, ld, n, vocab, d.tau, d.top_k, d.top_p, suppress, d.uniforms, ids, aux, mk.table, mk.ld, st);
+    else lia_sample_launch(logits, ld, n, vocab, d.tau, d.top_k, d.top_p, suppress, d.uniforms, ids, aux, st);
+    return;
+  }
+  const LiaBlockPos& p = blk->pos;
+  if (mk.table)
+    lia_verify_sample_masked_launch(logits, ld, n, vocab, d.tau, d.top_k, d.top_p, suppress, p.n_suppress, p.n_suppress_rows, p.T, p.r0, d.uniforms,
+                                    blk->ldu, blk->n_steps, blk->step0, blk->step_rows, blk->block_ids, ids, aux, mk.table, mk.ld, st);
+  else
+    lia_verify_sample_launch(logits, ld, n, vocab, d.tau, d.top_k, d.top_p, suppress, p.n_suppress, p.n_suppress_rows, p.T, p.r0, d.uniforms,
+                             blk->ldu, blk->n_steps, blk->step0, blk->step_rows, blk->block_ids, ids, aux, st);
 }
 
 extern "C" int lia_sample(lia_ctx* ctx, const lia_bf16* logits, long ld, int B, int vocab, float temperature, int top_k, float top_p,
@@ -341,23 +382,17 @@ extern "C" int lia_sample(lia_ctx* ctx, const lia_bf16* logits, long ld, int B, 
   if (ld < vocab) { lia_set_error("lia_sample: ld=%ld < vocab=%d", ld, vocab); return LIA_ERR_INVALID; }
   if (sample_settings_invalid("lia_sample", temperature, top_k, top_p)) return LIA_ERR_INVALID;
   if (suppress_token < -1 || suppress_token >= vocab) { lia_set_error("lia_sample: suppress_token=%d must be -1 or in [0, vocab)", suppress_token); return LIA_ERR_INVALID; }
-  const uint32_t* mask;
-  long ldm;
-  if (int mrc = token_mask_of("lia_sample", ctx, B, vocab, &mask, &ldm)) return mrc;
-  LiaSink sk;
-  if (int src = logprob_sink_of("lia_sample", ctx, B, vocab, &sk)) return src;
-  LiaPenalties pn;
-  if (int prc = penalties_of("lia_sample", ctx, B, vocab, &pn)) return prc;
-  const bf16_t* raw = logits;                      // (the sink reads the model's own distribution)
-  const long raw_ld = ld;
-  if (pn.counts) {
-    penalties_write(pn, logits, ld, B, vocab, (hipStream_t)stream);
-    logits = pn.scratch;
-    ld = pn.lds;
+  LiaHeadMods m;
+  if (int rc = head_mods_resolve("lia_sample", ctx, LiaHeadTakes{}, B, vocab, &m)) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  const LiaDraw draw{temperature, top_k, top_p, uniforms};
+  if (m.penalties.counts) {
+    penalties_write(m.penalties, logits, ld, B, vocab, st);
+    pick_draw(m.mask, m.penalties.scratch, m.penalties.lds, B, vocab, draw, suppress_token, nullptr, next_ids, stats, st);
+  } else {
+    pick_draw(m.mask, logits, ld, B, vocab, draw, suppress_token, nullptr, next_ids, stats, st);
   }
-  if (mask) lia_sample_masked_launch(logits, ld, B, vocab, temperature, top_k, top_p, suppress_token, uniforms, next_ids, stats, mask, ldm, (hipStream_t)stream);
-  else lia_sample_launch(logits, ld, B, vocab, temperature, top_k, top_p, suppress_token, uniforms, next_ids, stats, (hipStream_t)stream);
-  sink_write(sk, raw, raw_ld, B, vocab, next_ids, 0, (hipStream_t)stream);
+  sink_write(m.sink, logits, ld, B, vocab, next_ids, 0, st);      // (the sink reads the model's own distribution)
   HIP_TRY(hipGetLastError());
   return LIA_OK;
 }
@@ -481,8 +516,10 @@ static int lm_rows_chunked(const char* who, lia_ctx* ctx, const bf16_t* hidden, 
 static int lm_score_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int M, int H, const bf16_t* norm_w,
                          const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, const int64_t* targets, float* logprobs,
                          int64_t* greedy_ids, hipStream_t st) {
-  if (logprob_sink_refused(who, ctx, "the score heads report log-probabilities themselves and write no sink")) return LIA_ERR_INVALID;
-  if (penalties_refused(who, ctx, "the score heads report the model's own distribution and emit no token")) return LIA_ERR_INVALID;
+  LiaHeadMods none;
+  if (int mrc = head_mods_resolve(who, ctx, LiaHeadTakes{LIA_MOD_UNSEEN, "the score heads report log-probabilities themselves and write no sink",
+                                                         "the score heads report the model's own distribution and emit no token"}, M, vocab, &none))
+    return mrc;
   const int rc = lm_rows_chunked(who, ctx, hidden, ldh, M, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
     lia_token_logprobs_launch(logits, vocab, n, vocab, targets + r0, logprobs + r0, greedy_ids + r0, st);
   });
@@ -509,28 +546,59 @@ extern "C" int lia_llama_lm_score(lia_ctx* ctx, const lia_bf16* hidden, long ldh
 }
 
 // ------------------------------------------------------------------------------------------------
-// speculative verification: lm_score's chunks (lm_rows_chunked) with a per-row argmax behind them, then the acceptance kernel (lia_score.hip)
+// speculative verification: lm_score's chunks (lm_rows_chunked) with a per-row id kernel behind them, then an acceptance kernel
+// (lia_score.hip).  Three heads: the greedy one (argmax), the sampled one (lia_sample's draw behind every block position,
+// lia_verify_sample_kernel) and the rejection one (the accept test and the residual draw of a stochastic drafter's block,
+// lia_verify_reject_kernel, lia_sample.hip)
 // ------------------------------------------------------------------------------------------------
+// the block's shape and suppression, worded once for the three heads
+static bool block_args_invalid(const char* who, int B, int T, int n_suppress, int suppress_token, int vocab) {
+  if (B <= 0) { lia_set_error("%s: B=%d must be >= 1", who, B); return true; }
+  if (T < 2) { lia_set_error("%s: T=%d must be >= 2 (the pending token and at least one draft token)", who, T); return true; }
+  if ((long)B * T > 0x7fffffffL) { lia_set_error("%s: B=%d x T=%d rows", who, B, T); return true; }
+  if (n_suppress < 0 || n_suppress > T) { lia_set_error("%s: n_suppress=%d must be in [0, T=%d]", who, n_suppress, T); return true; }
+  if (suppress_token < -1 || (vocab > 0 && suppress_token >= vocab)) { lia_set_error("%s: suppress_token=%d must be -1 or in [0, vocab)", who, suppress_token); return true; }
+  return false;
+}
+// a block draw's settings and uniform table, worded once for the sampled and the rejection head
+static bool block_draw_invalid(const char* who, int B, int vocab, float temperature, int top_k, float top_p, long ldu, int n_steps, int step0) {
+  if (vocab > LIA_SAMPLE_MAX_VOCAB) { lia_set_error("%s: vocab=%d must be in [1, %d]", who, vocab, LIA_SAMPLE_MAX_VOCAB); return true; }
+  if (sample_settings_invalid(who, temperature, top_k, top_p)) return true;
+  if (ldu < B) { lia_set_error("%s: ldu=%ld < B=%d", who, ldu, B); return true; }
+  if (n_steps < 1) { lia_set_error("%s: n_steps=%d must be >= 1", who, n_steps); return true; }
+  if (step0 < 0) { lia_set_error("%s: step0=%d must be >= 0", who, step0); return true; }
+  return false;
+}
+// a chunk's logits into rows r0 .. of logits_out [B * T, vocab] (NULL: not asked for); *err keeps the first failure
+static void logits_out_copy(bf16_t* logits_out, const bf16_t* logits, int r0, int n, int vocab, hipStream_t st, hipError_t* err) {
+  if (logits_out && *err == hipSuccess)
+    *err = hipMemcpyAsync(logits_out + (size_t)r0 * vocab, logits, (size_t)n * vocab * sizeof(bf16_t), hipMemcpyDeviceToDevice, st);
+}
+
+// the arguments every verify head needs (names: their names, in the order they are passed), refused by name
+#define LIA_VERIFY_NULL(who, names, ...)                                                      \
+  do {                                                                                        \
+    const void* const ptrs[] = {__VA_ARGS__};                                                 \
+    for (size_t i = 0; i < sizeof(ptrs) / sizeof(*ptrs); ++i)                                 \
+      if (!ptrs[i]) { lia_set_error("%s: NULL %s", who, names[i]); return LIA_ERR_INVALID; }  \
+  } while (0)
+static const char* const GREEDY_ARGS[] = {"hidden", "norm weight", "lm_head weight", "block_ids", "greedy", "accepted", "common", "next"};
+static const char* const SAMPLED_ARGS[] = {"hidden", "norm weight", "lm_head weight", "block_ids", "sampled", "accepted", "common", "next"};
+static const char* const REJECT_ARGS[] = {"hidden", "norm weight", "lm_head weight", "block_ids", "token", "ok", "accepted", "common", "next"};
+
 // norm_b == nullptr: RMSNorm (Llama), else LayerNorm
 static int lm_verify_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int B, int T, int H, const bf16_t* norm_w,
                           const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, int suppress_token, int n_suppress,
                           const int64_t* block_ids, const int32_t* active, int64_t* greedy, int32_t* accepted, int32_t* common,
                           int64_t* next, hipStream_t st, const int32_t* n_suppress_rows = nullptr) {
-  if (penalties_refused(who, ctx, LIA_NO_BLOCK_PENALTIES)) return LIA_ERR_INVALID;
-  if (B <= 0) { lia_set_error("%s: B=%d must be >= 1", who, B); return LIA_ERR_INVALID; }
-  if (T < 2) { lia_set_error("%s: T=%d must be >= 2 (the pending token and at least one draft token)", who, T); return LIA_ERR_INVALID; }
-  if ((long)B * T > 0x7fffffffL) { lia_set_error("%s: B=%d x T=%d rows", who, B, T); return LIA_ERR_INVALID; }
-  if (n_suppress < 0 || n_suppress > T) { lia_set_error("%s: n_suppress=%d must be in [0, T=%d]", who, n_suppress, T); return LIA_ERR_INVALID; }
-  if (suppress_token < -1 || (vocab > 0 && suppress_token >= vocab)) { lia_set_error("%s: suppress_token=%d must be -1 or in [0, vocab)", who, suppress_token); return LIA_ERR_INVALID; }
-  const uint32_t* mask;
-  long ldm;
-  if (int mrc = token_mask_of(who, ctx, (long)B * T, vocab, &mask, &ldm)) return mrc;
-  LiaSink sk;
-  if (int src = logprob_sink_of(who, ctx, (long)B * T, vocab, &sk)) return src;
+  LiaHeadMods m;
+  if (int mrc = head_mods_resolve(who, ctx, LiaHeadTakes{nullptr, nullptr, LIA_NO_BLOCK_PENALTIES}, (long)B * T, vocab, &m,
+                                  [&] { return block_args_invalid(who, B, T, n_suppress, suppress_token, vocab); }))
+    return mrc;
   const int rc = lm_rows_chunked(who, ctx, hidden, ldh, B * T, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
-    if (mask) lia_verify_argmax_masked_launch(logits, vocab, n, vocab, suppress_token, n_suppress, n_suppress_rows, T, r0, greedy, mask, ldm, st);
-    else lia_verify_argmax_rows_launch(logits, vocab, n, vocab, suppress_token, n_suppress, n_suppress_rows, T, r0, greedy, st);
-    sink_write(sk, logits, vocab, n, vocab, greedy + r0, r0, st);
+    const LiaBlockPos pos{n_suppress, n_suppress_rows, T, r0};
+    pick_argmax(m.mask, logits, vocab, n, vocab, suppress_token, &pos, greedy, st);
+    sink_write(m.sink, logits, vocab, n, vocab, greedy + r0, r0, st);
   });
   if (rc) return rc;
   lia_verify_accept_launch(block_ids, greedy, active, B, T, accepted, common, next, st);
@@ -538,19 +606,11 @@ static int lm_verify_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, l
   return LIA_OK;
 }
 
-#define LIA_VERIFY_NULL(who, ...)                                                             \
-  do {                                                                                        \
-    const void* const ptrs[] = {__VA_ARGS__};                                                 \
-    static const char* const names[] = {"hidden", "norm weight", "lm_head weight", "block_ids", "greedy", "accepted", "common", "next"}; \
-    for (int i = 0; i < 8; ++i)                                                               \
-      if (!ptrs[i]) { lia_set_error("%s: NULL %s", who, names[i]); return LIA_ERR_INVALID; }  \
-  } while (0)
-
 extern "C" int lia_lm_verify(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* lnw, const lia_bf16* lnb,
                              const lia_bf16* emb, int vocab, float eps, int suppress_token, int n_suppress, const int64_t* block_ids,
                              const int32_t* active, int64_t* greedy, int32_t* accepted, int32_t* common, int64_t* next, void* stream) {
   if (!ctx) return LIA_ERR_INVALID;
-  LIA_VERIFY_NULL("lia_lm_verify", hidden, lnw, emb, block_ids, greedy, accepted, common, next);
+  LIA_VERIFY_NULL("lia_lm_verify", GREEDY_ARGS, hidden, lnw, emb, block_ids, greedy, accepted, common, next);
   if (!lnb) { lia_set_error("lia_lm_verify: NULL norm bias"); return LIA_ERR_INVALID; }
   return lm_verify_impl("lia_lm_verify", ctx, hidden, ldh, B, T, H, lnw, lnb, emb, vocab, eps, suppress_token, n_suppress, block_ids,
                         active, greedy, accepted, common, next, (hipStream_t)stream);
@@ -563,7 +623,7 @@ extern "C" int lia_lm_verify_rows(lia_ctx* ctx, const lia_bf16* hidden, long ldh
                                   const int64_t* block_ids, const int32_t* active, int64_t* greedy, int32_t* accepted, int32_t* common,
                                   int64_t* next, void* stream) {
   if (!ctx) return LIA_ERR_INVALID;
-  LIA_VERIFY_NULL("lia_lm_verify_rows", hidden, lnw, emb, block_ids, greedy, accepted, common, next);
+  LIA_VERIFY_NULL("lia_lm_verify_rows", GREEDY_ARGS, hidden, lnw, emb, block_ids, greedy, accepted, common, next);
   if (!lnb) { lia_set_error("lia_lm_verify_rows: NULL norm bias"); return LIA_ERR_INVALID; }
   if (!n_suppress_rows) { lia_set_error("lia_lm_verify_rows: NULL n_suppress_rows"); return LIA_ERR_INVALID; }
   return lm_verify_impl("lia_lm_verify_rows", ctx, hidden, ldh, B, T, H, lnw, lnb, emb, vocab, eps, suppress_token, 0, block_ids, active,
@@ -575,51 +635,32 @@ extern "C" int lia_llama_lm_verify(lia_ctx* ctx, const lia_bf16* hidden, long ld
                                    const int64_t* block_ids, const int32_t* active, int64_t* greedy, int32_t* accepted,
                                    int32_t* common, int64_t* next, void* stream) {
   if (!ctx) return LIA_ERR_INVALID;
-  LIA_VERIFY_NULL("lia_llama_lm_verify", hidden, normw, lm, block_ids, greedy, accepted, common, next);
+  LIA_VERIFY_NULL("lia_llama_lm_verify", GREEDY_ARGS, hidden, normw, lm, block_ids, greedy, accepted, common, next);
   return lm_verify_impl("lia_llama_lm_verify", ctx, hidden, ldh, B, T, H, normw, nullptr, lm, vocab, eps, suppress_token, n_suppress,
                         block_ids, active, greedy, accepted, common, next, (hipStream_t)stream);
 }
 
-// ------------------------------------------------------------------------------------------------
-// sampled verification: lm_verify_impl's chunks with lia_sample's draw behind every block position in place of the argmax
-// (lia_verify_sample_kernel, lia_sample.hip), then the same acceptance kernel on the sampled ids
-// ------------------------------------------------------------------------------------------------
-// norm_b == nullptr: RMSNorm (Llama), else LayerNorm
+// the sampled head.  norm_b == nullptr: RMSNorm (Llama), else LayerNorm
 static int lm_verify_sample_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int B, int T, int H, const bf16_t* norm_w,
                                  const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, int suppress_token, int n_suppress,
                                  const int32_t* n_suppress_rows, const lia_block_sampler* smp, const int64_t* block_ids,
                                  const int32_t* active, int64_t* sampled, int32_t* accepted, int32_t* common, int64_t* next,
                                  float* p_draft, bf16_t* logits_out, hipStream_t st) {
-  if (penalties_refused(who, ctx, LIA_NO_BLOCK_PENALTIES)) return LIA_ERR_INVALID;
-  if (!smp) { lia_set_error("%s: NULL sampler", who); return LIA_ERR_INVALID; }
-  if (!smp->uniforms) { lia_set_error("%s: NULL uniforms", who); return LIA_ERR_INVALID; }
-  if (B <= 0) { lia_set_error("%s: B=%d must be >= 1", who, B); return LIA_ERR_INVALID; }
-  if (T < 2) { lia_set_error("%s: T=%d must be >= 2 (the pending token and at least one draft token)", who, T); return LIA_ERR_INVALID; }
-  if ((long)B * T > 0x7fffffffL) { lia_set_error("%s: B=%d x T=%d rows", who, B, T); return LIA_ERR_INVALID; }
-  if (n_suppress < 0 || n_suppress > T) { lia_set_error("%s: n_suppress=%d must be in [0, T=%d]", who, n_suppress, T); return LIA_ERR_INVALID; }
-  if (suppress_token < -1 || (vocab > 0 && suppress_token >= vocab)) { lia_set_error("%s: suppress_token=%d must be -1 or in [0, vocab)", who, suppress_token); return LIA_ERR_INVALID; }
-  if (vocab > LIA_SAMPLE_MAX_VOCAB) { lia_set_error("%s: vocab=%d must be in [1, %d]", who, vocab, LIA_SAMPLE_MAX_VOCAB); return LIA_ERR_INVALID; }
-  if (sample_settings_invalid(who, smp->temperature, smp->top_k, smp->top_p)) return LIA_ERR_INVALID;
-  if (smp->ldu < B) { lia_set_error("%s: ldu=%ld < B=%d", who, smp->ldu, B); return LIA_ERR_INVALID; }
-  if (smp->n_steps < 1) { lia_set_error("%s: n_steps=%d must be >= 1", who, smp->n_steps); return LIA_ERR_INVALID; }
-  if (smp->step0 < 0) { lia_set_error("%s: step0=%d must be >= 0", who, smp->step0); return LIA_ERR_INVALID; }
-  const uint32_t* mask;
-  long ldm;
-  if (int mrc = token_mask_of(who, ctx, (long)B * T, vocab, &mask, &ldm)) return mrc;
-  LiaSink sk;
-  if (int src = logprob_sink_of(who, ctx, (long)B * T, vocab, &sk)) return src;
+  LiaHeadMods m;
+  if (int mrc = head_mods_resolve(who, ctx, LiaHeadTakes{nullptr, nullptr, LIA_NO_BLOCK_PENALTIES}, (long)B * T, vocab, &m, [&] {
+        if (!smp) { lia_set_error("%s: NULL sampler", who); return true; }
+        if (!smp->uniforms) { lia_set_error("%s: NULL uniforms", who); return true; }
+        return block_args_invalid(who, B, T, n_suppress, suppress_token, vocab) ||
+               block_draw_invalid(who, B, vocab, smp->temperature, smp->top_k, smp->top_p, smp->ldu, smp->n_steps, smp->step0);
+      }))
+    return mrc;
+  const LiaDraw draw{smp->temperature, smp->top_k, smp->top_p, smp->uniforms};
   hipError_t copy_err = hipSuccess;
   const int rc = lm_rows_chunked(who, ctx, hidden, ldh, B * T, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
-    if (mask)
-      lia_verify_sample_masked_launch(logits, vocab, n, vocab, smp->temperature, smp->top_k, smp->top_p, suppress_token, n_suppress,
-                                      n_suppress_rows, T, r0, smp->uniforms, smp->ldu, smp->n_steps, smp->step0, smp->step_rows, block_ids,
-                                      sampled, p_draft, mask, ldm, st);
-    else
-      lia_verify_sample_launch(logits, vocab, n, vocab, smp->temperature, smp->top_k, smp->top_p, suppress_token, n_suppress, n_suppress_rows,
-                               T, r0, smp->uniforms, smp->ldu, smp->n_steps, smp->step0, smp->step_rows, block_ids, sampled, p_draft, st);
-    sink_write(sk, logits, vocab, n, vocab, sampled + r0, r0, st);
-    if (logits_out && copy_err == hipSuccess)
-      copy_err = hipMemcpyAsync(logits_out + (size_t)r0 * vocab, logits, (size_t)n * vocab * sizeof(bf16_t), hipMemcpyDeviceToDevice, st);
+    const LiaBlockDraw blk{{n_suppress, n_suppress_rows, T, r0}, smp->ldu, smp->n_steps, smp->step0, smp->step_rows, block_ids};
+    pick_draw(m.mask, logits, vocab, n, vocab, draw, suppress_token, &blk, sampled, p_draft, st);
+    sink_write(m.sink, logits, vocab, n, vocab, sampled + r0, r0, st);
+    logits_out_copy(logits_out, logits, r0, n, vocab, st, &copy_err);
   });
   if (rc) return rc;
   HIP_TRY(copy_err);
@@ -628,21 +669,13 @@ static int lm_verify_sample_impl(const char* who, lia_ctx* ctx, const bf16_t* hi
   return LIA_OK;
 }
 
-#define LIA_VERIFY_SAMPLE_NULL(who, ...)                                                      \
-  do {                                                                                        \
-    const void* const ptrs[] = {__VA_ARGS__};                                                 \
-    static const char* const names[] = {"hidden", "norm weight", "lm_head weight", "block_ids", "sampled", "accepted", "common", "next"}; \
-    for (int i = 0; i < 8; ++i)                                                               \
-      if (!ptrs[i]) { lia_set_error("%s: NULL %s", who, names[i]); return LIA_ERR_INVALID; }  \
-  } while (0)
-
 extern "C" int lia_lm_verify_sample(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* lnw,
                                     const lia_bf16* lnb, const lia_bf16* emb, int vocab, float eps, int suppress_token, int n_suppress,
                                     const int32_t* n_suppress_rows, const lia_block_sampler* sampler, const int64_t* block_ids,
                                     const int32_t* active, int64_t* sampled, int32_t* accepted, int32_t* common, int64_t* next,
                                     float* p_draft, lia_bf16* logits_out, void* stream) {
   if (!ctx) return LIA_ERR_INVALID;
-  LIA_VERIFY_SAMPLE_NULL("lia_lm_verify_sample", hidden, lnw, emb, block_ids, sampled, accepted, common, next);
+  LIA_VERIFY_NULL("lia_lm_verify_sample", SAMPLED_ARGS, hidden, lnw, emb, block_ids, sampled, accepted, common, next);
   if (!lnb) { lia_set_error("lia_lm_verify_sample: NULL norm bias"); return LIA_ERR_INVALID; }
   return lm_verify_sample_impl("lia_lm_verify_sample", ctx, hidden, ldh, B, T, H, lnw, lnb, emb, vocab, eps, suppress_token, n_suppress,
                                n_suppress_rows, sampler, block_ids, active, sampled, accepted, common, next, p_draft, logits_out,
@@ -655,58 +688,46 @@ extern "C" int lia_llama_lm_verify_sample(lia_ctx* ctx, const lia_bf16* hidden, 
                                           const int32_t* active, int64_t* sampled, int32_t* accepted, int32_t* common, int64_t* next,
                                           float* p_draft, lia_bf16* logits_out, void* stream) {
   if (!ctx) return LIA_ERR_INVALID;
-  LIA_VERIFY_SAMPLE_NULL("lia_llama_lm_verify_sample", hidden, normw, lm, block_ids, sampled, accepted, common, next);
+  LIA_VERIFY_NULL("lia_llama_lm_verify_sample", SAMPLED_ARGS, hidden, normw, lm, block_ids, sampled, accepted, common, next);
   return lm_verify_sample_impl("lia_llama_lm_verify_sample", ctx, hidden, ldh, B, T, H, normw, nullptr, lm, vocab, eps, suppress_token,
                                n_suppress, n_suppress_rows, sampler, block_ids, active, sampled, accepted, common, next, p_draft,
                                logits_out, (hipStream_t)stream);
 }
 
-// ------------------------------------------------------------------------------------------------
-// rejection verification: lm_verify_sample_impl's chunks with lia_verify_reject_kernel (the accept test and the residual draw of a
-// stochastic drafter's block, lia_sample.hip), then the acceptance kernel on its ok / token
-// ------------------------------------------------------------------------------------------------
+// the rejection head
 static int lm_verify_reject_impl(const char* who, lia_ctx* ctx, const bf16_t* hidden, long ldh, int B, int T, int H, const bf16_t* norm_w,
                                  const bf16_t* norm_b, const bf16_t* emb, int vocab, float eps, int suppress_token, int n_suppress,
                                  const int32_t* n_suppress_rows, const lia_block_rejector* rej, const int64_t* block_ids,
                                  const int32_t* active, int64_t* token, int32_t* ok, int32_t* accepted, int32_t* common, int64_t* next,
                                  float* p_tok, float* q_tok, float* resid_mass, bf16_t* logits_out, hipStream_t st) {
-  if (logprob_sink_refused(who, ctx, "rejection verification writes none -- an accepted draft token is not this head's own output"))
-    return LIA_ERR_INVALID;
-  if (penalties_refused(who, ctx, LIA_NO_BLOCK_PENALTIES)) return LIA_ERR_INVALID;
-  if (ctx->token_mask) {
-    lia_set_error("%s: a token mask is set (lia_ctx_set_token_mask): rejection verification takes none -- the drafter's Q would have to be "
-                  "masked the same way", who);
-    return LIA_ERR_INVALID;
-  }
-  if (!rej) { lia_set_error("%s: NULL rejector", who); return LIA_ERR_INVALID; }
-  if (!rej->draft_logits) { lia_set_error("%s: NULL draft_logits", who); return LIA_ERR_INVALID; }
-  if (!rej->u_acc) { lia_set_error("%s: NULL u_acc", who); return LIA_ERR_INVALID; }
-  if (!rej->u_res) { lia_set_error("%s: NULL u_res", who); return LIA_ERR_INVALID; }
-  if (n_suppress_rows) { lia_set_error("%s: n_suppress_rows must be NULL (rejection verification is common mode only)", who); return LIA_ERR_INVALID; }
-  if (B <= 0) { lia_set_error("%s: B=%d must be >= 1", who, B); return LIA_ERR_INVALID; }
-  if (T < 2) { lia_set_error("%s: T=%d must be >= 2 (the pending token and at least one draft token)", who, T); return LIA_ERR_INVALID; }
-  if ((long)B * T > 0x7fffffffL) { lia_set_error("%s: B=%d x T=%d rows", who, B, T); return LIA_ERR_INVALID; }
-  if (n_suppress < 0 || n_suppress > T) { lia_set_error("%s: n_suppress=%d must be in [0, T=%d]", who, n_suppress, T); return LIA_ERR_INVALID; }
-  if (suppress_token < -1 || (vocab > 0 && suppress_token >= vocab)) { lia_set_error("%s: suppress_token=%d must be -1 or in [0, vocab)", who, suppress_token); return LIA_ERR_INVALID; }
-  if (vocab > LIA_SAMPLE_MAX_VOCAB) { lia_set_error("%s: vocab=%d must be in [1, %d]", who, vocab, LIA_SAMPLE_MAX_VOCAB); return LIA_ERR_INVALID; }
-  if (sample_settings_invalid(who, rej->temperature, rej->top_k, rej->top_p)) return LIA_ERR_INVALID;
-  if (rej->ldu < B) { lia_set_error("%s: ldu=%ld < B=%d", who, rej->ldu, B); return LIA_ERR_INVALID; }
-  if (rej->n_steps < 1) { lia_set_error("%s: n_steps=%d must be >= 1", who, rej->n_steps); return LIA_ERR_INVALID; }
-  if (rej->step0 < 0) { lia_set_error("%s: step0=%d must be >= 0", who, rej->step0); return LIA_ERR_INVALID; }
-  if (rej->ldd_row < vocab) { lia_set_error("%s: ldd_row=%ld < vocab=%d", who, rej->ldd_row, vocab); return LIA_ERR_INVALID; }
-  if (rej->ldd_pos < vocab) { lia_set_error("%s: ldd_pos=%ld < vocab=%d", who, rej->ldd_pos, vocab); return LIA_ERR_INVALID; }
-  if (vocab % 8 == 0 && (((uintptr_t)rej->draft_logits & 15) || rej->ldd_row % 8 || rej->ldd_pos % 8)) {
-    lia_set_error("%s: draft_logits=%p ldd_row=%ld ldd_pos=%ld: with vocab %% 8 == 0 the rows are read 16 bytes at a time -- a 16-byte "
-                  "aligned pointer and pitches that are multiples of 8", who, (const void*)rej->draft_logits, rej->ldd_row, rej->ldd_pos);
-    return LIA_ERR_INVALID;
-  }
+  const LiaHeadTakes none{"rejection verification takes none -- the drafter's Q would have to be masked the same way",
+                          "rejection verification writes none -- an accepted draft token is not this head's own output", LIA_NO_BLOCK_PENALTIES};
+  LiaHeadMods m;
+  if (int mrc = head_mods_resolve(who, ctx, none, (long)B * T, vocab, &m, [&] {
+        if (!rej) { lia_set_error("%s: NULL rejector", who); return true; }
+        if (!rej->draft_logits) { lia_set_error("%s: NULL draft_logits", who); return true; }
+        if (!rej->u_acc) { lia_set_error("%s: NULL u_acc", who); return true; }
+        if (!rej->u_res) { lia_set_error("%s: NULL u_res", who); return true; }
+        if (n_suppress_rows) { lia_set_error("%s: n_suppress_rows must be NULL (rejection verification is common mode only)", who); return true; }
+        if (block_args_invalid(who, B, T, n_suppress, suppress_token, vocab) ||
+            block_draw_invalid(who, B, vocab, rej->temperature, rej->top_k, rej->top_p, rej->ldu, rej->n_steps, rej->step0))
+          return true;
+        if (rej->ldd_row < vocab) { lia_set_error("%s: ldd_row=%ld < vocab=%d", who, rej->ldd_row, vocab); return true; }
+        if (rej->ldd_pos < vocab) { lia_set_error("%s: ldd_pos=%ld < vocab=%d", who, rej->ldd_pos, vocab); return true; }
+        if (vocab % 8 == 0 && (((uintptr_t)rej->draft_logits & 15) || rej->ldd_row % 8 || rej->ldd_pos % 8)) {
+          lia_set_error("%s: draft_logits=%p ldd_row=%ld ldd_pos=%ld: with vocab %% 8 == 0 the rows are read 16 bytes at a time -- a 16-byte "
+                        "aligned pointer and pitches that are multiples of 8", who, (const void*)rej->draft_logits, rej->ldd_row, rej->ldd_pos);
+          return true;
+        }
+        return false;
+      }))
+    return mrc;
   hipError_t copy_err = hipSuccess;
   const int rc = lm_rows_chunked(who, ctx, hidden, ldh, B * T, H, norm_w, norm_b, emb, vocab, eps, st, [&](const bf16_t* logits, int r0, int n) {
     lia_verify_reject_launch(logits, vocab, n, vocab, (const bf16_t*)rej->draft_logits, rej->ldd_row, rej->ldd_pos, rej->temperature, rej->top_k,
                              rej->top_p, suppress_token, n_suppress, T, r0, rej->u_acc, rej->u_res, rej->ldu, rej->n_steps, rej->step0,
                              block_ids, token, ok, p_tok, q_tok, resid_mass, st);
-    if (logits_out && copy_err == hipSuccess)
-      copy_err = hipMemcpyAsync(logits_out + (size_t)r0 * vocab, logits, (size_t)n * vocab * sizeof(bf16_t), hipMemcpyDeviceToDevice, st);
+    logits_out_copy(logits_out, logits, r0, n, vocab, st, &copy_err);
   });
   if (rc) return rc;
   HIP_TRY(copy_err);
@@ -715,21 +736,13 @@ static int lm_verify_reject_impl(const char* who, lia_ctx* ctx, const bf16_t* hi
   return LIA_OK;
 }
 
-#define LIA_VERIFY_REJECT_NULL(who, ...)                                                      \
-  do {                                                                                        \
-    const void* const ptrs[] = {__VA_ARGS__};                                                 \
-    static const char* const names[] = {"hidden", "norm weight", "lm_head weight", "block_ids", "token", "ok", "accepted", "common", "next"}; \
-    for (int i = 0; i < 9; ++i)                                                               \
-      if (!ptrs[i]) { lia_set_error("%s: NULL %s", who, names[i]); return LIA_ERR_INVALID; }  \
-  } while (0)
-
 extern "C" int lia_lm_verify_reject(lia_ctx* ctx, const lia_bf16* hidden, long ldh, int B, int T, int H, const lia_bf16* lnw,
                                     const lia_bf16* lnb, const lia_bf16* emb, int vocab, float eps, int suppress_token, int n_suppress,
                                     const int32_t* n_suppress_rows, const lia_block_rejector* rejector, const int64_t* block_ids,
                                     const int32_t* active, int64_t* token, int32_t* ok, int32_t* accepted, int32_t* common, int64_t* next,
                                     float* p_tok, float* q_tok, float* resid_mass, lia_bf16* logits_out, void* stream) {
   if (!ctx) return LIA_ERR_INVALID;
-  LIA_VERIFY_REJECT_NULL("lia_lm_verify_reject", hidden, lnw, emb, block_ids, token, ok, accepted, common, next);
+  LIA_VERIFY_NULL("lia_lm_verify_reject", REJECT_ARGS, hidden, lnw, emb, block_ids, token, ok, accepted, common, next);
   if (!lnb) { lia_set_error("lia_lm_verify_reject: NULL norm bias"); return LIA_ERR_INVALID; }
   return lm_verify_reject_impl("lia_lm_verify_reject", ctx, hidden, ldh, B, T, H, lnw, lnb, emb, vocab, eps, suppress_token, n_suppress,
                                n_suppress_rows, rejector, block_ids, active, token, ok, accepted, common, next, p_tok, q_tok, resid_mass,
@@ -742,7 +755,7 @@ extern "C" int lia_llama_lm_verify_reject(lia_ctx* ctx, const lia_bf16* hidden, 
                                           const int32_t* active, int64_t* token, int32_t* ok, int32_t* accepted, int32_t* common,
                                           int64_t* next, float* p_tok, float* q_tok, float* resid_mass, lia_bf16* logits_out, void* stream) {
   if (!ctx) return LIA_ERR_INVALID;
-  LIA_VERIFY_REJECT_NULL("lia_llama_lm_verify_reject", hidden, normw, lm, block_ids, token, ok, accepted, common, next);
+  LIA_VERIFY_NULL("lia_llama_lm_verify_reject", REJECT_ARGS, hidden, normw, lm, block_ids, token, ok, accepted, common, next);
   return lm_verify_reject_impl("lia_llama_lm_verify_reject", ctx, hidden, ldh, B, T, H, normw, nullptr, lm, vocab, eps, suppress_token,
                                n_suppress, n_suppress_rows, rejector, block_ids, active, token, ok, accepted, common, next, p_tok, q_tok,
                                resid_mass, logits_out, (hipStream_t)stream);

@@ -17,7 +17,7 @@ from . import _native as N
 from . import hostinfo, ops
 from .kvcache import KV_SERIAL
 from .model import LayerStore
-from .scheduler import check_verify_block, default_stream_format, minibatch_bounds, wire_format_code
+from .scheduler import HeadModifierHooks, check_verify_block, default_stream_format, minibatch_bounds, verify_head, wire_format_code
 from .streaming import HiddenPairs, ResidentRun, WeightPipeline, stream_order
 
 LLAMA_TENSORS = ("in_norm_w", "q_w", "k_w", "v_w", "o_w", "post_norm_w", "gate_w", "up_w", "down_w")
@@ -182,7 +182,7 @@ class LlamaKVState:
             self.kv.append(N.KV(k.data_ptr(), v.data_ptr(), smax, B, 1))
 
 
-class LlamaScheduler:
+class LlamaScheduler(HeadModifierHooks):
     """forward(ids, kv, gpu_percentage=..., num_minibatch=...) -> (logits, next ids) on the device."""
 
     def __init__(self, model, device=0, n_slots=4, pack=None, split_decode=None):
@@ -227,34 +227,14 @@ class LlamaScheduler:
         penalties (penalties.Penalties): as OffloadScheduler.forward -- the ids come from the logits penalised under the
         generation's count table, set on the context around the head only."""
         m, sh = self.model, self.model.shape
-        lib = N.lib()
         B, T = input_ids.shape
         x, xlast = self._layers(input_ids, kv_state, gpu_percentage, num_minibatch, pin_weight, enable_cxl)
         ctx = self.ctx
-        st = ctypes.c_void_p(ctx.stream)
-        logits = torch.empty((B, sh.vocab), dtype=torch.bfloat16, device="cuda")
-        nxt_ids = torch.empty((B,), dtype=torch.int64, device="cuda")
-        x_lm, T_lm = (x, T) if xlast is None else (xlast, 1)     # (the last layer already reduced the block to its last position)
-        if token_mask is not None:
-            ctx.set_token_mask(token_mask)
-        if logprobs is not None:
-            ctx.set_logprob_sink(logprobs, (B,))
-        try:
-            ctx.token_mask_fits(sh.vocab)
-            if penalties is not None:
-                penalties.bind(ctx)
-            N.check(lib.lia_llama_lm_head(ctx.handle, ctypes.c_void_p(x_lm.data_ptr()), B, T_lm, sh.hidden, ctypes.c_void_p(m.final_norm_w.data_ptr()),
-                                          ctypes.c_void_p(m.lm_head.data_ptr()), sh.vocab, sh.rms_eps, suppress_token,
-                                          ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(nxt_ids.data_ptr()), st), "lia_llama_lm_head")
+        with ctx.head_modifiers(token_mask, logprobs, (B,), penalties):
+            # (xlast: the last layer already reduced the block to its last position)
+            logits, nxt_ids = ctx.llama_lm_head(x if xlast is None else xlast, m.final_norm_w, m.lm_head, sh.rms_eps, suppress_token)
             if sampler is not None:
                 nxt_ids = sampler(ctx, logits, suppress_token)
-        finally:
-            if token_mask is not None:
-                ctx.set_token_mask(None)
-            if logprobs is not None:
-                ctx.set_logprob_sink(None)
-            if penalties is not None:
-                ctx.set_penalties(None)
         ctx.synchronize()
         kv_state.len += T
         return logits, nxt_ids
@@ -300,24 +280,9 @@ class LlamaScheduler:
                 self.ctx.set_option(N.LIA_OPT_BLOCK_ATTENTION, 0)
         ids_dev = block_ids.to(device="cuda", dtype=torch.int64).contiguous()
         act_dev = None if active is None else torch.as_tensor(active).to(device="cuda", dtype=torch.int32).contiguous()
-        if token_mask is not None:
-            self.ctx.set_token_mask(token_mask)
-        if logprobs is not None:
-            self.ctx.set_logprob_sink(logprobs, tuple(block_ids.shape))
-        try:
-            if rejector is not None:
-                res = self.ctx.llama_lm_verify_reject(x, m.final_norm_w, m.lm_head, ids_dev, rejector, sh.rms_eps, suppress_token, n_suppress,
-                                                      active=act_dev, return_logits=return_logits, return_probs=True)
-            elif sampler is None:
-                res = self.ctx.llama_lm_verify(x, m.final_norm_w, m.lm_head, ids_dev, sh.rms_eps, suppress_token, n_suppress, act_dev)
-            else:
-                res = self.ctx.llama_lm_verify_sample(x, m.final_norm_w, m.lm_head, ids_dev, sampler, sh.rms_eps, suppress_token, n_suppress,
-                                                      active=act_dev, return_logits=return_logits, return_p_draft=True)
-        finally:
-            if token_mask is not None:
-                self.ctx.set_token_mask(None)
-            if logprobs is not None:
-                self.ctx.set_logprob_sink(None)
+        with self.ctx.head_modifiers(token_mask, logprobs, tuple(block_ids.shape)):
+            res = verify_head(self.ctx, ((m.final_norm_w,), m.lm_head, sh.rms_eps, "llama_"), x, ids_dev, act_dev, suppress_token, n_suppress,
+                              sampler=sampler, rejector=rejector, return_logits=return_logits)
         self.ctx.synchronize()
         common = int(res.common.item())
         kv_state.len = pos0 + common + 1
@@ -409,24 +374,6 @@ class LlamaScheduler:
                 pipe.release(idx)
             x, y = y, x
         return x, xlast
-
-    def set_token_mask(self, mask):
-        """None only (generate() when a constrained generation ends): no allowed-token table on the library context; as
-        OffloadScheduler.set_token_mask"""
-        if mask is not None:
-            raise ValueError("set_token_mask takes None only: a table is passed per call, forward(token_mask=) / verify(token_mask=)")
-        if self.ctx is not None:
-            self.ctx.set_token_mask(None)
-
-    supports_penalties = True         # forward(penalties=): generate()'s repetition / presence / frequency penalties
-
-    def set_penalties(self, table):
-        """None only (generate() when a penalised generation ends): no count table on the library context; as
-        OffloadScheduler.set_penalties"""
-        if table is not None:
-            raise ValueError("set_penalties takes None only: the table is passed per call, forward(penalties=)")
-        if self.ctx is not None:
-            self.ctx.set_penalties(None)
 
     def stream_stats(self, reset=False):
         return self.pipe.stats(reset) if self.pipe else (0.0, 0.0)

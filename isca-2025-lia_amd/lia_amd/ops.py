@@ -5,6 +5,7 @@ Every function takes contiguous bf16 CUDA tensors (int64 for ids) and launches o
 (a raw hipStream_t as int; default = the context's compute stream).
 """
 import collections
+import contextlib
 import ctypes
 
 import torch
@@ -26,6 +27,14 @@ def _chk(t, dtype=torch.bfloat16):
         return
     if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
         raise ValueError(f"expected a contiguous {dtype} CUDA tensor, got {t.dtype} {t.device} contiguous={t.is_contiguous()}")
+
+
+def _chk_logits(logits, rows_name="M"):
+    """logits [rows, vocab] as the bare head kernels take them (rows may be strided) -> (rows, vocab)"""
+    if not logits.is_cuda or logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError(f"logits: expected a [{rows_name}, vocab] bf16 CUDA tensor with unit column stride, got {logits.dtype} {logits.device} "
+                         f"shape {tuple(logits.shape)} strides {logits.stride()}")
+    return logits.shape
 
 
 # lia_lm_verify's outputs, all on the device: greedy int64 [B, T], accepted int32 [B], common int32 [1], next int64 [B].  On the
@@ -229,7 +238,9 @@ class Context:
         if m.numel() == 0:
             raise ValueError(f"token mask: an empty tensor of shape {tuple(mask.shape)}")
         torch.cuda.current_stream().synchronize()              # (the library's stream reads what torch's wrote)
-        self._point_token_mask(m, 0)
+        rows, W = m.shape
+        ldm = 0 if rows == 1 else W                            # (one row: broadcast)
+        N.check(self.lib.lia_ctx_set_token_mask(self.handle, _ptr(m), ldm, rows), "lia_ctx_set_token_mask")
         self._token_mask = m
 
     def token_mask_fits(self, vocab):
@@ -237,13 +248,6 @@ class Context:
         m = self._token_mask
         if m is not None and m.shape[1] < (vocab + 31) // 32:
             raise ValueError(f"token mask: rows of {m.shape[1]} words, a vocabulary of {vocab} tokens needs {(vocab + 31) // 32}")
-
-    def _point_token_mask(self, m, r0):
-        """the table from row r0 of m on (one row: broadcast)"""
-        rows, W = m.shape
-        ldm = 0 if rows == 1 else W
-        N.check(self.lib.lia_ctx_set_token_mask(self.handle, ctypes.c_void_p(m.data_ptr() + 4 * r0 * ldm), ldm, rows - r0 if ldm else 1),
-                "lia_ctx_set_token_mask")
 
     def set_logprob_sink(self, req, shape=None):
         """lia_ctx_set_logprob_sink: req (LogprobRequest; its tensors are allocated here for a head call on `shape` = [B] or [B, T]
@@ -260,24 +264,15 @@ class Context:
             raise ValueError(f"logprobs: n_top={req.n_top} must be in [0, {LOGPROB_MAX_TOP}]")
         req.allocate(shape, f"cuda:{self.device}")
         self._logprob_sink = req
-        self._point_logprob_sink(req, 0)
-
-    def _point_logprob_sink(self, req, r0):
-        """the sink from row r0 of the request's tensors on"""
-        n, rows = req.n_top, req.chosen.numel()
-        N.check(self.lib.lia_ctx_set_logprob_sink(self.handle, n, ctypes.c_void_p(req.chosen.data_ptr() + 4 * r0),
-                                                  ctypes.c_void_p(req.top_ids.data_ptr() + 8 * r0 * n) if n else None,
-                                                  ctypes.c_void_p(req.top_logprobs.data_ptr() + 4 * r0 * n) if n else None, rows - r0),
-                "lia_ctx_set_logprob_sink")
+        n = req.n_top
+        N.check(self.lib.lia_ctx_set_logprob_sink(self.handle, n, _ptr(req.chosen), _ptr(req.top_ids) if n else None,
+                                                  _ptr(req.top_logprobs) if n else None, req.chosen.numel()), "lia_ctx_set_logprob_sink")
 
     def topn_logprobs(self, logits, ids, n_top, stream=None):
         """lia_topn_logprobs (the bare kernel): per row of logits [M, vocab] (bf16, rows may be strided) the log-probability of ids[r]
         (int64 [M]) and the n_top tokens of largest logit with theirs, ordered by logit descending, ties by the lower id.  Returns
         (float32 [M], int64 [M, n_top], float32 [M, n_top]) on the device."""
-        if not logits.is_cuda or logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
-            raise ValueError(f"logits: expected a [M, vocab] bf16 CUDA tensor with unit column stride, got {logits.dtype} {logits.device} "
-                             f"shape {tuple(logits.shape)} strides {logits.stride()}")
-        M, vocab = logits.shape
+        M, vocab = _chk_logits(logits)
         _chk(ids, torch.int64)
         if ids.numel() != M:
             raise ValueError(f"ids has {ids.numel()} entries, logits {M} rows")
@@ -316,20 +311,31 @@ class Context:
                              f"{scratch.dtype} {scratch.device} shape {tuple(scratch.shape)}")
         if synchronize:
             torch.cuda.current_stream().synchronize()          # (the library's stream reads what torch's wrote)
+        N.check(self.lib.lia_ctx_set_penalties(self.handle, _ptr(counts), counts.stride(0), counts.shape[0], float(repetition), float(presence),
+                                               float(frequency), _ptr(scratch), scratch.stride(0)), "lia_ctx_set_penalties")
         self._penalties = (counts, scratch, float(repetition), float(presence), float(frequency))
-        try:
-            self._point_penalties(0)
-        except Exception:
-            self._penalties = None
-            raise
 
-    def _point_penalties(self, r0):
-        """the table and the scratch from their row r0 on"""
-        counts, scratch, theta, presence, frequency = self._penalties
-        N.check(self.lib.lia_ctx_set_penalties(self.handle, ctypes.c_void_p(counts.data_ptr() + 2 * r0 * counts.stride(0)), counts.stride(0),
-                                               counts.shape[0] - r0, theta, presence, frequency,
-                                               ctypes.c_void_p(scratch.data_ptr() + 2 * r0 * scratch.stride(0)), scratch.stride(0)),
-                "lia_ctx_set_penalties")
+    @contextlib.contextmanager
+    def head_modifiers(self, token_mask=None, logprobs=None, shape=None, penalties=None):
+        """what a scheduler puts around one head call (and the sampler behind it): the allowed-token table (set_token_mask), the
+        log-probability request for a head on `shape` rows (set_logprob_sink) and the generation's penalties (penalties.Penalties:
+        its queued counts run, then its table is set) -- each where given, in that order -- and, however the block ends, none of
+        them on the context afterwards: no later head call sees a modifier that was meant for this one."""
+        try:
+            if token_mask is not None:
+                self.set_token_mask(token_mask)
+            if logprobs is not None:
+                self.set_logprob_sink(logprobs, shape)
+            if penalties is not None:
+                penalties.bind(self)
+            yield self
+        finally:
+            if token_mask is not None:
+                self.set_token_mask(None)
+            if logprobs is not None:
+                self.set_logprob_sink(None)
+            if penalties is not None:
+                self.set_penalties(None)
 
     def token_counts_add(self, counts, ids, generated, vocab=None, first=None, active=None, stream=None):
         """lia_token_counts_add: ids (int64 CUDA [B, n], unit column stride) are added to rows 0 .. B - 1 of counts -- generated False:
@@ -355,10 +361,7 @@ class Context:
         """lia_apply_penalties (the bare kernel): the rows of logits [M, vocab] (bf16, rows may be strided) rewritten under counts
         [M, >= vocab] -> out (a new [M, vocab] tensor when None; `logits` itself: in place)."""
         self._chk_counts(counts)
-        if not logits.is_cuda or logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
-            raise ValueError(f"logits: expected a [M, vocab] bf16 CUDA tensor with unit column stride, got {logits.dtype} {logits.device} "
-                             f"shape {tuple(logits.shape)} strides {logits.stride()}")
-        M, vocab = logits.shape
+        M, vocab = _chk_logits(logits)
         if counts.shape[0] < M:
             raise ValueError(f"logits has {M} rows, the count table {counts.shape[0]}")
         if out is None:
@@ -371,58 +374,34 @@ class Context:
                                              self._st(stream)), "lia_apply_penalties")
         return out
 
-    LM_HEAD_ROWS = 256       # rows per lia_lm_head call (its argmax scratch is sized for that many)
-
-    def lm_head(self, hidden, lnw, lnb, emb, eps=1e-5, suppress_token=-1, stream=None):
-        """final LN + tied lm_head on the LAST position + argmax (models.py:424-431, greedy_search.py:367).  A batch beyond 256 rows
-        (the reference's --batch-size 900 ... 1580 lines, llm/scripts/cxl_offloading.sh:13-39) goes through in chunks of 256 rows:
-        rows are independent, the results are those of one call.  With a token mask set (set_token_mask) chunk b0 reads the table
-        from its row b0 on; the table is pointed back at row 0 afterwards.  A log-probability sink (set_logprob_sink) and the penalties
-        (set_penalties: count table and scratch) likewise."""
-        for t in (hidden, lnw, lnb, emb):
+    def _lm_head(self, name, norm, head, hidden, eps, suppress_token, stream):
+        for t in (hidden,) + norm + (head,):
             _chk(t)
         B, T, H = hidden.shape
-        vocab = emb.shape[0]
-        logits = torch.empty((B, vocab), dtype=torch.bfloat16, device=hidden.device)
+        vocab = head.shape[0]
         self.token_mask_fits(vocab)
+        logits = torch.empty((B, vocab), dtype=torch.bfloat16, device=hidden.device)
         nxt = torch.empty((B,), dtype=torch.int64, device=hidden.device)
-        tm = self._token_mask if B > self.LM_HEAD_ROWS else None
-        if tm is not None and 1 < tm.shape[0] < B:
-            raise ValueError(f"lia_lm_head: the call has {B} rows, the token mask table {tm.shape[0]}")
-        lp = self._logprob_sink if B > self.LM_HEAD_ROWS else None
-        if lp is not None and lp.chosen.numel() < B:
-            raise ValueError(f"lia_lm_head: the call has {B} rows, the log-probability sink {lp.chosen.numel()}")
-        pn = self._penalties if B > self.LM_HEAD_ROWS else None
-        if pn is not None and pn[0].shape[0] < B:
-            raise ValueError(f"lia_lm_head: the call has {B} rows, the count table {pn[0].shape[0]}")
-        try:
-            for b0 in range(0, B, self.LM_HEAD_ROWS):
-                nb = min(self.LM_HEAD_ROWS, B - b0)
-                if tm is not None and b0:
-                    self._point_token_mask(tm, b0)
-                if lp is not None and b0:
-                    self._point_logprob_sink(lp, b0)
-                if pn is not None and b0:
-                    self._point_penalties(b0)
-                N.check(self.lib.lia_lm_head(self.handle, _ptr(hidden[b0:b0 + nb]), nb, T, H, _ptr(lnw), _ptr(lnb), _ptr(emb), vocab, eps, suppress_token,
-                                             _ptr(logits[b0:b0 + nb]), _ptr(nxt[b0:b0 + nb]), self._st(stream)), "lia_lm_head")
-        finally:
-            if tm is not None:
-                self._point_token_mask(tm, 0)
-            if lp is not None:
-                self._point_logprob_sink(lp, 0)
-            if pn is not None:
-                self._point_penalties(0)
+        N.check(getattr(self.lib, name)(self.handle, _ptr(hidden), B, T, H, *[_ptr(t) for t in norm], _ptr(head), vocab, eps, suppress_token,
+                                        _ptr(logits), _ptr(nxt), self._st(stream)), name)
         return logits, nxt
+
+    def lm_head(self, hidden, lnw, lnb, emb, eps=1e-5, suppress_token=-1, stream=None):
+        """lia_lm_head: final LN + tied lm_head on the LAST position of hidden [B, T, H] + argmax (models.py:424-431,
+        greedy_search.py:367) -> (logits bf16 [B, vocab], ids int64 [B]).  Any B: the library walks a batch beyond 256 rows (the
+        reference's --batch-size 900 ... 1580 lines, llm/scripts/cxl_offloading.sh:13-39) in chunks of 256, and row i reads row i
+        of a token mask, a log-probability sink and the penalties' tables in every chunk."""
+        return self._lm_head("lia_lm_head", (lnw, lnb), emb, hidden, eps, suppress_token, stream)
+
+    def llama_lm_head(self, hidden, normw, lm, eps=1e-5, suppress_token=-1, stream=None):
+        """lia_llama_lm_head: lm_head with the final RMSNorm and the untied lm_head of a Llama"""
+        return self._lm_head("lia_llama_lm_head", (normw,), lm, hidden, eps, suppress_token, stream)
 
     def sample(self, logits, temperature, top_k, top_p, uniforms, suppress_token=-1, stats=None, stream=None):
         """lia_sample: temperature -> top-k -> top-p -> one draw per row of logits [B, vocab] (bf16, rows may be strided) with
         uniforms [B] (float32, in [0, 1)).  Returns the ids (int64 [B]); stats (float32 [B, 4], optional) receives per row t_k, the
         top-p boundary, the kept count and the kept mass.  Any B: rows are independent."""
-        if not logits.is_cuda or logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
-            raise ValueError(f"logits: expected a [B, vocab] bf16 CUDA tensor with unit column stride, got {logits.dtype} {logits.device} "
-                             f"shape {tuple(logits.shape)} strides {logits.stride()}")
-        B, vocab = logits.shape
+        B, vocab = _chk_logits(logits, "B")
         _chk(uniforms, torch.float32)
         self.token_mask_fits(vocab)
         if uniforms.numel() != B:
@@ -440,10 +419,7 @@ class Context:
         """lia_token_logprobs: per row of logits [M, vocab] (bf16, rows may be strided) the log-probability of targets[r] (int64
         [M], -1: none -> 0.0) under the row's softmax, and the row's greedy token (first maximal index).  Returns (float32 [M],
         int64 [M]) on the device."""
-        if not logits.is_cuda or logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
-            raise ValueError(f"logits: expected a [M, vocab] bf16 CUDA tensor with unit column stride, got {logits.dtype} {logits.device} "
-                             f"shape {tuple(logits.shape)} strides {logits.stride()}")
-        M, vocab = logits.shape
+        M, vocab = _chk_logits(logits)
         _chk(targets, torch.int64)
         if targets.numel() != M:
             raise ValueError(f"targets has {targets.numel()} entries, logits {M} rows")
@@ -501,44 +477,37 @@ class Context:
                            torch.empty((1,), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int64, device=dev))
         return B, T, H, out
 
+    def _verify(self, name, norm, head, hidden, block_ids, eps, suppress_token, n_suppress, active, stream):
+        """n_suppress: the bound of every row, or (lia_lm_verify_rows) an int32 [B] device tensor of one bound per row"""
+        for t in norm + (head,):
+            _chk(t)
+        per_row = isinstance(n_suppress, torch.Tensor)
+        if per_row:
+            _chk(n_suppress, torch.int32)
+        B, T, H, out = self._verify_args(hidden, block_ids, active)
+        if per_row and n_suppress.numel() != B:
+            raise ValueError(f"n_suppress_rows has {n_suppress.numel()} entries, block_ids {B} rows")
+        vocab = head.shape[0]
+        self.token_mask_fits(vocab)
+        N.check(getattr(self.lib, name)(self.handle, _ptr(hidden), H, B, T, H, *[_ptr(t) for t in norm], _ptr(head), vocab, eps,
+                                        int(suppress_token), _ptr(n_suppress) if per_row else int(n_suppress), _ptr(block_ids), _ptr(active),
+                                        _ptr(out.greedy), _ptr(out.accepted), _ptr(out.common), _ptr(out.next), self._st(stream)), name)
+        return out
+
     def lm_verify(self, hidden, lnw, lnb, emb, block_ids, eps=1e-5, suppress_token=-1, n_suppress=0, active=None, stream=None):
         """lia_lm_verify: final LN + tied lm_head on every row of hidden [B, T, H] (lm_score's chunks), the greedy token of every
         block position (suppress_token counts as -inf at positions < n_suppress) and what block_ids [B, T] = [pending | draft]
         (int64, device) accepts of it; active (int32 [B], device, or None): rows with 0 never limit `common`.  -> VerifyResult."""
-        for t in (lnw, lnb, emb):
-            _chk(t)
-        B, T, H, out = self._verify_args(hidden, block_ids, active)
-        self.token_mask_fits(emb.shape[0])
-        N.check(self.lib.lia_lm_verify(self.handle, _ptr(hidden), H, B, T, H, _ptr(lnw), _ptr(lnb), _ptr(emb), emb.shape[0], eps,
-                                       int(suppress_token), int(n_suppress), _ptr(block_ids), _ptr(active), _ptr(out.greedy),
-                                       _ptr(out.accepted), _ptr(out.common), _ptr(out.next), self._st(stream)), "lia_lm_verify")
-        return out
+        return self._verify("lia_lm_verify", (lnw, lnb), emb, hidden, block_ids, eps, suppress_token, int(n_suppress), active, stream)
 
     def lm_verify_rows(self, hidden, lnw, lnb, emb, block_ids, n_suppress_rows, eps=1e-5, suppress_token=-1, active=None, stream=None):
         """lia_lm_verify_rows: lm_verify with one bound per row -- suppress_token counts as -inf at block positions
         t < n_suppress_rows[b] (int32 [B], device, each in [0, T])."""
-        for t in (lnw, lnb, emb):
-            _chk(t)
-        _chk(n_suppress_rows, torch.int32)
-        B, T, H, out = self._verify_args(hidden, block_ids, active)
-        if n_suppress_rows.numel() != B:
-            raise ValueError(f"n_suppress_rows has {n_suppress_rows.numel()} entries, block_ids {B} rows")
-        self.token_mask_fits(emb.shape[0])
-        N.check(self.lib.lia_lm_verify_rows(self.handle, _ptr(hidden), H, B, T, H, _ptr(lnw), _ptr(lnb), _ptr(emb), emb.shape[0], eps,
-                                            int(suppress_token), _ptr(n_suppress_rows), _ptr(block_ids), _ptr(active), _ptr(out.greedy),
-                                            _ptr(out.accepted), _ptr(out.common), _ptr(out.next), self._st(stream)), "lia_lm_verify_rows")
-        return out
+        return self._verify("lia_lm_verify_rows", (lnw, lnb), emb, hidden, block_ids, eps, suppress_token, n_suppress_rows, active, stream)
 
     def llama_lm_verify(self, hidden, normw, lm, block_ids, eps=1e-5, suppress_token=-1, n_suppress=0, active=None, stream=None):
         """lia_llama_lm_verify: lm_verify with the final RMSNorm and the untied lm_head of a Llama"""
-        for t in (normw, lm):
-            _chk(t)
-        B, T, H, out = self._verify_args(hidden, block_ids, active)
-        self.token_mask_fits(lm.shape[0])
-        N.check(self.lib.lia_llama_lm_verify(self.handle, _ptr(hidden), H, B, T, H, _ptr(normw), _ptr(lm), lm.shape[0], eps,
-                                             int(suppress_token), int(n_suppress), _ptr(block_ids), _ptr(active), _ptr(out.greedy),
-                                             _ptr(out.accepted), _ptr(out.common), _ptr(out.next), self._st(stream)), "lia_llama_lm_verify")
-        return out
+        return self._verify("lia_llama_lm_verify", (normw,), lm, hidden, block_ids, eps, suppress_token, int(n_suppress), active, stream)
 
     def _verify_sample(self, name, norm, head, hidden, block_ids, block, eps, suppress_token, n_suppress, n_suppress_rows, active,
                        return_logits, return_p_draft, stream):

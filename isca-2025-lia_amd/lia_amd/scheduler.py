@@ -126,7 +126,47 @@ def check_verify_rows(block_ids, kv_state, row_lens, flags, n_gpu, L):
                          f"need {int(row_lens.max()) + T}")
 
 
-class OffloadScheduler:
+def verify_head(ctx, head, hidden, ids_dev, act_dev, suppress_token, n_suppress=0, n_suppress_rows=None, sampler=None, rejector=None,
+                return_logits=False):
+    """the verify head of one pass, for every scheduler: rejection verification with a rejector, else the sampled head with a sampler,
+    else the greedy one; n_suppress_rows (int32 [B], device: row mode) in place of n_suppress.  head: (norm tensors, head weight, eps,
+    family prefix of the ops.Context methods -- "" or "llama_").  -> ops.VerifyResult"""
+    norm, weight, eps, family = head
+    if rejector is not None:
+        return getattr(ctx, family + "lm_verify_reject")(hidden, *norm, weight, ids_dev, rejector, eps, suppress_token, n_suppress,
+                                                         active=act_dev, return_logits=return_logits, return_probs=True)
+    if sampler is not None:
+        return getattr(ctx, family + "lm_verify_sample")(hidden, *norm, weight, ids_dev, sampler, eps, suppress_token, n_suppress,
+                                                         n_suppress_rows=n_suppress_rows, active=act_dev, return_logits=return_logits,
+                                                         return_p_draft=True)
+    if n_suppress_rows is not None:
+        return getattr(ctx, family + "lm_verify_rows")(hidden, *norm, weight, ids_dev, n_suppress_rows, eps, suppress_token, act_dev)
+    return getattr(ctx, family + "lm_verify")(hidden, *norm, weight, ids_dev, eps, suppress_token, n_suppress, act_dev)
+
+
+class HeadModifierHooks:
+    """what generation.generate() asks of a scheduler about the head modifiers, shared by OffloadScheduler and LlamaScheduler: a table
+    is passed per call -- forward(token_mask=, penalties=) / verify(token_mask=) set it on the library context around their head call
+    (ops.Context.head_modifiers) -- and these clear the context when a generation ends, also after an exception."""
+
+    supports_penalties = True         # forward(penalties=): generate()'s repetition / presence / frequency penalties
+
+    def set_token_mask(self, mask):
+        """None only: no allowed-token table on the library context -- every later head call is the unmasked one"""
+        if mask is not None:
+            raise ValueError("set_token_mask takes None only: a table is passed per call, forward(token_mask=) / verify(token_mask=)")
+        if self.ctx is not None:
+            self.ctx.set_token_mask(None)
+
+    def set_penalties(self, table):
+        """None only: no count table on the library context"""
+        if table is not None:
+            raise ValueError("set_penalties takes None only: the table is passed per call, forward(penalties=)")
+        if self.ctx is not None:
+            self.ctx.set_penalties(None)
+
+
+class OffloadScheduler(HeadModifierHooks):
     """forward(input_ids, kv_state, **lia flags) -> (logits [B,vocab], next_ids [B]) on the device."""
 
     resident_packed = False     # (class-level: a scheduler built without __init__ holds its residents raw)
@@ -337,23 +377,10 @@ class OffloadScheduler:
         finally:
             if s.split_opt:
                 ctx.set_option(N.LIA_OPT_SPLIT_DECODE, 0)
-        if token_mask is not None:
-            ctx.set_token_mask(token_mask)
-        if logprobs is not None:
-            ctx.set_logprob_sink(logprobs, (s.B,))
-        try:
-            if penalties is not None:
-                penalties.bind(ctx)
+        with ctx.head_modifiers(token_mask, logprobs, (s.B,), penalties):
             logits, nxt = ctx.lm_head(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, sh.ln_eps, suppress_token)
             if sampler is not None:
                 nxt = sampler(ctx, logits, suppress_token)
-        finally:
-            if token_mask is not None:
-                ctx.set_token_mask(None)
-            if logprobs is not None:
-                ctx.set_logprob_sink(None)
-            if penalties is not None:
-                ctx.set_penalties(None)
         self._deliver(s, kv_state)
         return logits, nxt
 
@@ -435,33 +462,18 @@ class OffloadScheduler:
                 hidden = self._run_layers(s, kv_state)
         finally:
             ctx.set_option(N.LIA_OPT_BLOCK_ATTENTION, 0)
-        if token_mask is not None:
-            ctx.set_token_mask(token_mask)
-        if logprobs is not None:
-            ctx.set_logprob_sink(logprobs, (B, T))
-        try:
-            res = self._verify_head(ctx, hidden, ids_dev, act_dev, suppress_token, n_suppress, sampler, rejector, return_logits)
-        finally:
-            if token_mask is not None:
-                ctx.set_token_mask(None)
-            if logprobs is not None:
-                ctx.set_logprob_sink(None)
+        with ctx.head_modifiers(token_mask, logprobs, (B, T)):
+            res = verify_head(ctx, self._head(), hidden, ids_dev, act_dev, suppress_token, n_suppress, sampler=sampler, rejector=rejector,
+                              return_logits=return_logits)
         self._deliver(s, kv_state)
         common = int(res.common.item())
         kv_state.len = pos0 + common + 1
         return res, common
 
-    def _verify_head(self, ctx, hidden, ids_dev, act_dev, suppress_token, n_suppress, sampler, rejector, return_logits):
-        m, sh = self.model, self.model.shape
-        if rejector is not None:
-            res = ctx.lm_verify_reject(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, rejector, sh.ln_eps, suppress_token,
-                                       n_suppress, active=act_dev, return_logits=return_logits, return_probs=True)
-        elif sampler is None:
-            res = ctx.lm_verify(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, sh.ln_eps, suppress_token, n_suppress, act_dev)
-        else:
-            res = ctx.lm_verify_sample(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, sampler, sh.ln_eps, suppress_token,
-                                       n_suppress, active=act_dev, return_logits=return_logits, return_p_draft=True)
-        return res
+    def _head(self):
+        """verify_head's description of this model's head: (norm tensors, head weight, eps, family prefix of the ops.Context methods)"""
+        m = self.model
+        return (m.final_ln_w, m.final_ln_b), m.embed_tokens, m.shape.ln_eps, ""
 
     def verify_rows(self, block_ids, kv_state, row_lens, suppress_token=-1, n_suppress_rows=None, active=None, prefill_policy=1,
                     decoding_policy=1, no_overlap=False, pin_weight=False, gpu_percentage=0, num_minibatch=1, enable_cxl=False,
@@ -499,34 +511,12 @@ class OffloadScheduler:
                 hidden = self._run_layers(s, kv_state)
             finally:
                 ctx.set_row_lens(None)
-            if sampler is None:
-                res = ctx.lm_verify_rows(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, nsup_dev, sh.ln_eps, suppress_token, act_dev)
-            else:
-                res = ctx.lm_verify_sample(hidden, m.final_ln_w, m.final_ln_b, m.embed_tokens, ids_dev, sampler, sh.ln_eps, suppress_token,
-                                           n_suppress_rows=nsup_dev, active=act_dev, return_logits=return_logits, return_p_draft=True)
+            res = verify_head(ctx, self._head(), hidden, ids_dev, act_dev, suppress_token, n_suppress_rows=nsup_dev, sampler=sampler,
+                              return_logits=return_logits)
             self._deliver(s, kv_state)
         finally:
             kv_state.len = len0
         return res
-
-    def set_token_mask(self, mask):
-        """None (what generate() calls when a constrained generation ends, also after an exception): no allowed-token table on the
-        library context -- every later head call is the unmasked one.  forward(token_mask=) / verify(token_mask=) set a table
-        themselves, around their head call."""
-        if mask is not None:
-            raise ValueError("set_token_mask takes None only: a table is passed per call, forward(token_mask=) / verify(token_mask=)")
-        if self.ctx is not None:
-            self.ctx.set_token_mask(None)
-
-    supports_penalties = True         # forward(penalties=): generate()'s repetition / presence / frequency penalties
-
-    def set_penalties(self, table):
-        """None only (generate() when a penalised generation ends, also after an exception): no count table on the library context.
-        forward(penalties=) sets one itself, around its head call."""
-        if table is not None:
-            raise ValueError("set_penalties takes None only: the table is passed per call, forward(penalties=)")
-        if self.ctx is not None:
-            self.ctx.set_penalties(None)
 
     # -- left-padded batches (generation.generate(..., attention_mask=)) -----------------------------------------------------
     def set_key_starts(self, starts):

@@ -134,6 +134,92 @@ def test_lm_head_chunks_beyond_256_rows(ctx):
         ctx.set_penalties(None)
 
 
+def _llama_head_by_hand(torch, ctx, inp, mask, n_top, table, lds, bounds):
+    """lia_llama_lm_head through the raw ABI, one call per (r0, n) of bounds, every modifier pointed at its row r0 by hand: mask
+    (int32 [rows, W]; one row: broadcast), a sink of n_top alternatives, the count table (int16 [rows, ldc]) with a scratch of pitch lds.
+    -> logits, ids, (chosen, top_ids, top_logprobs), scratch"""
+    from lia_amd import _native as N
+    hidden, nw, _, head = inp
+    B, T, _ = hidden.shape
+    lib, h = ctx.lib, ctx.handle
+    at = lambda t, off: ctypes.c_void_p(t.data_ptr() + off)          # noqa: E731
+    logits = torch.zeros((B, V), dtype=torch.bfloat16, device="cuda")
+    nxt = torch.full((B,), -9, dtype=torch.int64, device="cuda")
+    chosen = torch.zeros(B, dtype=torch.float32, device="cuda")
+    top_ids = torch.full((B, n_top), -9, dtype=torch.int64, device="cuda")
+    top = torch.zeros((B, n_top), dtype=torch.float32, device="cuda")
+    scratch = torch.zeros((B, lds), dtype=torch.bfloat16, device="cuda")
+    ldm = 0 if mask.shape[0] == 1 else mask.shape[1]
+    ldc = table.shape[1]
+    torch.cuda.synchronize()
+    try:
+        for r0, n in bounds:
+            N.check(lib.lia_ctx_set_token_mask(h, at(mask, 4 * r0 * ldm), ldm, B - r0 if ldm else 1), "lia_ctx_set_token_mask")
+            N.check(lib.lia_ctx_set_logprob_sink(h, n_top, at(chosen, 4 * r0), at(top_ids, 8 * r0 * n_top), at(top, 4 * r0 * n_top), B - r0),
+                    "lia_ctx_set_logprob_sink")
+            N.check(lib.lia_ctx_set_penalties(h, at(table, 2 * r0 * ldc), ldc, B - r0, *SETTINGS, at(scratch, 2 * r0 * lds), lds),
+                    "lia_ctx_set_penalties")
+            N.check(lib.lia_llama_lm_head(h, at(hidden, 2 * r0 * T * H), n, T, H, _p(nw), _p(head), V, EPS, -1, at(logits, 2 * r0 * V),
+                                          at(nxt, 8 * r0), ctypes.c_void_p(ctx.stream)), "lia_llama_lm_head")
+    finally:
+        lib.lia_ctx_set_token_mask(h, None, 0, 0)
+        lib.lia_ctx_set_logprob_sink(h, 0, None, None, None, 0)
+        lib.lia_ctx_set_penalties(h, None, 0, 0, 1.0, 0.0, 0.0, None, 0)
+    ctx.synchronize()
+    return logits, nxt, (chosen, top_ids, top), scratch
+
+
+@pytest.mark.parametrize("broadcast_mask", [False, True])
+def test_llama_head_of_257_rows_offsets_every_modifier(ctx, broadcast_mask):
+    """B = 257 through Context.llama_lm_head with a mask table, a sink (n_top = 3) and a count table all set: logits, ids, sink rows
+    and scratch rows are bit for bit those of a 256-row call and a 1-row call made through the raw ABI with every table pointed at
+    the call's first row by hand.  Row 256 differs from row 0 in its hidden row, its mask row and its count row, and its id is
+    another under row 0's: a second chunk that read any table from row 0 would be caught.  Also with ONE broadcast mask row."""
+    import torch
+    from lia_amd import ops
+    B, n_top = 257, 3
+    inp = _head_inputs(torch, "llama", B, 29)
+    hidden, nw, _, head = inp
+    raw_logits, raw_ids = _lm_head(torch, ctx, "llama", inp)
+    lg = _u16(raw_logits)
+    table = _table(B, V, raw_ids, 15)
+    rows = PR.penalty_ref(lg, table, *SETTINGS)
+    allowed = np.random.RandomState(6).rand(B, V) < 0.5
+    allowed[np.arange(B), PR.first_argmax(rows)] = False             # the penalised winner is forbidden: both must act
+    allowed[:, 5] = True
+    if broadcast_mask:
+        allowed[:] = allowed[256]
+    want = MR.first_argmax(PR.bf16_to_f32(rows), allowed)
+    # row 256 under row 0's tables is another row: the hidden rows differ, and so does the id under row 0's mask / counts
+    assert not torch.equal(hidden[256], hidden[0]) and (table[256] != table[0]).any()
+    assert MR.first_argmax(PR.bf16_to_f32(PR.penalty_ref(lg[256:], table[:1], *SETTINGS)), allowed[256:])[0] != want[256]
+    if not broadcast_mask:
+        assert (allowed[256] != allowed[0]).any() and MR.first_argmax(PR.bf16_to_f32(rows[256:]), allowed[:1])[0] != want[256]
+    mask = torch.from_numpy(MR.pack(allowed[256:] if broadcast_mask else allowed)).cuda()
+    counts = _dev(torch, table)
+    for lds in (V, V + 8):
+        hand = _llama_head_by_hand(torch, ctx, inp, mask, n_top, counts, lds, ((0, 256), (256, 1)))
+        req = ops.LogprobRequest(n_top)
+        scratch = torch.zeros((B, lds), dtype=torch.bfloat16, device="cuda")
+        torch.cuda.synchronize()
+        ctx.set_token_mask(mask)
+        ctx.set_logprob_sink(req, (B,))
+        ctx.set_penalties(counts, *SETTINGS, scratch=scratch)
+        try:
+            logits, ids = ctx.llama_lm_head(hidden, nw, head, EPS)
+            ctx.synchronize()
+        finally:
+            ctx.set_token_mask(None)
+            ctx.set_logprob_sink(None)
+            ctx.set_penalties(None)
+        assert torch.equal(logits, hand[0]) and torch.equal(logits, raw_logits), lds
+        assert torch.equal(ids, hand[1]) and (ids.cpu().numpy() == want).all(), lds
+        for got, ref in zip((req.chosen, req.top_ids, req.top_logprobs), hand[2]):
+            assert torch.equal(got.view(torch.int32) if got.dtype == torch.float32 else got,
+                               ref.view(torch.int32) if ref.dtype == torch.float32 else ref), lds
+        assert torch.equal(scratch.view(torch.int16), hand[3].view(torch.int16)) and (_u16(scratch)[:, :V] == rows).all(), lds
+
+
 def _draw(torch, ctx, logits, u, tau, k, p, suppress=-1):
     stats = torch.full((logits.shape[0], 4), -7.0, device="cuda")
     torch.cuda.synchronize()
@@ -294,3 +380,28 @@ def test_block_and_score_heads_refuse_by_name(ctx):
     ctx.synchronize()
     for llama, name in ((False, "lia_lm_verify_reject"), (True, "lia_llama_lm_verify_reject")):
         assert reject(llama) == N.LIA_ERR_INVALID and f"{name}: NULL rejector" in err()
+
+
+def test_the_first_fault_reported_keeps_its_place(ctx):
+    """a call that is wrong in two ways reports what it always reported: a rejection head with penalties set AND a one-token block
+    (T = 1) is refused for the penalties -- the modifiers a head does not take come before its own arguments"""
+    import torch
+    from lia_amd import _native as N
+    B, T = 3, 1
+    _, nw, nb, head = _head_inputs(torch, "opt", B, 23)
+    hid = torch.zeros((B, T, H), dtype=torch.bfloat16, device="cuda")
+    blk = torch.zeros((B, T), dtype=torch.int64, device="cuda")
+    out = [torch.zeros((B, T), dtype=torch.int64, device="cuda"), torch.zeros((B, T), dtype=torch.int32, device="cuda"),
+           torch.zeros(B, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda"),
+           torch.zeros(B, dtype=torch.int64, device="cuda")]
+    torch.cuda.synchronize()
+    ctx.set_penalties(torch.zeros((B * T, V), dtype=torch.int16, device="cuda"), 1.2)
+    try:
+        for name, norm in (("lia_lm_verify_reject", [_p(nw), _p(nb)]), ("lia_llama_lm_verify_reject", [_p(nw)])):
+            rc = getattr(ctx.lib, name)(ctx.handle, _p(hid), H, B, T, H, *norm, _p(head), V, EPS, -1, 0, None, None, _p(blk), None,
+                                        *[_p(t) for t in out], None, None, None, None, None)
+            assert rc == N.LIA_ERR_INVALID
+            assert ctx.lib.lia_last_error().decode() == (f"{name}: penalties are set (lia_ctx_set_penalties): every block position would need "
+                                                         "its own counts -- penalties are not applied under speculation")
+    finally:
+        ctx.set_penalties(None)

@@ -276,6 +276,43 @@ def test_257_rows_through_ops_lm_head_repoint_the_table_per_chunk(ctx):
         ctx.set_token_mask(None)
 
 
+def test_257_rows_through_the_raw_call(ctx):
+    """lia_lm_head itself serves 257 rows (chunks of 256 inside the library): with a per-row table, what ops.Context.lm_head returns;
+    with a 100-row table LIA_ERR_INVALID by name, the whole batch checked before anything is launched -- the ids keep their sentinel"""
+    import torch
+    from lia_amd import _native as N
+    B, V = 257, 256
+    inp = _head_inputs(torch, "opt", B, V, 3)
+    hidden, nw, nb, head = inp
+    _, raw_ids = _lm_head(torch, ctx, "opt", inp)
+    allowed = np.random.RandomState(8).rand(B, V) < 0.5
+    allowed[np.arange(B), raw_ids] = False                      # every row's unmasked winner is forbidden
+    allowed[256] = False
+    allowed[256, [5, 200]] = True
+
+    def raw():
+        logits = torch.full((B, V), 7.0, dtype=torch.bfloat16, device="cuda")
+        nxt = torch.full((B,), -9, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        rc = ctx.lib.lia_lm_head(ctx.handle, _p(hidden), B, 1, H, _p(nw), _p(nb), _p(head), V, EPS, -1, _p(logits), _p(nxt),
+                                 ctypes.c_void_p(ctx.stream))
+        ctx.synchronize()
+        return rc, logits, nxt.cpu().numpy()
+
+    ctx.set_token_mask(_dev_mask(torch, allowed))
+    try:
+        want_logits, want_ids = _lm_head(torch, ctx, "opt", inp)
+        rc, logits, ids = raw()
+        assert rc == N.LIA_OK and torch.equal(logits, want_logits) and (ids == want_ids).all() and ids[256] in (5, 200)
+        ctx.set_token_mask(_dev_mask(torch, allowed[:100]))
+        rc, _, ids = raw()
+        assert rc == N.LIA_ERR_INVALID
+        assert "lia_lm_head: the call has 257 rows, the token mask table 100 (lia_ctx_set_token_mask)" in ctx.lib.lia_last_error().decode()
+        assert (ids == -9).all()
+    finally:
+        ctx.set_token_mask(None)
+
+
 def _verify_setup(torch, family, B, T, V, seed):
     inp = _head_inputs(torch, family, B, V, seed, T=T)
     allowed = np.random.RandomState(seed + 1).rand(B, T, V) < 0.5           # a different mask per (row, position)
